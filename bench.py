@@ -7,9 +7,18 @@ on synthetic data.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  `value` = whole-job images/sec with inputs resident in HBM.  `roofline` is the
-dominant kernel family measured with events on the launch stream in an instrumented pass after the timed region;
-`cpu_baseline` is the CPU oracle (oracle/ref_cpu.py, kind "port") timed on this host on a bounded sample."""
+Prints ONE JSON line (rank 0).  `value` = whole-job images/sec with inputs resident in HBM.  A plain run sets up, warms up,
+times the --steps steps and prints the line; everything else it can measure runs only with --full (null otherwise):
+`roofline` is the dominant kernel family measured with events on the launch stream in an instrumented pass after the timed
+region, `parity_mode` a bounded f32 leg of the same workload, `cpu_baseline` the CPU oracle (oracle/ref_cpu.py, kind "port")
+timed on this host on a bounded sample.
+
+--dump-outputs DIR writes what a caller of the timed step receives from its last run, as float32 .npy files: loss.npy
+([total, ce, overlap]) and the optimizer's flat arenas after the step, params.npy (weights, then BatchNorm running statistics)
+and ema.npy, each a fixed, seeded sample of DUMP_MAX elements where the arena is larger.  Inputs and initial weights are seeded,
+but the bf16 path is not bitwise reproducible (weight gradients and BatchNorm sums are accumulated with f32 atomics): two runs
+of one build agree to about 1e-5 in the loss and 1e-3 (relative L2) in the arenas.  The step's weight gradients themselves are
+not dumped: that accumulation order moves them by tens of percent from run to run, so they cannot tell two builds apart."""
 from __future__ import annotations
 
 import argparse
@@ -25,6 +34,7 @@ F_IMG = 129.3e9          # cfg2: algorithmic FLOP / image, fwd+bwd, live graph, 
 PEAK_BF16 = 2500.0       # TFLOP/s dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_F32 = 157.3         # TFLOP/s f32 MFMA
 PEAK_HBM = 8000.0        # GB/s
+DUMP_MAX = 1 << 22       # --dump-outputs: elements per array (16 MB of float32; both arenas + the loss stay under 64 MB)
 
 
 CW = [1, 2, 25, 2, 10, 3, 25, 10, 5, 15, 25, 1]          # unet-lite/yolo5-seg/weight.yaml:3-14
@@ -127,6 +137,24 @@ def spawn_ranks(n: int) -> int:
     return 0
 
 
+def dump_outputs(out_dir: str, items, opt) -> None:
+    """--dump-outputs: the loss scalars of the last step and the optimizer's weight arenas after it, as float32 .npy files.  An arena
+    larger than DUMP_MAX is sampled at the same DUMP_MAX sorted positions on every run (legacy RandomState: a frozen stream)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(()).cpu() for v in items]),
+              "params": opt.params_arena, "ema": opt.ema_arena}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX:
+            idx = np.sort(np.random.RandomState(0).permutation(t.numel())[:DUMP_MAX])
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def parity_leg(ydl, args, wl, dev, imgs, tgts, out_hw):
     """A bounded leg of the SAME workload in parity mode (f32 storage and arithmetic, deterministic weight gradients): the mode every
     1e-4 claim against the reference is made in.  Fresh model and optimizer, eager launches (26 ms of GPU time per step hide the host),
@@ -180,6 +208,9 @@ def main():
     ap.add_argument("--bs", type=int, default=0, help="images per GPU (default: the workload's)")
     ap.add_argument("--size", type=int, default=0, help="input size (default: the workload's)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the instrumented roofline pass, the f32 parity leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dcn-offset-std", type=float, default=0.0,
                     help="DCNv3 workloads: re-draw the offset projections so that the sampling offsets have about this standard deviation "
@@ -190,7 +221,7 @@ def main():
     ap.add_argument("--eager", action="store_true", help="issue every launch from Python (no launch-list replay, no HIP graph)")
     ap.add_argument("--prioritize", type=int, default=0, help="replay the main chain on a high-priority stream, side work on low-priority ones")
     ap.add_argument("--try-hipgraph", action="store_true", help="also time the single-stream HIP-graph capture of the step")
-    ap.add_argument("--profile-json", default="", help="dump the per-launch event records of the instrumented pass")
+    ap.add_argument("--profile-json", default="", help="dump the per-launch event records of the instrumented pass (--full)")
     ap.add_argument("--graph-overlap", action="store_true", help="capture the side stream (wgrad / dead branch) into the graphs too")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--dp-algo", default="allreduce", choices=["allreduce", "rs_ag"],
@@ -202,6 +233,10 @@ def main():
     ap.add_argument("--no-parity-leg", action="store_true", help="skip the bounded f32 (parity-mode) leg after the timed region")
     ap.add_argument("--parity-steps", type=int, default=5)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.profile_json and not args.full:
+        ap.error("--profile-json records the instrumented pass, which only --full runs")
     wl = WORKLOADS[args.workload]
     args.bs = args.bs or wl["bs"]
     args.size = args.size or wl["size"]
@@ -354,8 +389,10 @@ def main():
             gstep = rstep = None
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
-            for _ in range(3):
-                step()
+        # the same number of re-warm steps whichever path won, so that the state the timed region starts from (and what
+        # --dump-outputs writes) does not depend on the choice
+        for _ in range(3):
+            step()
         if rank == 0:
             fmt = lambda v: "n/a" if v >= BIG else f"{v:.2f}"
             print(f"[bench] ms/step: eager {fmt(t_eager)}, replay {fmt(t_replay)}, hipgraph {fmt(t_graph)} -> {mode}", file=sys.stderr)
@@ -382,9 +419,11 @@ def main():
         dt = float(tt.item())
     loss_val = float(items[0])
     ips = args.bs * world * args.steps / dt
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, items, opt)
 
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # instrumented pass: every C-ABI launch bracketed by events on the stream it is launched on.  The second
         # stream is switched off here so that a kernel's duration is its own (in the timed region above wgrad and the
         # dead head branch overlap with the main chain, which inflates per-kernel durations but shortens the step)
@@ -472,7 +511,7 @@ def main():
         roof["end_to_end_mfma_frac"] = ips / world * flop_img / 1e12 / peak
 
     parity = None
-    if rank == 0 and world == 1 and args.dtype == "bf16" and not args.no_parity_leg:
+    if rank == 0 and world == 1 and args.full and args.dtype == "bf16" and not args.no_parity_leg:
         rstep = gstep = None                # the recorded step's private pool is not needed any more
         torch.cuda.synchronize()
         try:
@@ -482,7 +521,7 @@ def main():
             torch.cuda.synchronize()
 
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         base = cpu_baseline(wl, 2, args.size, args.cpu_steps if args.size <= 640 else 1)
 
     if rank == 0:

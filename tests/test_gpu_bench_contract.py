@@ -1,10 +1,11 @@
 """bench.py's output contract on a small instance of the default workload: exactly one JSON line on stdout with the fields the driver
-reads, a roofline object measured inside the run and a CPU baseline timed beside it."""
+reads; with --full also a roofline object measured inside the run and a CPU baseline timed beside it; what --dump-outputs writes."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +14,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--bs", "2", "--size", "128",
-                        "--cpu-steps", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--cpu-steps", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -37,6 +38,27 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     par = d["parity_mode"]
     assert par["dtype"] == "f32" and par["value"] > 0 and par["ms_per_step"] > 0 and "error" not in par
     assert abs(par["value"] - 2 * 1000.0 / par["ms_per_step"]) <= 1e-6 * par["value"]
+
+
+def test_plain_run_times_only_the_headline_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries the headline alone (no instrumented pass, f32 leg or CPU baseline); --dump-outputs writes the
+    last timed step's loss and the optimizer's weight arenas after it as float32, sampled to at most 64 MB in all"""
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--bs", "2", "--size", "128",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["dtype"] == "bf16" and d["ms_per_step"] > 0
+    assert abs(d["value"] - 2 * 1000.0 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    assert d["roofline"] is None and d["parity_mode"] is None and d["cpu_baseline"] is None
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert sorted(got) == ["ema", "loss", "params"]
+    assert all(a.dtype == np.float32 and a.ndim == 1 and np.isfinite(a).all() for a in got.values())
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 << 20
+    assert got["loss"].shape == (3,) and got["loss"][0] == np.float32(d["loss"])
+    assert np.abs(got["params"]).max() > 0 and np.abs(got["ema"]).max() > 0
 
 
 def test_plain_launch_with_gpus_2_starts_two_ranks():
