@@ -49,7 +49,8 @@ void ydl_debug_set(int key, int val);
 /* diagnostics: number of (kernel, device) launch-attribute initialisations done so far */
 int ydl_debug_attr_sets(void);
 /* diagnostics: name of the kernel instantiation the last call of an entry family launched (process-wide);
- * family 0 ydl_conv_fwd, 1 ydl_conv_dgrad, 2 ydl_conv_wgrad, 3 ydl_bn_finalize.  "" if none yet. */
+ * family 0 ydl_conv_fwd, 1 ydl_conv_dgrad, 2 ydl_conv_wgrad, 3 ydl_bn_finalize, 4 ydl_deform_bwd, 5 ydl_deform_gather.
+ * "" if none yet. */
 const char* ydl_debug_last_kernel(int family);
 
 /* ---- convolution as implicit GEMM on MFMA ------------------------------------------------------------
@@ -332,6 +333,24 @@ int ydl_dcnv3_bwd(int dtype, const void* input, const void* offset, const void* 
                   int dilation_h, int dilation_w, int group, int group_channels, float offset_scale,
                   int N, int H_in, int W_in, int H_out, int W_out, void* stream);
 
+/* ---- deformable convolution (torchvision.ops.deform_conv2d: DCNv1 with mask NULL, DCNv2 with a mask) --------------------------
+ * Column form: ydl_deform_gather writes col[pix][k*C + c] = mask * bilinear(x at the deformed tap k), k = i*kw + j, pix = (n*Ho + ho)*Wo
+ * + wo, in the compute dtype; with ones_column the element col[pix][kh*kw*C] is 1 (a bias as one more weight column); elements up to
+ * ldc are zero.  The convolution is then a 1x1 GEMM (ydl_conv_fwd / _fwd_sums, ydl_conv_dgrad, ydl_conv_wgrad) with Cin = kh*kw*C (+1)
+ * over col, whose weight [Cout][kh*kw*C] is the KRSC weight itself.  x: NHWC rows of ldx elements; offset: rows of ldo, (dy, dx)
+ * interleaved per kernel point and offset group, 2*G*kh*kw values; mask: rows of ldm, G*kh*kw values, or NULL; mask_sigmoid: the
+ * mask holds logits and the kernels apply the sigmoid (and its derivative).  G offset groups; channel c is in group c / (C/G).
+ * Validity is tested per bilinear corner (no outer test of the sampling position: see INTEGRATION.md for the -1 border). */
+int ydl_deform_gather(int dtype, const void* x, int ldx, const void* offset, int ldo, const void* mask, int ldm, int mask_sigmoid,
+                      void* col, int ldc, int ones_column, int N, int H, int W, int C, int Ho, int Wo, int kh, int kw,
+                      int sh, int sw, int ph, int pw, int dh, int dw, int G, void* stream);
+/* Backward from dcol (rows of ldc, the gradient of col): grad_input f32 [N][H][W][C] dense, ACCUMULATED with f32 atomics (zero it
+ * first; NULL = not needed); grad_offset f32 [pix][2*G*kh*kw] and grad_mask f32 [pix][G*kh*kw] (of the logits when mask_sigmoid)
+ * fully written, either may be NULL.  Kernel (ydl_debug_last_kernel(4)): the LDS-window kernel at 3x3 / stride 1 / dilation 1, the
+ * per-corner-atomic kernel otherwise (or with ydl_debug_set(20, 0)). */
+int ydl_deform_bwd(int dtype, const void* x, int ldx, const void* offset, int ldo, const void* mask, int ldm, int mask_sigmoid,
+                   const void* dcol, int ldc, float* grad_input, float* grad_offset, float* grad_mask, int N, int H, int W, int C,
+                   int Ho, int Wo, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int G, void* stream);
 
 /* ---- pieces of the DCNv3 module around the sampling op (models/ops_dcnv3/build/.../modules/dcnv3.py:50-136) ------------
  * depth-wise k x k convolution, stride 1, 'same' padding (the `dw_conv = Conv(c, c, k, g=c)` branch, :89);

@@ -58,6 +58,8 @@ def parse_opt(argv=None):
     p.add_argument("--optimizer", type=str, default="SGD")
     p.add_argument("--label-smoothing", type=float, default=0.0)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--dcn", default="substitute", choices=["substitute", "native"],
+                   help="C3_DCN / C2f_DCN rows: substitute C3 / C2f (default, as the benchmark) or build them natively (DeformConv2d on HIP)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f32"], help="compute dtype of the HIP kernels")
     p.add_argument("--steps-per-epoch", type=int, default=50, help="synthetic batches per epoch")
     p.add_argument("--lr0", type=float, default=0.01)
@@ -117,12 +119,13 @@ def build_model(opt):
         return getattr(ydl, cls_name)({"nc": 12}), loss_kind
     path = opt.cfg or os.path.join(ROOT, "yolo_dual_amd", "cfg", default_yaml)
     cfg = yaml.safe_load(open(path))
+    native = getattr(opt, "dcn", "substitute") == "native"
     for sec in ("backbone", "head"):
         for l in cfg[sec]:
-            if l[2] in ("C3_DCN", "C2f_DCN"):          # torchvision DeformConv2d blocks: parity unpinned, substituted like the benchmark
+            if l[2] in ("C3_DCN", "C2f_DCN") and not native:   # torchvision DeformConv2d blocks: parity unpinned, substituted like the benchmark
                 print(f"[train_seg] {l[2]} -> {l[2][:-4]} (torchvision deformable conv is not part of the reference; SURVEY §8c)")
                 l[2] = l[2][:-4]
-    model = getattr(ydl, cls_name)(cfg)
+    model = getattr(ydl, cls_name)(cfg, deformable=True) if native else getattr(ydl, cls_name)(cfg)
     model.img_size = [opt.imgsz, opt.imgsz]
     return model, loss_kind
 

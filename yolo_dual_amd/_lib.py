@@ -106,6 +106,8 @@ SIGNATURES = {
     "ydl_dcnv3_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _vp]),
     "ydl_dcnv3_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f,
                            _i, _i, _i, _i, _i, _vp]),
+    "ydl_deform_gather": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i] + [_i] * 15 + [_vp]),
+    "ydl_deform_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp] + [_i] * 15 + [_vp]),
     "ydl_dwconv_fwd": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_dwconv_dgrad": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_dwconv_wgrad_ws_bytes": (_i64, [_i, _i]),
@@ -168,7 +170,8 @@ def debug_epoch() -> int:
 
 
 def last_kernel(family: int) -> str:
-    """name of the kernel instantiation the last call of an entry family launched (0 fwd, 1 dgrad, 2 wgrad, 3 bn_finalize)"""
+    """name of the kernel instantiation the last call of an entry family launched (0 fwd, 1 dgrad, 2 wgrad, 3 bn_finalize,
+    4 deform_bwd, 5 deform_gather)"""
     return lib().ydl_debug_last_kernel(family).decode()
 
 

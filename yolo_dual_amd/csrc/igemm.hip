@@ -4819,6 +4819,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 //              key 10 = integer-factor bilinear resize backward (resize_bwd_int_kernel): 1 (default) on, 0 generic gather
 //              key 11 = row-walking resize forward: 1 (default) on, 0 element-indexed kernel
 //              key 12 = patch-form weight gradient of the space-to-depth stem (stemw_kernel): 1 (default) on, 0 tiled kernel
+//              key 20 = deformable-convolution backward with the LDS window (deform_bwd_window_kernel): 1 (default) on, 0 per-corner atomics
 //              key 19 = loader-wave ring kernel (igemm2l_kernel) where pick_cfg prefers it: 1 (default) on, 0 off
 //              key 18 = loader waves of the LDS-DMA weight-gradient kernel (wgrad3s_kernel): 4 (default) / 2 / 1 loader waves per CTA, 0 = wgrad3_kernel
 //              key 17 = weights-in-registers kernel for 3x3 / s1 over one 64-channel block (igemm2w_kernel): 1 (default) on, 0 off
@@ -4833,8 +4834,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 // after a change (yolo_dual_amd._lib.debug_set does).
 extern int g_resize_int, g_resize_rows;       // spatial.hip
 void ydl_dcn_debug_set(int key, int val);     // dcnv3.hip
+void ydl_deform_debug_set(int key, int val);  // deform.hip
 extern "C" void ydl_debug_set(int key, int val) {
     ydl_dcn_debug_set(key, val);
+    ydl_deform_debug_set(key, val);
     if (key == 0) g_wgrad_tr = val;
     if (key == 1) g_pw_enabled = val;
     if (key == 2) g_dgrad_merge = val;

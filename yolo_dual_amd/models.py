@@ -24,7 +24,8 @@ import torch.nn as nn
 import yaml
 
 from . import _lib as L
-from .modules import (GAM, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C3, C3_DCNV3, C3Common, C3k2, Concat,
+from .modules import (GAM, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C2f_DCN, C3, C3_DCN, C3_DCNCommon, C3_DCNV3,
+                      C3Common, C3k2, Concat,
                       Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region)
 from .tape import Tape, Var
 
@@ -53,7 +54,7 @@ class Softmax(nn.Module):
 
 def _kaiming_init(model: nn.Module, nonlinearity: str) -> None:
     for m in model.modules():
-        if isinstance(m, nn.Conv2d):
+        if isinstance(m, nn.Conv2d) and not getattr(m, "_keep_init", False):
             nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity=nonlinearity)
         elif isinstance(m, nn.BatchNorm2d):
             nn.init.constant_(m.weight, 1)
@@ -92,8 +93,9 @@ class _YamlSegModel(YdlModule):
     head_modules: Dict[str, type] = {}
     init_nonlinearity = "leaky_relu"
 
-    def __init__(self, cfg, num_classes: Optional[int] = None):
+    def __init__(self, cfg, num_classes: Optional[int] = None, deformable: bool = False):
         super().__init__()
+        self.deformable = deformable        # build the yaml's C3_DCN / C2f_DCN rows natively (DeformConv2d on the HIP kernels)
         if isinstance(cfg, str):
             with open(check_yaml(cfg), "r") as f:
                 self.yaml = yaml.safe_load(f)
@@ -126,6 +128,8 @@ class _YamlSegModel(YdlModule):
 
     # builders: ``Module(c1, *args)``; the yaml ``number`` column and the multiples are ignored (T3)
     def _make(self, table, module: str, c1: int, args, where: str):
+        if module in ("C3_DCN", "C2f_DCN") and self.deformable:
+            return {"C3_DCN": C3_DCN, "C2f_DCN": C2f_DCN}[module](c1, *args), args[0]
         if module in ("C3_DCN", "C2f_DCN"):
             raise NotImplementedError(
                 f"{module} wraps torchvision.ops.DeformConv2d, which is not part of the reference repository "
@@ -523,25 +527,27 @@ _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": 
                 "nn.Upsample": Upsample, "Upsample": Upsample, "C3_DCNV3": C3_DCNV3, "Bottleneck_DCNV3": Bottleneck_DCNV3}
 
 
-def parse_model(d: dict, ch: List[int]):
+def parse_model(d: dict, ch: List[int], deformable: bool = False):
     """models/yolo.py:299-382 for the block set of this path: resolves module names, applies depth/width gains
     (``n = max(round(n*gd), 1)``, ``c2 = make_divisible(c2*gw, 8)``), inserts ``n`` for C3, and tags every layer
-    with ``.i .f .type .np``.  Returns (nn.Sequential, sorted save-list)."""
+    with ``.i .f .type .np``.  Returns (nn.Sequential, sorted save-list).  ``deformable``: resolve ``C3_DCN`` to models/common.py's
+    DCNv2 block (C3_DCNCommon, n inserted like C3: models/yolo.py:321,327)."""
     gd, gw = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0)
     no = d.get("nc", 0)
     layers, save, c2 = [], [], ch[-1]
+    table = dict(_PARSE_TABLE, C3_DCN=C3_DCNCommon) if deformable else _PARSE_TABLE
     for i, (f, n, m, args) in enumerate(d["backbone"] + d["head"]):
-        if m not in _PARSE_TABLE:
+        if m not in table:
             raise NotImplementedError(f"parse_model: module {m} is outside the segmentation hot path")
-        cls = _PARSE_TABLE[m]
+        cls = table[m]
         args = [None if a == "None" else a for a in args]
         n = n_ = max(round(n * gd), 1) if n > 1 else n
-        if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3):
+        if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3, C3_DCNCommon):
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)
             args = [c1, c2, *args[1:]]
-            if cls in (C3Common, C3_DCNV3):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
+            if cls in (C3Common, C3_DCNV3, C3_DCNCommon):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
                 args.insert(2, n)
                 n = 1
         elif cls is Concat:
@@ -563,7 +569,7 @@ def parse_model(d: dict, ch: List[int]):
 class SegYoloModel(YdlModule):
     """BaseModel of models/yolo.py:114-125 restricted to this block set: ``model`` + ``save`` routing by ``m.f``."""
 
-    def __init__(self, cfg, ch: int = 3, nc: Optional[int] = None):
+    def __init__(self, cfg, ch: int = 3, nc: Optional[int] = None, deformable: bool = False):
         super().__init__()
         if isinstance(cfg, dict):
             self.yaml = deepcopy(cfg)
@@ -572,7 +578,7 @@ class SegYoloModel(YdlModule):
                 self.yaml = yaml.safe_load(f)
         if nc is not None:
             self.yaml["nc"] = nc
-        self.model, self.save = parse_model(self.yaml, [ch])
+        self.model, self.save = parse_model(self.yaml, [ch], deformable=deformable)
         _kaiming_init(self, "leaky_relu")
 
     def forward(self, x, augment=False, profile=False, visualize=False):

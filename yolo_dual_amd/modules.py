@@ -25,7 +25,8 @@ from .tape import Tape, Var, round_up, _p, _stream, zero_
 
 __all__ = ["autopad", "Conv", "C3", "C3Common", "Bottleneck", "C2f", "C3k2", "GAM", "SPPF", "Concat", "Upsample",
            "BasicBlock", "BottleneckBlock", "SegmentHead", "run_region", "Linear", "DCNv3", "DCNV3_YoLo", "Bottleneck_DCNV3",
-           "C3_DCNV3"]
+           "C3_DCNV3", "DeformConv2d", "C3_DCN", "C2f_DCN", "DCNv2",
+           "Bottleneck_DCN", "C3_DCNCommon"]
 
 
 def autopad(k, p=None, d=1):
@@ -700,6 +701,302 @@ class C2f(YdlModule):
         if self.add:
             return self.cv2._fwd(tape, cat, res=x, res_mode=L.RES_AFTER_ACT)
         return self.cv2._fwd(tape, cat)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# deformable convolution (torchvision.ops.DeformConv2d) and the script blocks built on it
+# ----------------------------------------------------------------------------------------------------------
+class DeformConv2d(YdlModule):
+    """``torchvision.ops.DeformConv2d(in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
+    bias=True)`` with ``forward(x, offset, mask=None)``; state_dict ``weight`` [out, in, kh, kw] (+ ``bias``).  Stand-alone
+    calls run yolo_dual_amd.deform.deform_conv2d; inside a taped block the op and the BatchNorm that follows it run through
+    ``Tape.deform_conv``.  Weight groups > 1 are not implemented."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True):
+        super().__init__()
+        if groups != 1:
+            raise NotImplementedError("DeformConv2d: weight groups > 1 are not implemented on the HIP path (every reference "
+                                      "call site uses groups=1)")
+        pair = lambda v: (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+        self.in_channels, self.out_channels, self.groups = in_channels, out_channels, groups
+        self.kernel_size, self.stride, self.padding, self.dilation = pair(kernel_size), pair(stride), pair(padding), pair(dilation)
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, *self.kernel_size))
+        self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))        # torchvision's reset_parameters
+        if self.bias is not None:
+            nn.init.uniform_(self.bias, -1 / math.sqrt(in_channels * self.kernel_size[0] * self.kernel_size[1]),
+                             1 / math.sqrt(in_channels * self.kernel_size[0] * self.kernel_size[1]))
+        self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)     # KRSC master
+
+    def forward(self, x, offset, mask=None):
+        from .deform import deform_conv2d
+        return deform_conv2d(x, offset, self.weight, self.bias, self.stride, self.padding, self.dilation, mask)
+
+    def extra_repr(self):
+        return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, "
+                f"padding={self.padding}, dilation={self.dilation}, bias={self.bias is not None}")
+
+
+class _DeformGemm:
+    """parameter holder of the 1x1 GEMM over a deformable column buffer, with Conv's interface for Tape.conv_bn_act: weight
+    [Cout][kh*kw*Cin (+1)] = the KRSC weight (+ the bias column), followed by the BatchNorm ``bn``.  Not a module: it only
+    points at the DeformConv2d's parameters and the block's BatchNorm."""
+    k, s, p = 1, 1, 0
+
+    def __init__(self, dc: DeformConv2d, bn: nn.BatchNorm2d):
+        self.dc, self.bn = dc, bn
+        kh, kw = dc.kernel_size
+        self.kk = kh * kw * dc.in_channels
+        self.c1 = self.kk + (1 if dc.bias is not None else 0)
+        self.c2 = dc.out_channels
+        self._wcache = {}
+
+    def mark_step(self, tape: Tape) -> None:
+        if tape.train:
+            self.bn._nbt_pending += 1
+
+    def _wkey(self, tape: Tape):
+        w, b = self.dc.weight, self.dc.bias
+        return (tape.dname, w.data_ptr(), w._version, b._version if b is not None else -1, config.weight_epoch())
+
+    def compute_weights(self, tape: Tape):
+        key = self._wkey(tape)
+        c = self._wcache
+        if c.get("key") == key:
+            return c["w"], c["wt"]
+        dev = self.dc.weight.device
+        if c.get("w") is None or c["w"].dtype != tape.tdt or c["w"].device != dev:
+            c["w"] = torch.empty((self.c2, 1, round_up(self.c1, 8)), dtype=tape.tdt, device=dev)
+            c["wt"] = torch.empty((self.c1, 1, round_up(self.c2, 8)), dtype=tape.tdt, device=dev)
+        st = _stream()
+        wk = self.dc.weight.detach().permute(0, 2, 3, 1)
+        if not wk.is_contiguous():
+            self.dc.weight.data = self.dc.weight.data.contiguous(memory_format=torch.channels_last)
+            wk = self.dc.weight.detach().permute(0, 2, 3, 1)
+        if self.dc.bias is None:
+            master = wk
+        else:                      # [Cout][kk | bias]: two strided copies into a cached f32 buffer
+            master = c.get("master")
+            if master is None or master.device != dev:
+                master = c["master"] = torch.empty((self.c2, self.c1), dtype=torch.float32, device=dev)
+            L.call("ydl_copy2d", L.YDL_F32, _p(wk), self.kk, _p(master), self.c1, self.c2, self.kk, 0, st)
+            L.call("ydl_copy2d", L.YDL_F32, _p(self.dc.bias.detach()), 1, ctypes.c_void_p(master.data_ptr() + 4 * self.kk), self.c1,
+                   self.c2, 1, 0, st)
+        L.call("ydl_weight_prep", tape.dt, _p(master), _p(c["w"]), _p(c["wt"]), self.c2, 1, self.c1, st)
+        c["key"] = key
+        return c["w"], c["wt"]
+
+    coeffs = Conv.coeffs
+    touch_bn = Conv.touch_bn
+
+    def _grad_of(self, p: nn.Parameter) -> torch.Tensor:
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+        return p.grad
+
+    def grad_slot(self, tape: Tape, which: str):
+        p = self.bn.weight if which == "gamma" else self.bn.bias
+        return self._grad_of(p), 1
+
+    def trainable(self):
+        b = self.dc.bias
+        return (self.dc.weight.requires_grad or (b is not None and b.requires_grad), self.bn.weight.requires_grad,
+                self.bn.bias.requires_grad)
+
+    def splittable(self) -> bool:
+        return False
+
+    def wgrad(self, tape: Tape, gp, x: Var, dy: Var, st, col0: int = 0, final: bool = True, fuse=None) -> bool:
+        w, b = self.dc.weight, self.dc.bias
+        gk = self._grad_of(w).permute(0, 2, 3, 1) if w.requires_grad else None
+        if b is None and self.kk % 8 == 0 and gk is not None and gk.is_contiguous():
+            done = _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(gk), st, fuse)
+            config.mark_touched(w)
+            return done
+        if gk is not None and not gk.is_contiguous():
+            raise RuntimeError("DeformConv2d weight gradient must be KRSC-contiguous")
+        ld = round_up(self.c1, 8)
+        tmp = zero_(torch.empty((self.c2, ld), dtype=torch.float32, device=w.device), st)
+        _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(tmp), st)
+        tape._keep.append(tmp)
+        if gk is not None:
+            L.call("ydl_copy2d", L.YDL_F32, _p(tmp), ld, _p(gk), self.kk, self.c2, self.kk, 1, st)
+            config.mark_touched(w)
+        if b is not None and b.requires_grad:
+            L.call("ydl_copy2d", L.YDL_F32, ctypes.c_void_p(tmp.data_ptr() + 4 * self.kk), ld, _p(self._grad_of(b)), 1, self.c2, 1, 1, st)
+            config.mark_touched(b)
+        return False
+
+
+class _DCNSeq(nn.Sequential):
+    """one inner block of the script C3_DCN / C2f_DCN (seg_diceloss_yolov5.py:449-454): Sequential(Conv(c, c, 3, act=False),
+    Conv(c, 18, 3) offset branch, DeformConv2d(c, c, 3, padding=1, bias=False), Sequential(BatchNorm2d(c), SiLU))"""
+    takes_list = False
+
+    def __init__(self, c, g=1):
+        if g != 1:
+            raise NotImplementedError("C3_DCN / C2f_DCN: groups g > 1 are not implemented on the HIP path")
+        bn = _BNHolder(c)
+        super().__init__(Conv(c, c, 3, 1, g=g, d_or_act=False), Conv(c, 2 * 3 * 3, 3, 1, g=g, d_or_act=True),
+                         DeformConv2d(c, c, kernel_size=3, padding=1, groups=g, bias=False), nn.Sequential(bn, nn.SiLU(inplace=True)))
+        self.__dict__["_gemm"] = _DeformGemm(self[2], bn)
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        x1 = self[0]._fwd(tape, x)
+        off = self[1]._fwd(tape, x1)
+        return tape.deform_conv(x1, off, None, self[2], self._gemm, L.ACT_SILU, out=out)
+
+    def forward(self, x):
+        return run_region(self, [x]) if not isinstance(x, Var) else self._fwd(x.tape, x)
+
+
+class C3_DCN(C3):
+    """Seg-script C3_DCN (unet-lite/yolo5-seg/seg_diceloss_yolov5.py:431-465): C3 wiring (cv3(cat(m(cv1 x), cv2 x)) (+ x)) whose
+    inner blocks are 3x3 Conv -> offset Conv(c, 18, 3) -> DeformConv2d(c, c, 3, padding=1) -> BN -> SiLU."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, 0, shortcut, g, e)
+        self.m = nn.Sequential(*(_DCNSeq(self.c_, g) for _ in range(n)))
+
+
+class C2f_DCN(C2f):
+    """Seg-script C2f_DCN (yolov8/seg_diceloss_yolov8.py:417-457): C2f wiring (split, chain on the last chunk, concat) with the
+    C3_DCN inner blocks."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, 0, shortcut, g, e)
+        self.cv2 = Conv((2 + n) * self.c, c2, 1)
+        self.m = nn.ModuleList(_DCNSeq(self.c, g) for _ in range(n))
+
+
+class _BiasConv2d(nn.Conv2d):
+    """``nn.Conv2d(c1, c2, k, s, p, bias=True)`` run by Tape.conv_bias (no BatchNorm, no activation); weight kept channels_last
+    (the KRSC master).  ``_keep_init``: the yaml models' kaiming pass leaves its (zero) initialisation alone."""
+    _keep_init = True
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
+        self._wcache = {}
+
+    def compute_weights(self, tape: Tape):
+        key = (tape.dname, self.weight.data_ptr(), self.weight._version, config.weight_epoch())
+        c = self._wcache
+        kk = self.kernel_size[0] * self.kernel_size[1]
+        dev = self.weight.device
+        if c.get("w") is None or c["w"].dtype != tape.tdt or c["w"].device != dev:
+            c["w"] = torch.empty((self.out_channels, kk, round_up(self.in_channels, 8)), dtype=tape.tdt, device=dev)
+            c["wt"] = torch.empty((self.in_channels, kk, round_up(self.out_channels, 8)), dtype=tape.tdt, device=dev)
+            c["key"] = None
+        if c.get("key") != key:
+            wk = self.weight.detach().permute(0, 2, 3, 1)
+            if not wk.is_contiguous():
+                self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
+                wk = self.weight.detach().permute(0, 2, 3, 1)
+            L.call("ydl_weight_prep", tape.dt, _p(wk), _p(c["w"]), _p(c["wt"]), self.out_channels, kk, self.in_channels, _stream())
+            c["key"] = key
+        return c["w"], c["wt"]
+
+    def bias_coeffs(self, device):
+        cp = round_up(self.out_channels, 8)
+        key = (self.bias.data_ptr(), self.bias._version, config.weight_epoch())
+        c = self._wcache
+        if c.get("ones") is None or c["ones"].device != device:
+            c["ones"] = torch.ones(cp, dtype=torch.float32, device=device)
+            c["bpad"] = torch.zeros(cp, dtype=torch.float32, device=device)
+            c["bkey"] = None
+        if c.get("bkey") != key:
+            L.call("ydl_copy2d", L.YDL_F32, _p(self.bias.detach()), self.out_channels, _p(c["bpad"]), cp, 1, self.out_channels, 0,
+                   _stream())
+            c["bkey"] = key
+        return c["ones"], c["bpad"]
+
+    def _grad_of(self, p: nn.Parameter) -> torch.Tensor:
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+        return p.grad
+
+    def wgrad(self, tape: Tape, gp, x: Var, dy: Var, st) -> None:
+        if not self.weight.requires_grad:
+            return
+        gk = self._grad_of(self.weight).permute(0, 2, 3, 1)
+        kk = self.kernel_size[0] * self.kernel_size[1]
+        cin_p = round_up(self.in_channels, 8)
+        if cin_p == self.in_channels and gk.is_contiguous():
+            _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(gk), st)
+        else:
+            if not gk.is_contiguous():
+                raise RuntimeError("conv_offset_mask weight gradient must be KRSC-contiguous")
+            tmp = zero_(torch.empty((self.out_channels, kk, cin_p), dtype=torch.float32, device=gk.device), st)
+            _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(tmp), st)
+            L.call("ydl_wgrad_unpad", _p(tmp), _p(gk), self.out_channels, kk, self.in_channels, 1, st)
+        config.mark_touched(self.weight)
+
+
+class DCNv2(YdlModule):
+    """models/common.py:1629-1690: ``conv_offset_mask`` (plain biased Conv2d, zero-initialised) -> offsets = channels [0, 2GK),
+    mask = sigmoid(channels [2GK, 3GK)) -> deform_conv2d(x, weight, offset, mask, bias) -> BatchNorm -> SiLU.  The sigmoid runs
+    inside the gather / backward kernels (the logits are read in place), the bias is one more column of the GEMM (so it reaches
+    the output, the BN running mean and its gradient exactly as in the reference)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=1, dilation=1, groups=1, deformable_groups=1):
+        super().__init__()
+        if groups != 1:
+            raise NotImplementedError("DCNv2: weight groups > 1 are not implemented on the HIP path")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.stride = (kernel_size, kernel_size), (stride, stride)
+        self.padding, self.dilation = (padding, padding), (dilation, dilation)
+        self.groups, self.deformable_groups = groups, deformable_groups
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, *self.kernel_size))
+        self.bias = nn.Parameter(torch.empty(out_channels))
+        self.conv_offset_mask = _BiasConv2d(in_channels, deformable_groups * 3 * kernel_size * kernel_size, kernel_size, stride,
+                                            padding, bias=True)
+        self.bn = _BNHolder(out_channels)
+        self.act = nn.SiLU()
+        self.reset_parameters()
+        self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
+        self.__dict__["_gemm"] = _DeformGemm(self, self.bn)
+
+    def reset_parameters(self):
+        n = self.in_channels * self.kernel_size[0] * self.kernel_size[1]
+        std = 1.0 / math.sqrt(n)
+        self.weight.data.uniform_(-std, std)
+        self.bias.data.zero_()
+        self.conv_offset_mask.weight.data.zero_()
+        self.conv_offset_mask.bias.data.zero_()
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None, res: Optional[Var] = None, res_mode: int = L.RES_NONE) -> Var:
+        GK = self.deformable_groups * self.kernel_size[0] * self.kernel_size[1]
+        om = tape.conv_bias(x, self.conv_offset_mask)
+        return tape.deform_conv(x, om.slice(0, 2 * GK), om.slice(2 * GK, 3 * GK), self, self._gemm, L.ACT_SILU, mask_sigmoid=True,
+                                out=out, res=res, res_mode=res_mode)
+
+
+class Bottleneck_DCN(YdlModule):
+    """models/common.py:1692-1703: x (+) DCNv2(cv1(x))"""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = DCNv2(c_, c2, 3, 1, groups=g)
+        self.add = shortcut and c1 == c2
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        h = self.cv1._fwd(tape, x)
+        if self.add:
+            return self.cv2._fwd(tape, h, out=out, res=x, res_mode=L.RES_AFTER_ACT)
+        return self.cv2._fwd(tape, h, out=out)
+
+
+class C3_DCNCommon(C3Common):
+    """models/common.py:1705-1711 ``C3_DCN(C3)``: common.py's C3 wiring (no outer residual) with n Bottleneck_DCN (e=1.0).
+    parse_model resolves the yaml name C3_DCN to this class (with ``deformable=True``); the seg-script builders resolve it to
+    the script C3_DCN."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, 0, shortcut, g, e)
+        self.m = nn.Sequential(*(Bottleneck_DCN(self.c_, self.c_, shortcut, g, e=1.0) for _ in range(n)))
 
 
 class GAM(YdlModule):

@@ -1272,6 +1272,108 @@ class Tape:
             self.bw.append(bw)
         return out
 
+    def conv_bias(self, x: Var, m) -> Var:
+        """plain ``nn.Conv2d(..., bias=True)`` with no BatchNorm and no activation (DCNv2's conv_offset_mask, models/common.py:1652-1659):
+        implicit-GEMM convolution, the bias added by ydl_bn_act_fwd (scale 1); backward: bias gradient by ydl_channel_sum, weight
+        gradient and input gradient by the conv kernels.  ``m`` is a yolo_dual_amd.modules._BiasConv2d."""
+        x = self._flat(x)
+        k, s, p = m.kernel_size[0], m.stride[0], m.padding[0]
+        Cin, Cout = m.in_channels, m.out_channels
+        if x.C != Cin:
+            raise RuntimeError(f"Conv2d input channel mismatch: got {x.C}, weight expects {Cin}")
+        Ho = (x.H + 2 * p - k) // s + 1
+        Wo = (x.W + 2 * p - k) // s + 1
+        w, wt = m.compute_weights(self)
+        out = self.new(x.N, Cout, Ho, Wo)
+        geom = L.ConvGeom(x.N, x.H, x.W, Cin, Ho, Wo, Cout, k, s, p, x.ld, out.ld, 0)
+        gp = ctypes.byref(geom)
+        st = _stream()
+        npix = x.N * Ho * Wo
+        L.call("ydl_conv_fwd", gp, self.dt, _p(x.t), _p(w), _p(out.t), None, 0, st)
+        ones, bias = m.bias_coeffs(self.device)
+        L.call("ydl_bn_act_fwd", self.dt, _p(out.t), out.ld, _p(ones), _p(bias), None, 0, L.RES_NONE, L.ACT_NONE,
+               _p(out.t), out.ld, npix, round_up(Cout, 8), st)
+        if self.record:
+            if x.need:
+                self._use(x)
+
+            def bw():
+                # the consumers (DCNv2: the offset and mask slices) write channel slices of this buffer's gradient
+                if not (out.is_set() or any(c.gset for c in out.children)):
+                    return
+                st2 = _stream()
+                dout = self._gbuf(out)
+                dov = Var(self, dout, out.ld, False)
+                if m.bias.requires_grad:
+                    ws = torch.empty(L.lib().ydl_channel_sum_ws_bytes(Cout) // 4, dtype=torch.float32, device=self.device)
+                    L.call("ydl_channel_sum", self.dt, _p(dout), out.ld, _p(m._grad_of(m.bias)), _p(ws), npix, Cout, 1, st2)
+                    from . import config as _cfg
+                    _cfg.mark_touched(m.bias)
+                m.wgrad(self, gp, x, dov, st2)
+                if x.need:
+                    gx, acc = self.grad_target(x)
+                    L.call("ydl_conv_dgrad", gp, self.dt, _p(dout), _p(wt), _p(gx), acc, st2)
+                self._keep.append(geom)
+            self.bw.append(bw)
+        return out
+
+    def deform_conv(self, x: Var, offset: Var, mask: Optional[Var], m, gm, act: int, mask_sigmoid: bool = False,
+                    out: Optional[Var] = None, res: Optional[Var] = None, res_mode: int = L.RES_NONE) -> Var:
+        """act(bn(deform_conv2d(x, offset, m.weight, m.bias, mask))) (torchvision.ops.deform_conv2d followed by the block's
+        BatchNorm): ydl_deform_gather writes the column buffer, the 1x1 GEMM over it is an ordinary ``conv_bn_act`` with the
+        parameter holder ``gm`` (yolo_dual_amd.modules._DeformGemm: weight [Cout][kh*kw*Cin] = the KRSC weight, the bias as one more column), so the BN
+        statistics, the deferred weight gradient and d col come from the existing conv path; the backward of the gather turns
+        d col into the input, offset and mask gradients.  ``offset`` / ``mask`` are read with their own row strides (channel
+        slices of one buffer are fine); ``mask_sigmoid``: ``mask`` holds logits and the kernels apply the sigmoid."""
+        x = self._flat(x)
+        offset = self.materialize(offset)
+        mask = self.materialize(mask) if mask is not None else None
+        kh, kw = m.kernel_size
+        (sh, sw), (ph, pw), (dh, dw) = m.stride, m.padding, m.dilation
+        K = kh * kw
+        if x.C != m.in_channels:
+            raise RuntimeError(f"DeformConv2d input channel mismatch: got {x.C}, weight expects {m.in_channels}")
+        G = offset.C // (2 * K)
+        if G < 1 or offset.C != 2 * G * K or x.C % G or (mask is not None and mask.C != G * K):
+            raise RuntimeError(f"DeformConv2d: offset has {offset.C} channels (2*G*{K} expected), mask "
+                               f"{mask.C if mask is not None else None}")
+        Ho = (x.H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1
+        Wo = (x.W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+        if (offset.H, offset.W) != (Ho, Wo) or (mask is not None and (mask.H, mask.W) != (Ho, Wo)):
+            raise RuntimeError("DeformConv2d: offset / mask resolution does not match the output")
+        kc = gm.c1
+        ld = round_up(kc, 8)
+        buf = torch.empty((x.N, Ho, Wo, ld), dtype=self.tdt, device=self.device)
+        need = x.need or offset.need or (mask is not None and mask.need)
+        col = Var(self, buf.permute(0, 3, 1, 2)[:, :kc], ld, need)
+        L.call("ydl_deform_gather", self.dt, _p(x.t), x.ld, _p(offset.t), offset.ld, _p(mask.t) if mask is not None else None,
+               mask.ld if mask is not None else 0, int(mask_sigmoid), _p(col.t), ld, int(m.bias is not None),
+               x.N, x.H, x.W, x.C, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, G, _stream())
+        if self.record and need:
+            self._keep.append(buf)      # the deferred weight gradient reads col on the side stream: alive until the streams join
+            if x.need:
+                self._use(x)
+
+            def bw():
+                if not col.is_set():
+                    return
+                st2 = _stream()
+                npix = x.N * Ho * Wo
+                gin = zero_(torch.empty((x.N, x.H, x.W, x.C), dtype=torch.float32, device=self.device)) if x.need else None
+                goff = torch.empty((npix, 2 * G * K), dtype=torch.float32, device=self.device) if offset.need else None
+                gmsk = (torch.empty((npix, G * K), dtype=torch.float32, device=self.device)
+                        if mask is not None and mask.need else None)
+                L.call("ydl_deform_bwd", self.dt, _p(x.t), x.ld, _p(offset.t), offset.ld, _p(mask.t) if mask is not None else None,
+                       mask.ld if mask is not None else 0, int(mask_sigmoid), _p(self._gbuf(col)), ld, _p(gin), _p(goff), _p(gmsk),
+                       x.N, x.H, x.W, x.C, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, G, st2)
+                for v, g32 in ((x, gin), (offset, goff), (mask, gmsk)):
+                    if g32 is not None:
+                        gv, acc = self.grad_target(v)
+                        L.call("ydl_cast_f32", v.dt, _p(g32), g32.shape[-1], _p(gv), v.ld, v.npix, v.C, acc, st2)
+            self.bw.append(bw)
+        gm.mark_step(self)
+        return self.conv_bn_act(col, gm, 1, 0, act, out=out, res=res, res_mode=res_mode)
+
     def scale_channels(self, x: Var, gate: torch.Tensor) -> Var:
         x = self.materialize(x)
         out = self.new_like(x)
