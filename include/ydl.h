@@ -68,8 +68,12 @@ typedef struct {
                                  over a channel concat is evaluated as the sum of one convolution per source */
 } ydl_conv_geom;
 
-/* BN-statistics workspace of the forward epilogue: [grid_m][2][round_up(Cout,8)] floats, where block b of
- * the launch covered min(block_m, N*Ho*Wo - b*block_m) pixels.  The three queries are pure functions of g. */
+/* BN-statistics workspace of the forward epilogue: [grid_m][2][round_up(Cout,8)] floats of (sum, M2) per channel, row b for
+ * block b of the launch.  A block is one launch tile, which may be a 2-D patch of the image: only the row count grid_m and the
+ * per-row pixel count min(block_m, N*Ho*Wo - b*block_m) are promised, not which pixels a row covers.  The workspace also holds
+ * the room ydl_bn_finalize needs behind the rows.  The three queries are pure functions of g (and of the debug knobs), run on
+ * the host without a device, and describe the launch ydl_conv_fwd makes with stats_ws != NULL and accumulate == 0 (a launch that
+ * accumulates on a geometry where they would differ returns an error); 0 for a geometry ydl_conv_fwd refuses. */
 int64_t ydl_conv_fwd_stats_ws_bytes(const ydl_conv_geom* g, int dtype);
 int ydl_conv_fwd_grid_m(const ydl_conv_geom* g, int dtype);
 int ydl_conv_fwd_block_m(const ydl_conv_geom* g, int dtype);

@@ -278,6 +278,33 @@ def test_fused_stride2_dgrad_through_the_c_abi(cin, cout, N, Ho, Wo, accumulate)
     assert float((got - ref).abs().max()) < 1.6e-2 * float(ref.abs().max())
 
 
+# deterministic bf16 (partial-row statistics + ydl_bn_finalize, as in parity mode): the tape sizes and merges the rows with the
+# ydl_conv_fwd_grid_m / _block_m / _stats_ws_bytes queries, which must describe the kernel that runs — the BM = 256 ring ids run on
+# the 128-pixel patch kernel on maps that are multiples of 8 x 16.  (tag, N, c1, c2, k, s, H, W, debug knobs, forward kernel)
+DET = [
+    ("det_patch24_bf16", 4, 128, 128, 3, 1, 160, 160, (), "igemm2h_kernel<128,128,2>"),
+    ("det_ring24_bf16", 4, 128, 128, 3, 1, 152, 152, (), "igemm2l_kernel<256,128,8+4,3>"),
+    ("det_patch15_bf16", 4, 128, 128, 3, 1, 160, 160, ((19, 0),), "igemm2h_kernel<128,128,2>"),
+    ("det_ring15_bf16", 4, 128, 128, 3, 1, 152, 152, ((19, 0),), "igemm2_kernel<256,128,8,4,3,stg>"),
+]
+
+
+@pytest.mark.parametrize("case", DET, ids=[c[0] for c in DET])
+def test_deterministic_bf16_statistics_on_the_ring_and_patch_kernels(case):
+    from yolo_dual_amd import _lib as L
+    tag, N, c1, c2, k, s_, H, W, knobs, expk = case
+    for key, val in knobs:
+        L.debug_set(key, val)        # (bumps the debug epoch: the new module's geometry cache is built under the knob)
+    try:
+        got, ref, kern = _case("bf16", N, c1, c2, k, s_, H, W, deterministic=True)
+    finally:
+        for key, _val in knobs:
+            L.debug_set(key, -1)
+    assert kern["fwd"] == expk, (tag, kern)
+    assert kern["bn_finalize"].startswith("bn_finalize<"), (tag, kern)
+    _check(got, ref, "bf16", tag)
+
+
 def test_bn_finalize_two_level_merge_against_oracle():
     """> 1024 per-block partial rows (147 456 pixels / 128): the level-1 pre-merge of ydl_bn_finalize"""
     got, ref, kern = _case("f32", 4, 16, 32, 3, 1, 192, 192)

@@ -3036,7 +3036,15 @@ static int launch_igemm2s(IgemmArgs a, hipStream_t st, int fam) {
 }
 
 static bool ring_has_bnred(int id) { return id == 7 || id == 9 || id == 13; }
-static int launch_ring(int id, const IgemmArgs& a, hipStream_t st, int fam) {
+// statistics rows of a forward launch: grid_m partial rows of block_m pixels (the last one may be shorter)
+struct FwdRows { int grid_m, block_m; };
+// rows != nullptr: no launch, *rows = the partial-row geometry of the kernel this id runs on (the patch form or the ring tile)
+static int launch_ring(int id, const IgemmArgs& a, hipStream_t st, int fam, FwdRows* rows = nullptr) {
+    if (rows) {
+        const int bm = (a.br.nseg == 0 && halo_ok(a, id)) ? 128 : kRingBM[id];       // (igemm2h / igemm2hs: one 8 x 16 patch per tile)
+        *rows = FwdRows{(a.M + bm - 1) / bm, bm};
+        return 0;
+    }
     if (a.br.nseg > 0) {          // epilogue with the fused BatchNorm-backward reduce: the instantiations the dgrads of the models use
         switch (id) {
             case 7: return launch_igemm2<128, 128, 8, 4, 2, true>(a, st, fam);
@@ -3159,18 +3167,20 @@ static TileCfg pick_cfg(int M, int Cst, int nchunks = 0, bool bf16 = false, int 
 
 // path_out != nullptr: no launch, *path_out = the kernel family this geometry runs on (0 register-staged tiles, 1 point-wise
 // streaming kernel, 2 LDS-DMA ring, 3 stem kernel)
+// rows_out != nullptr: no launch, *rows_out = the (grid_m, block_m) of the statistics partial rows this launch would write (the
+// ydl_conv_fwd_* queries: host only, no device state — the device-dependent conditions of wreg_ok come after its partial-row refusal)
 template <typename T>
-static int dispatch_igemm(const IgemmArgs& a, hipStream_t st, int fam, int* grid_m_out = nullptr, int force_bm = 0, int* path_out = nullptr) {
+static int dispatch_igemm(const IgemmArgs& a, hipStream_t st, int fam, FwdRows* rows_out = nullptr, int force_bm = 0, int* path_out = nullptr) {
     if constexpr (sizeof(T) == 2) {
         if (fam == 0 && !force_bm && args_stem(a)) {
             const StemPlan sp = stem_plan(a.M, a.Wo);
             if (sp.ok && path_out) { *path_out = 3; return 0; }
+            if (sp.ok && rows_out) { *rows_out = FwdRows{sp.grid_m, sp.block_m}; return 0; }
             if (sp.ok) {
                 StemArgs q{};
                 q.X = (const bf16_t*)a.A; q.W = (const bf16_t*)a.B; q.Y = (bf16_t*)a.C; q.stats = a.stats;
                 q.H = a.Hi; q.Wd = a.Wi; q.ldc = a.ldc; q.M = a.M; q.block_m = sp.block_m; q.stats_ld = a.stats_ld;
                 q.stats_atomic = a.stats_atomic; q.bytesX = a.bytesA;
-                if (grid_m_out) *grid_m_out = sp.grid_m;
                 ydl_note_kernel(fam, "stem_kernel<bf16,16,64>");
                 stem_kernel<<<sp.grid_m, 256, 0, st>>>(q);
                 YDL_LAUNCH_CHECK();
@@ -3181,13 +3191,13 @@ static int dispatch_igemm(const IgemmArgs& a, hipStream_t st, int fam, int* grid
     {
         const PwPlan pl = pw_plan(a.M, a.Kc, a.Cout, a.Cst, (int)sizeof(T), args_pointwise(a));
         if (pl.ok && !force_bm && path_out) { *path_out = 1; return 0; }
+        if (pl.ok && !force_bm && rows_out) { *rows_out = FwdRows{pl.grid_m, pl.block_m}; return 0; }
         if (pl.ok && !force_bm) {
             YDL_CHECK(a.br.nseg == 0, "fused BatchNorm reduce: this geometry runs on the point-wise kernel (query ydl_conv_dgrad_bnred_supported)");
             PwArgs q{};
             q.X = a.A; q.W = a.B; q.Y = a.C; q.stats = a.stats;
             q.M = a.M; q.lda = a.lda; q.ldc = a.ldc; q.Cout = a.Cout; q.WN = pl.WN; q.accumulate = a.accumulate;
             q.block_m = pl.block_m; q.stats_ld = a.stats_ld; q.stats_atomic = a.stats_atomic; q.bytesX = a.bytesA; q.ldw_bytes = a.ldb_bytes;
-            if (grid_m_out) *grid_m_out = pl.grid_m;
             return launch_pw<T>(q, pl, st, fam);
         }
     }
@@ -3195,7 +3205,7 @@ static int dispatch_igemm(const IgemmArgs& a, hipStream_t st, int fam, int* grid
         // weights-in-registers kernel: 3x3 / s1 over one 64-channel block (igemm2w_kernel).  (Not for the path query of
         // ydl_conv_dgrad_bnred_supported: a launch WITH the fused BatchNorm reduce skips this kernel and runs on the ring.)
         if (!force_bm && !path_out && wreg_ok(a)) {
-            if (grid_m_out) *grid_m_out = (a.M + 127) / 128;
+            YDL_CHECK(rows_out == nullptr, "internal: the weights-in-registers kernel writes no statistics partial rows");
             return launch_igemm2w(a, st, fam);
         }
     }
@@ -3209,8 +3219,7 @@ static int dispatch_igemm(const IgemmArgs& a, hipStream_t st, int fam, int* grid
     if constexpr (sizeof(T) == 2) {
         if (c.ring && !force_bm) {
             if (path_out) { *path_out = ring_has_bnred(c.ring) ? 2 : 4; return 0; }
-            if (grid_m_out) *grid_m_out = (a.M + c.BM - 1) / c.BM;
-            return launch_ring(c.ring, a, st, fam);
+            return launch_ring(c.ring, a, st, fam, rows_out);
         }
     }
     if (path_out) { *path_out = 0; return 0; }
@@ -3221,7 +3230,7 @@ static int dispatch_igemm(const IgemmArgs& a, hipStream_t st, int fam, int* grid
     static const int env_bn = getenv("YDL_FORCE_BN") ? atoi(getenv("YDL_FORCE_BN")) : 0;
     if (env_bm && a.stats == nullptr) c.BM = env_bm;        // (the stats workspace is sized from pick_cfg: keep it for those)
     if (env_bn && c.BN != 16 && a.Cst >= env_bn) c.BN = env_bn;
-    if (grid_m_out) *grid_m_out = (a.M + c.BM - 1) / c.BM;
+    if (rows_out) { *rows_out = FwdRows{(a.M + c.BM - 1) / c.BM, c.BM}; return 0; }
     static const int nw8 = getenv("YDL_NW8") ? atoi(getenv("YDL_NW8")) : 1;
     if (c.BM == 128 && c.BN == 128) {
         if (nw8 == 2) return launch_igemm<T, 128, 128, 4, 2>(a, st, fam);      // 2x2 waves, 64x64 wave tiles (experiment)
@@ -3262,37 +3271,11 @@ static int check_geom(const ydl_conv_geom* g, int dtype) {
     return 0;
 }
 
-// number of M-blocks / pixels per block of the forward launch (the caller sizes and consumes the stats partials with them)
-static void fwd_blocks(const ydl_conv_geom* g, int dtype, int* grid_m, int* block_m) {
-    int M = g->N * g->Ho * g->Wo;
-    int Cst = round_up(g->Cout, 8) <= g->ldy ? round_up(g->Cout, 8) : g->Cout;
-    if (dtype == YDL_BF16 && g->k == 3 && g->s == 1 && g->p == 1 && round_up(g->Cin, 8) == 16 && g->ldx == 16 && g->Cout == 64 && Cst == 64 &&
-        g->ldw == 0) {
-        const StemPlan sp = stem_plan(M, g->Wo);          // the thin-input kernel (same conditions as args_stem)
-        if (sp.ok) { *grid_m = sp.grid_m; *block_m = sp.block_m; return; }
-    }
-    const PwPlan pl = pw_plan(M, round_up(g->Cin, 8), g->Cout, Cst, esize(dtype), g->k == 1 && g->s == 1 && g->p == 0);
-    if (pl.ok) { *grid_m = pl.grid_m; *block_m = pl.block_m; return; }
-    TileCfg c = pick_cfg(M, Cst, g->k * g->k * (round_up(g->Cin, 8) / (16 / esize(dtype))), dtype == YDL_BF16,
-                         round_up(g->Cin, 8), g->k * g->k);
-    *grid_m = (M + c.BM - 1) / c.BM;
-    *block_m = c.BM;
-}
-
-extern "C" int64_t ydl_conv_fwd_stats_ws_bytes(const ydl_conv_geom* g, int dtype) {
-    // [gridM][2][round_up(Cout,8)] floats + room for ydl_bn_finalize's level-1 chunk partials (gridM/64 + 1 rows)
-    int gm, bm;
-    fwd_blocks(g, dtype, &gm, &bm);
-    return ((int64_t)gm + gm / 64 + 2) * 2 * round_up(g->Cout, 8) * (int64_t)sizeof(float);
-}
-extern "C" int ydl_conv_fwd_grid_m(const ydl_conv_geom* g, int dtype) { int gm, bm; fwd_blocks(g, dtype, &gm, &bm); return gm; }
-extern "C" int ydl_conv_fwd_block_m(const ydl_conv_geom* g, int dtype) { int gm, bm; fwd_blocks(g, dtype, &gm, &bm); return bm; }
-
-static int conv_fwd_impl(const ydl_conv_geom* g, int dtype, const void* x, const void* w, void* y,
-                         float* stats_ws, int stats_atomic, int accumulate, void* stream) {
+// argument block of a forward launch (ydl_conv_fwd / _sums and the statistics queries build it the same way)
+static int fwd_args(const ydl_conv_geom* g, int dtype, const void* x, const void* w, void* y, float* stats_ws, int stats_atomic,
+                    int accumulate, IgemmArgs& a) {
     if (int e = check_geom(g, dtype)) return e;
-    YDL_CHECK(aligned16(x) && aligned16(w) && aligned16(y), "pointers must be 16-byte aligned");
-    IgemmArgs a{};
+    a = IgemmArgs{};
     a.A = x; a.B = w; a.C = y; a.stats = stats_ws;
     a.N = g->N; a.Hi = g->Hi; a.Wi = g->Wi; a.lda = g->ldx;
     a.Kc = round_up(g->Cin, 8);
@@ -3309,7 +3292,49 @@ static int conv_fwd_impl(const ydl_conv_geom* g, int dtype, const void* x, const
             int tpi = r * g->k + s;
             a.dh[tpi] = (signed char)(r - g->p); a.dw[tpi] = (signed char)(s - g->p); a.wt[tpi] = (unsigned char)tpi;
         }
-    if (int e = set_extents(a, dtype)) return e;
+    return set_extents(a, dtype);
+}
+
+// statistics partial rows of a forward launch: the dispatcher's own selection, run in its query form (no launch)
+static int fwd_rows(const IgemmArgs& a, int dtype, FwdRows& r) {
+    return dtype == YDL_F32 ? dispatch_igemm<float>(a, nullptr, 0, &r) : dispatch_igemm<bf16_t>(a, nullptr, 0, &r);
+}
+
+// (grid_m, block_m) of ydl_conv_fwd with partial rows: the rows a launch with accumulate = 0 writes (a launch that accumulates checks
+// that it writes the same ones).  {0, 0} on a bad geometry.
+static FwdRows fwd_blocks(const ydl_conv_geom* g, int dtype) {
+    static float stats_tag;                // any non-null pointer: the queries describe a launch WITH partial rows
+    IgemmArgs a;
+    FwdRows r{0, 0};
+    if (fwd_args(g, dtype, nullptr, nullptr, nullptr, &stats_tag, 0, 0, a) || fwd_rows(a, dtype, r)) return FwdRows{0, 0};
+    return r;
+}
+
+extern "C" int64_t ydl_conv_fwd_stats_ws_bytes(const ydl_conv_geom* g, int dtype) {
+    // [gridM][2][round_up(Cout,8)] floats + room for ydl_bn_finalize's level-1 chunk partials (gridM/64 + 1 rows)
+    const FwdRows r = fwd_blocks(g, dtype);
+    if (r.grid_m <= 0) return 0;
+    return ((int64_t)r.grid_m + r.grid_m / 64 + 2) * 2 * round_up(g->Cout, 8) * (int64_t)sizeof(float);
+}
+extern "C" int ydl_conv_fwd_grid_m(const ydl_conv_geom* g, int dtype) { return fwd_blocks(g, dtype).grid_m; }
+extern "C" int ydl_conv_fwd_block_m(const ydl_conv_geom* g, int dtype) { return fwd_blocks(g, dtype).block_m; }
+
+static int conv_fwd_impl(const ydl_conv_geom* g, int dtype, const void* x, const void* w, void* y,
+                         float* stats_ws, int stats_atomic, int accumulate, void* stream) {
+    IgemmArgs a;
+    if (int e = fwd_args(g, dtype, x, w, y, stats_ws, stats_atomic, accumulate, a)) return e;
+    YDL_CHECK(aligned16(x) && aligned16(w) && aligned16(y), "pointers must be 16-byte aligned");
+    if (stats_ws != nullptr && !stats_atomic && accumulate) {
+        // the queries describe the launch without accumulation: this one must write the same rows (the thin-input stem kernel,
+        // for one, runs only without it)
+        FwdRows r0{0, 0}, r1{0, 0};
+        IgemmArgs a0 = a;
+        a0.accumulate = 0;
+        if (int e = fwd_rows(a0, dtype, r0)) return e;
+        if (int e = fwd_rows(a, dtype, r1)) return e;
+        YDL_CHECK(r0.grid_m == r1.grid_m && r0.block_m == r1.block_m,
+                  "partial-row statistics with accumulate != 0: this geometry runs on another kernel than ydl_conv_fwd_grid_m / _block_m describe");
+    }
     hipStream_t st = (hipStream_t)stream;
     return dtype == YDL_F32 ? dispatch_igemm<float>(a, st, 0) : dispatch_igemm<bf16_t>(a, st, 0);
 }
