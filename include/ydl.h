@@ -308,6 +308,49 @@ int ydl_sgd_ema_step_dev(float* params, const float* grads, float* momentum, flo
 int ydl_sgd_ema_step_multi(float* params, const float* grads, float* momentum, float* ema, const int64_t* runs_dev,
                            int nruns, int64_t max_run, const float* hyper_dev, int use_ema, void* stream);
 
+/* ---- optimizer: Adam / AdamW / RMSProp + EMA on flat arenas (torch.optim.{Adam,AdamW,RMSprop}, single-tensor path) ---- */
+/* rule: YDL_OPT_ADAM (coupled decay), YDL_OPT_ADAMW (decoupled decay), YDL_OPT_RMSPROP (not centered).
+ * state1 / state2 are flat f32 arenas like `momentum` above, zero before the first step: Adam and AdamW keep exp_avg in
+ * state1 and exp_avg_sq in state2; RMSProp keeps the momentum buffer in state1 (untouched when beta1 == 0) and square_avg
+ * in state2.  Elements [0, n_decay) take the weight decay, [0, n_params) are updated, [0, n_total) feed the EMA.
+ * Every factor that torch computes in Python double precision is computed by the CALLER in double and handed over rounded
+ * once to f32:
+ *   step_size    Adam/AdamW: lr / (1 - beta1^t);  RMSProp: lr
+ *   bc2_sqrt     Adam/AdamW: sqrt(1 - beta2^t);   RMSProp: unused
+ *   decay_mul    AdamW: 1 - lr * weight_decay (p *= decay_mul on the decay range);  others: unused
+ *   weight_decay Adam/RMSProp: g += weight_decay * p on the decay range;  AdamW: unused
+ *   beta1        Adam/AdamW: beta1;  RMSProp: momentum          one_minus_beta1 = 1 - beta1 (Adam/AdamW)
+ *   beta2        Adam/AdamW: beta2;  RMSProp: alpha             one_minus_beta2 = 1 - beta2 (or 1 - alpha)
+ * t is the step count of the parameters of THIS call (all of them share it).  g = grad * grad_scale. */
+#define YDL_OPT_ADAM 1
+#define YDL_OPT_ADAMW 2
+#define YDL_OPT_RMSPROP 3
+int ydl_optim_ema_step(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
+                       int64_t n_decay, int64_t n_params, int64_t n_total,
+                       float step_size, float bc2_sqrt, float decay_mul, float weight_decay,
+                       float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                       float grad_scale, float ema_decay /* <0: skip EMA */, void* stream);
+
+/* graph-capturable form: hyper_dev = device float[YDL_OPT_HYPER_FLOATS]
+ *   [0..2] lr of {weights, BN weights, biases}   [3] beta1 | momentum   [4] weight_decay   [5] grad_scale   [6] ema_decay
+ *   [7] beta2 | alpha   [8] eps   [9] 1 - beta1   [10] 1 - beta2 | 1 - alpha   [11] decay_mul of the weights group
+ *   [12 + 4c + i] step_size of bias-correction class c for lr index i (i = 0..2)   [12 + 4c + 3] bc2_sqrt of class c
+ * A bias-correction class is a set of parameters with the same step count t (c < YDL_OPT_MAX_CLASSES); RMSProp has no
+ * correction: it reads lr from [lr_index] and ignores bc_class. */
+#define YDL_OPT_MAX_CLASSES 16
+#define YDL_OPT_HYPER_FLOATS 76
+int ydl_optim_ema_step_dev(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
+                           int64_t n_decay, int64_t n_params, int64_t n_total, const float* hyper_dev,
+                           int lr_index, int bc_class, int use_weight_decay, int use_ema, void* stream);
+
+/* every run of one step in one launch: runs_dev = device int64[nruns][8] rows {offset (elements into all five arenas), n_decay,
+ * n_params, n_total, lr_index, flags: bit 0 weight decay, bc_class, 0}, each row with the meaning of the arguments of
+ * ydl_optim_ema_step_dev applied at `offset`; max_run = the largest n_total (grid sizing).  The arenas are 16-byte aligned;
+ * the rows are read on the device unchecked: the caller keeps them inside the arenas. */
+int ydl_optim_ema_step_multi(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
+                             const int64_t* runs_dev, int nruns, int64_t max_run, const float* hyper_dev, int use_ema,
+                             void* stream);
+
 /* ---- evaluation: argmax + confusion matrix (val_diceloss.py:37-75) ---------------------------------- */
 int ydl_confusion_matrix(const float* pred, int64_t sn, int64_t sc, int64_t sh, int64_t sw,
                          const int64_t* target, int N, int C, int H, int W, int ignore_index,

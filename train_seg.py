@@ -55,7 +55,8 @@ def parse_opt(argv=None):
     p.add_argument("--save-dir", type=str, default="runs/train-seg")
     p.add_argument("--noval", action="store_true")
     p.add_argument("--nosave", action="store_true")
-    p.add_argument("--optimizer", type=str, default="SGD")
+    p.add_argument("--optimizer", type=str, default="SGD", choices=["SGD", "Adam", "AdamW", "RMSProp"],
+                   help="optimizer (Adam and AdamW take beta1 = --momentum); every choice runs the fused HIP step with EMA")
     p.add_argument("--label-smoothing", type=float, default=0.0)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--dcn", default="substitute", choices=["substitute", "native"],
@@ -262,7 +263,7 @@ def train(opt) -> float:
         mb = ydl.strip_optimizer(best)                                                   # :1229
         print(f"[train_seg] best model saved to {best} ({mb:.1f} MB, optimizer stripped)")
     pa = optimizer.params_arena[:optimizer.n_params].double()
-    LAST_RUN.update(param_sum=float(pa.sum()), param_abs_sum=float(pa.abs().sum()))
+    LAST_RUN.update(param_sum=float(pa.sum()), param_abs_sum=float(pa.abs().sum()), loss=float(mloss[0]))
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

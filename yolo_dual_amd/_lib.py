@@ -14,6 +14,8 @@ ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2
 RES_NONE, RES_AFTER_ACT, RES_BEFORE_ACT = 0, 1, 2
 RES_GRAD_ACCUMULATE = 16
 LOSS_DICE, LOSS_JACCARD = 0, 1
+OPT_ADAM, OPT_ADAMW, OPT_RMSPROP = 1, 2, 3      # YDL_OPT_* of ydl.h
+OPT_MAX_CLASSES, OPT_HYPER_FLOATS = 16, 76
 RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BILINEAR_AC = 0, 1, 2
 
 
@@ -100,6 +102,9 @@ SIGNATURES = {
     "ydl_sgd_ema_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f, _f, _f, _f, _f, _i, _f, _vp]),
     "ydl_sgd_ema_step_dev": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _vp]),
     "ydl_sgd_ema_step_multi": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _i, _vp]),
+    "ydl_optim_ema_step": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
+    "ydl_optim_ema_step_dev": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _vp]),
+    "ydl_optim_ema_step_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _i, _vp]),
     "ydl_confusion_matrix": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ydl_dcnv3_set_border_rule": (None, [_i]),
     "ydl_dcnv3_get_border_rule": (_i, []),

@@ -84,7 +84,7 @@ def strip_optimizer(f: str = "best.pt", s: str = "") -> float:
 
 
 def smart_resume(ckpt: dict, optimizer, ema=None, weights: str = "last.pt", epochs: int = 300, resume: bool = True):
-    """utils/torch_utils.py:361-378.  ``ema``: the FlatSGDEMA (its EMA shadow is restored from ckpt['ema'] when present)"""
+    """utils/torch_utils.py:361-378.  ``ema``: the flat-arena optimizer (its EMA shadow is restored from ckpt['ema'] when present)"""
     best_fitness = 0.0
     start_epoch = ckpt["epoch"] + 1
     if ckpt.get("optimizer") is not None:

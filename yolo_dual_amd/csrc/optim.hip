@@ -355,3 +355,225 @@ extern "C" int ydl_sgd_ema_step_dev(float* params, const float* grads, float* mo
     YDL_LAUNCH_CHECK();
     return 0;
 }
+
+
+// ---- Adam / AdamW / RMSProp + EMA over the flat arenas (torch.optim.{Adam,AdamW,RMSprop}, single-tensor path) -------------------
+// One streaming pass, nine words per parameter (p rw, g r, state1 rw, state2 rw, ema rw; SGD has seven).  The three entry forms
+// (host scalars, device hyper vector, run table) share ONE element function and ONE walk, so that they agree bit for bit; the
+// element function keeps torch's operation order and is compiled without FMA contraction (a contraction the compiler picks in one
+// inlining context and not in another would break that agreement, and torch's CPU kernels do not contract either).
+struct OptHyper {
+    float step;        // Adam/AdamW: lr / (1 - beta1^t);  RMSProp: lr
+    float bc2s;        // Adam/AdamW: sqrt(1 - beta2^t)
+    float dmul;        // AdamW: 1 - lr*wd
+    float wd;          // Adam/RMSProp: coupled decay
+    float b1, b2, omb1, omb2, eps, gscale, d;
+};
+
+template <int RULE>
+__device__ __forceinline__ void optim_ema_elem(float& p, float g, float& s1, float& s2, float& e, bool is_param, bool dec, bool use_ema,
+                                               const OptHyper& h) {
+#pragma clang fp contract(off)
+    if (is_param) {
+        g = g * h.gscale;
+        if (RULE == YDL_OPT_ADAMW) {
+            if (dec) p = p * h.dmul;
+        } else if (dec && h.wd != 0.f) {
+            g = g + h.wd * p;
+        }
+        if (RULE != YDL_OPT_RMSPROP) {
+            const float diff = g - s1;                                   // exp_avg.lerp_(grad, 1 - beta1)
+            s1 = h.omb1 < 0.5f ? s1 + h.omb1 * diff : g - diff * (1.f - h.omb1);
+            s2 = s2 * h.b2 + (h.omb2 * g) * g;                           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+            const float denom = sqrtf(s2) / h.bc2s + h.eps;
+            p = p + (-h.step * s1) / denom;                              // param.addcdiv_(exp_avg, denom, value=-step_size)
+        } else {
+            s2 = s2 * h.b2 + (h.omb2 * g) * g;                           // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+            const float avg = sqrtf(s2) + h.eps;
+            if (h.b1 > 0.f) {
+                s1 = s1 * h.b1 + g / avg;                                // buf.mul_(momentum).addcdiv_(grad, avg)
+                p = p + (-h.step) * s1;                                  // param.add_(buf, alpha=-lr)
+            } else {
+                p = p + (-h.step * g) / avg;                             // param.addcdiv_(grad, avg, value=-lr)
+            }
+        }
+    }
+    if (use_ema) {
+        e = e * h.d;
+        e = e + (1.f - h.d) * p;
+    }
+}
+
+// One run [off, off + n_total) of the arenas, walked in float4 groups aligned to the ARENA (16-byte accesses whatever the run's
+// offset); the groups that straddle the run's ends, runs whose decay / parameter boundary is not the whole run, and arenas that are
+// not co-aligned (`vec` false) take the element form.  Same arithmetic per element either way.
+template <int RULE>
+__device__ __forceinline__ void optim_ema_walk(float* __restrict__ params, const float* __restrict__ grads, float* __restrict__ st1,
+                                               float* __restrict__ st2, float* __restrict__ ema, long long off, long long n_decay,
+                                               long long n_params, long long n_total, const OptHyper& h, bool ue, bool vec) {
+    const bool us1 = RULE != YDL_OPT_RMSPROP || h.b1 > 0.f;              // RMSProp without momentum keeps no buffer
+    const long long a0 = off & ~3ll, end = off + n_total;
+    const bool uniform = vec && (n_params == n_total || n_params == 0) && (n_decay == n_params || n_decay == 0);
+    for (long long q = a0 + 4 * ((long long)blockIdx.x * blockDim.x + threadIdx.x); q < end; q += 4ll * gridDim.x * blockDim.x) {
+        if (uniform && q >= off && q + 4 <= end) {
+            const bool isp = n_params != 0, dec = n_decay != 0;
+            float4 p4 = *(const float4*)(params + q), g4 = make_float4(0.f, 0.f, 0.f, 0.f), a4 = g4, b4 = g4, e4 = g4;
+            if (isp) {
+                g4 = *(const float4*)(grads + q);
+                if (us1) a4 = *(const float4*)(st1 + q);
+                b4 = *(const float4*)(st2 + q);
+            }
+            if (ue) e4 = *(const float4*)(ema + q);
+            optim_ema_elem<RULE>(p4.x, g4.x, a4.x, b4.x, e4.x, isp, dec, ue, h);
+            optim_ema_elem<RULE>(p4.y, g4.y, a4.y, b4.y, e4.y, isp, dec, ue, h);
+            optim_ema_elem<RULE>(p4.z, g4.z, a4.z, b4.z, e4.z, isp, dec, ue, h);
+            optim_ema_elem<RULE>(p4.w, g4.w, a4.w, b4.w, e4.w, isp, dec, ue, h);
+            if (isp) {
+                *(float4*)(params + q) = p4;
+                if (us1) *(float4*)(st1 + q) = a4;
+                *(float4*)(st2 + q) = b4;
+            }
+            if (ue) *(float4*)(ema + q) = e4;
+        } else {
+            for (int k = 0; k < 4; ++k) {
+                const long long i = q + k - off;
+                if (i < 0 || i >= n_total) continue;
+                const bool isp = i < n_params;
+                float p = params[off + i], g = 0.f, a = 0.f, b = 0.f, e = 0.f;
+                if (isp) {
+                    g = grads[off + i];
+                    if (us1) a = st1[off + i];
+                    b = st2[off + i];
+                }
+                if (ue) e = ema[off + i];
+                optim_ema_elem<RULE>(p, g, a, b, e, isp, i < n_decay, ue, h);
+                if (isp) {
+                    params[off + i] = p;
+                    if (us1) st1[off + i] = a;
+                    st2[off + i] = b;
+                }
+                if (ue) ema[off + i] = e;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ OptHyper optim_hyper_load(int rule, const float* __restrict__ hyper, int lr_idx, int cls, bool use_wd) {
+    OptHyper h;
+    const bool rms = rule == YDL_OPT_RMSPROP;
+    h.step = rms ? hyper[lr_idx] : hyper[12 + 4 * cls + lr_idx];
+    h.bc2s = rms ? 1.f : hyper[12 + 4 * cls + 3];
+    h.dmul = hyper[11];
+    h.wd = use_wd ? hyper[4] : 0.f;
+    h.b1 = hyper[3]; h.b2 = hyper[7]; h.eps = hyper[8]; h.omb1 = hyper[9]; h.omb2 = hyper[10];
+    h.gscale = hyper[5]; h.d = hyper[6];
+    return h;
+}
+
+template <int RULE>
+__global__ __launch_bounds__(256) void optim_ema_kernel(float* params, const float* grads, float* st1, float* st2, float* ema, long long off,
+                                                        long long n_decay, long long n_params, long long n_total, OptHyper h, int vec) {
+    optim_ema_walk<RULE>(params, grads, st1, st2, ema, off, n_decay, n_params, n_total, h, h.d >= 0.f && ema != nullptr, vec != 0);
+}
+
+template <int RULE>
+__global__ __launch_bounds__(256) void optim_ema_dev_kernel(float* params, const float* grads, float* st1, float* st2, float* ema, long long off,
+                                                            long long n_decay, long long n_params, long long n_total,
+                                                            const float* __restrict__ hyper, int lr_idx, int cls, int use_wd, int use_ema,
+                                                            int vec) {
+    const OptHyper h = optim_hyper_load(RULE, hyper, lr_idx, cls, use_wd != 0);
+    optim_ema_walk<RULE>(params, grads, st1, st2, ema, off, n_decay, n_params, n_total, h, use_ema && ema != nullptr, vec != 0);
+}
+
+// grid row y handles run y = {offset, n_decay, n_params, n_total, lr_index, flags (bit 0 weight decay), bc_class, 0} of the device table
+template <int RULE>
+__global__ __launch_bounds__(256) void optim_ema_multi_kernel(float* params, const float* grads, float* st1, float* st2, float* ema,
+                                                              const long long* __restrict__ runs, const float* __restrict__ hyper,
+                                                              int use_ema) {
+    const long long* r = runs + (size_t)blockIdx.y * 8;
+    const OptHyper h = optim_hyper_load(RULE, hyper, (int)r[4], (int)r[6], ((int)r[5] & 1) != 0);
+    optim_ema_walk<RULE>(params, grads, st1, st2, ema, r[0], r[1], r[2], r[3], h, use_ema && ema != nullptr, true);
+}
+
+static inline unsigned optim_grid_x(long long n) {
+    long long gx = (n + 4 + 1023) / 1024;                 // four elements per thread (+ the alignment slack of the first group)
+    if (gx > 2048) gx = 2048;
+    if (gx < 1) gx = 1;
+    return (unsigned)gx;
+}
+
+// per-run forms: the pointers are arena + offset and need not be 16-byte aligned.  When every array the run touches sits at the
+// same distance `lead` (0..3 elements) behind a 16-byte boundary, all are rebased onto that boundary and the run starts at `lead`
+// (the vector walk); otherwise the element walk.
+static inline int optim_lead(const void* p) { return (int)((((uintptr_t)p) >> 2) & 3u); }
+struct OptRebase { float *p, *s1, *s2, *e; const float* g; long long off; int vec; };
+static OptRebase optim_rebase(float* params, const float* grads, float* s1, float* s2, float* ema, bool has_params, bool has_ema) {
+    const int lead = optim_lead(params);
+    bool co = (((uintptr_t)params) & 3u) == 0;
+    if (has_params) co = co && optim_lead(grads) == lead && optim_lead(s1) == lead && optim_lead(s2) == lead;
+    if (has_ema) co = co && optim_lead(ema) == lead;
+    OptRebase r{params, s1, s2, ema, grads, 0, 0};
+    if (co) {
+        r.p = params - lead; r.g = grads - lead; r.s1 = s1 - lead; r.s2 = s2 - lead; r.e = ema ? ema - lead : nullptr;
+        r.off = lead; r.vec = 1;
+    }
+    return r;
+}
+
+#define YDL_OPT_RULE_OK(rule) ((rule) == YDL_OPT_ADAM || (rule) == YDL_OPT_ADAMW || (rule) == YDL_OPT_RMSPROP)
+#define YDL_OPT_DISPATCH(rule, KERNEL, grid, st, ...)                                              \
+    do {                                                                                           \
+        if ((rule) == YDL_OPT_ADAM) KERNEL<YDL_OPT_ADAM><<<grid, 256, 0, st>>>(__VA_ARGS__);       \
+        else if ((rule) == YDL_OPT_ADAMW) KERNEL<YDL_OPT_ADAMW><<<grid, 256, 0, st>>>(__VA_ARGS__); \
+        else KERNEL<YDL_OPT_RMSPROP><<<grid, 256, 0, st>>>(__VA_ARGS__);                           \
+    } while (0)
+
+extern "C" int ydl_optim_ema_step(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
+                                  int64_t n_decay, int64_t n_params, int64_t n_total,
+                                  float step_size, float bc2_sqrt, float decay_mul, float weight_decay,
+                                  float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                                  float grad_scale, float ema_decay, void* stream) {
+    YDL_CHECK(YDL_OPT_RULE_OK(rule), "unknown optimizer rule");
+    YDL_CHECK(params && grads && state1 && state2, "null pointer");
+    YDL_CHECK(0 <= n_decay && n_decay <= n_params && n_params <= n_total, "bad arena partition");
+    const OptHyper h{step_size, bc2_sqrt, decay_mul, weight_decay, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, grad_scale, ema_decay};
+    const OptRebase r = optim_rebase(params, grads, state1, state2, ema, n_params > 0, ema != nullptr && ema_decay >= 0.f);
+    const dim3 grid(optim_grid_x(n_total));
+    hipStream_t st = (hipStream_t)stream;
+    YDL_OPT_DISPATCH(rule, optim_ema_kernel, grid, st, r.p, r.g, r.s1, r.s2, r.e, r.off, (long long)n_decay, (long long)n_params,
+                     (long long)n_total, h, r.vec);
+    YDL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ydl_optim_ema_step_dev(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
+                                      int64_t n_decay, int64_t n_params, int64_t n_total, const float* hyper_dev,
+                                      int lr_index, int bc_class, int use_weight_decay, int use_ema, void* stream) {
+    YDL_CHECK(YDL_OPT_RULE_OK(rule), "unknown optimizer rule");
+    YDL_CHECK(params && grads && state1 && state2 && hyper_dev, "null pointer");
+    YDL_CHECK(0 <= n_decay && n_decay <= n_params && n_params <= n_total, "bad arena partition");
+    YDL_CHECK(lr_index >= 0 && lr_index <= 2 && bc_class >= 0 && bc_class < YDL_OPT_MAX_CLASSES, "bad lr index or bias-correction class");
+    const OptRebase r = optim_rebase(params, grads, state1, state2, ema, n_params > 0, ema != nullptr && use_ema);
+    const dim3 grid(optim_grid_x(n_total));
+    hipStream_t st = (hipStream_t)stream;
+    YDL_OPT_DISPATCH(rule, optim_ema_dev_kernel, grid, st, r.p, r.g, r.s1, r.s2, r.e, r.off, (long long)n_decay, (long long)n_params,
+                     (long long)n_total, hyper_dev, lr_index, bc_class, use_weight_decay, use_ema, r.vec);
+    YDL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ydl_optim_ema_step_multi(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
+                                        const int64_t* runs_dev, int nruns, int64_t max_run, const float* hyper_dev, int use_ema,
+                                        void* stream) {
+    YDL_CHECK(YDL_OPT_RULE_OK(rule), "unknown optimizer rule");
+    YDL_CHECK(params && grads && state1 && state2 && runs_dev && hyper_dev, "null pointer");
+    YDL_CHECK(nruns > 0 && nruns <= 65535 && max_run >= 0, "bad run count");
+    YDL_CHECK(aligned16(params) && aligned16(grads) && aligned16(state1) && aligned16(state2) && (ema == nullptr || aligned16(ema)),
+              "arenas must be 16-byte aligned");
+    const dim3 grid(optim_grid_x(max_run), (unsigned)nruns);
+    hipStream_t st = (hipStream_t)stream;
+    YDL_OPT_DISPATCH(rule, optim_ema_multi_kernel, grid, st, params, grads, state1, state2, ema, (const long long*)runs_dev, hyper_dev,
+                     use_ema);
+    YDL_LAUNCH_CHECK();
+    return 0;
+}

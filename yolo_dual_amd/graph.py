@@ -19,11 +19,11 @@ import torch
 
 from . import config
 from .modules import _BNHolder
-from .optim import FlatSGDEMA
+from .optim import FlatArenaOptimizer
 
 
 class GraphedTrainStep:
-    def __init__(self, model, criterion, optimizer: FlatSGDEMA, imgs: torch.Tensor, targets: torch.Tensor,
+    def __init__(self, model, criterion, optimizer: FlatArenaOptimizer, imgs: torch.Tensor, targets: torch.Tensor,
                  dp=None, warmup: int = 3, segmented: Optional[bool] = None):
         self.model, self.criterion, self.opt, self.dp = model, criterion, optimizer, dp
         if segmented is None:

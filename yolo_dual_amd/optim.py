@@ -1,4 +1,6 @@
-"""Flat-arena SGD(nesterov) + EMA: the optimizer step of the hot path as ONE fused HIP kernel per parameter run.
+"""Flat-arena optimizers + EMA: the optimizer step of the hot path as ONE fused HIP kernel per parameter run.  ``FlatSGDEMA`` is
+the scripts' SGD(nesterov); ``FlatAdamEMA`` / ``FlatAdamWEMA`` / ``FlatRMSPropEMA`` are the other names ``smart_optimizer`` takes.
+All share the arenas, the slots, the EMA shadow and the run tables of ``FlatArenaOptimizer``.
 
 Semantics restate ``smart_optimizer(model, 'SGD', lr, momentum, decay)`` (utils/torch_utils.py:318-346: three groups —
 biases / BN weights without decay, other weights with decay; torch.optim.SGD(nesterov=True)) and ``ModelEMA``
@@ -29,9 +31,14 @@ def _is_bn(m: nn.Module) -> bool:
     return "Norm" in type(m).__name__ or isinstance(m, nn.modules.batchnorm._BatchNorm)
 
 
-class FlatSGDEMA(torch.optim.Optimizer):
-    def __init__(self, model: nn.Module, lr: float = 0.01, momentum: float = 0.937, weight_decay: float = 5e-4,
-                 ema: bool = True, ema_decay: float = 0.9999, ema_tau: float = 2000.0, ema_updates: int = 0):
+class FlatArenaOptimizer(torch.optim.Optimizer):
+    """what every flat-arena optimizer shares: the arenas ``[weights with decay | BN weights | biases | float buffers]``, the slots,
+    the EMA shadow, the device hyper-parameter vector with its pinned ring, and the cache of device run tables.  A rule adds its
+    state arenas (``n_state`` of them, allocated once between the gradient arena and the EMA shadow), its param_groups and its step"""
+    _HYPER_FLOATS = 7
+
+    def _init_arenas(self, model: nn.Module, n_state: int, ema: bool, ema_decay: float, ema_tau: float, ema_updates: int):
+        """lay the model out in the arenas; returns (decay weights, BN weights, biases, device)"""
         g0, g1, g2 = [], [], []          # decay weights, BN weights, biases   (names kept for the arena order)
         seen = set()
         for mod in model.modules():
@@ -59,7 +66,7 @@ class FlatSGDEMA(torch.optim.Optimizer):
         self.n_total = self.n_params + sum(b.numel() for b in bufs)
         self.params_arena = torch.empty(self.n_total, dtype=torch.float32, device=dev)
         self.grads_arena = torch.zeros(self.n_params, dtype=torch.float32, device=dev)
-        self.mom_arena = torch.zeros(self.n_params, dtype=torch.float32, device=dev)
+        self._state_arenas = [torch.zeros(self.n_params, dtype=torch.float32, device=dev) for _ in range(n_state)]
         self.ema_arena = torch.empty(self.n_total, dtype=torch.float32, device=dev) if ema else None
         self._slots: List[Tuple[nn.Parameter, int, int, int]] = []      # (param, offset, numel, group)
         off = 0
@@ -80,13 +87,14 @@ class FlatSGDEMA(torch.optim.Optimizer):
         if ema:
             self.ema_arena.copy_(self.params_arena)
         self.ema_decay, self.ema_tau, self.updates = ema_decay, ema_tau, ema_updates
-        self._has_buf: Dict[int, bool] = {}
-        # torch.optim.Optimizer plumbing (lr schedulers read/write param_groups[*]['lr']); group order follows
-        # smart_optimizer: biases, decay weights, BN weights
-        defaults = dict(lr=lr, momentum=momentum, nesterov=True, weight_decay=0.0)
-        super().__init__([{"params": g2 or [torch.nn.Parameter(torch.zeros(0, device=dev))]},
-                          {"params": g0, "weight_decay": weight_decay},
-                          {"params": g1, "weight_decay": 0.0}], defaults)
+        return g0, g1, g2, dev
+
+    def _init_groups(self, g0, g1, g2, dev, defaults: dict, weight_decay: float) -> None:
+        """torch.optim.Optimizer plumbing (lr schedulers read/write param_groups[*]['lr']); group order follows
+        smart_optimizer: biases, decay weights, BN weights"""
+        torch.optim.Optimizer.__init__(self, [{"params": g2 or [torch.nn.Parameter(torch.zeros(0, device=dev))]},
+                                              {"params": g0, "weight_decay": weight_decay},
+                                              {"params": g1, "weight_decay": 0.0}], defaults)
         config.bump_weight_epoch()
 
     # ------------------------------------------------------------------
@@ -137,10 +145,87 @@ class FlatSGDEMA(torch.optim.Optimizer):
         if getattr(self, "_hyper_ring", None) is None:
             # ring of pinned staging buffers, each guarded by the event of its last H2D copy: the host never rewrites a
             # buffer whose copy may still be queued behind a graph replay (one reused buffer raced with the next step's write)
-            self._hyper_ring = [(torch.empty(7, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(8)]
+            self._hyper_ring = [(torch.zeros(self._HYPER_FLOATS, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(8)]
             self._hyper_slot = 0
             self._hyper_used = [False] * 8
-            self._hyper_dev = torch.empty(7, dtype=torch.float32, device=self.params_arena.device)
+            self._hyper_dev = torch.zeros(self._HYPER_FLOATS, dtype=torch.float32, device=self.params_arena.device)
+
+    def ensure_runs_table(self) -> None:
+        """device table of the CURRENT run structure (as the last backward left the touched flags), created now: call after the
+        warm-up steps and before entering a private pool, next to ``ensure_hyper``"""
+        sig = self._run_rows(self._runs(commit=False))
+        if sig:
+            self._runs_dev = self._runs_table(sig)
+
+    def _runs_table(self, sig: tuple) -> tuple:
+        """(signature, device table) for a run structure.  Tables are cached per signature and never freed: a recorded launch list or
+        a captured graph holds the raw device pointer of the table it was recorded with, and a later eager step with another
+        structure (a freeze change, a different touched set) must not hand that block back to the allocator"""
+        cache = self.__dict__.setdefault("_runs_cache", {})
+        tab = cache.get(sig)
+        if tab is None:
+            n_tot = self.n_total
+            for row in sig:                             # rows index the arenas unchecked in the kernel: validate them here
+                off, n = row[0], row[3]
+                if off < 0 or n < 0 or off + n > n_tot:
+                    raise RuntimeError(f"optimizer run table row ({off}, {n}) outside the arenas ({n_tot})")
+            tab = (sig, torch.tensor(sig, dtype=torch.int64).to(self.params_arena.device))
+            cache[sig] = tab
+        return tab
+
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        """restore the EMA shadow from a ``state_dict`` (smart_resume: ``ema.ema.load_state_dict(ckpt['ema']...)``)"""
+        if self.ema_arena is None:
+            raise RuntimeError("EMA disabled")
+        cur = self.ema_state_dict()
+        by_ptr = {}
+        for p, off, n, _g in self._slots:
+            by_ptr[p.data_ptr()] = (off, n)
+        for b, off, n in self._buf_slots:
+            by_ptr[b.data_ptr()] = (off, n)
+        for k, v in self.model.state_dict().items():
+            slot = by_ptr.get(v.data_ptr())
+            if slot is None or not v.dtype.is_floating_point or k not in sd or tuple(sd[k].shape) != tuple(cur[k].shape):
+                continue
+            off, n = slot
+            src = sd[k].float().to(self.ema_arena.device)
+            if v.dim() == 4:
+                src = src.permute(0, 2, 3, 1).contiguous()
+            self.ema_arena[off:off + n].copy_(src.reshape(-1))
+
+    # ------------------------------------------------------------------ EMA access (ModelEMA.ema equivalent)
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """state_dict of the EMA shadow (same keys as model.state_dict(); integer buffers are copied as is)."""
+        if self.ema_arena is None:
+            raise RuntimeError("EMA disabled")
+        by_ptr = {}
+        for p, off, n, _g in self._slots:
+            by_ptr[p.data_ptr()] = (off, n)
+        for b, off, n in self._buf_slots:
+            by_ptr[b.data_ptr()] = (off, n)
+        out = {}
+        for k, v in self.model.state_dict().items():
+            slot = by_ptr.get(v.data_ptr())
+            if slot is None or not v.dtype.is_floating_point:
+                out[k] = v.clone()
+                continue
+            off, n = slot
+            flat = self.ema_arena[off:off + n]
+            if v.dim() == 4:
+                O, I, kh, kw = v.shape
+                out[k] = flat.view(O, kh, kw, I).permute(0, 3, 1, 2).clone()
+            else:
+                out[k] = flat.view(v.shape).clone()
+        return out
+
+
+class FlatSGDEMA(FlatArenaOptimizer):
+    def __init__(self, model: nn.Module, lr: float = 0.01, momentum: float = 0.937, weight_decay: float = 5e-4,
+                 ema: bool = True, ema_decay: float = 0.9999, ema_tau: float = 2000.0, ema_updates: int = 0):
+        g0, g1, g2, dev = self._init_arenas(model, 1, ema, ema_decay, ema_tau, ema_updates)
+        self.mom_arena = self._state_arenas[0]
+        self._has_buf: Dict[int, bool] = {}
+        self._init_groups(g0, g1, g2, dev, dict(lr=lr, momentum=momentum, nesterov=True, weight_decay=0.0), weight_decay)
 
     def prepare_step(self, grad_scale: float = 1.0) -> None:
         """host half of a step: advance the EMA counter and push {lr, momentum, wd, grad_scale, ema decay} to the device
@@ -191,28 +276,6 @@ class FlatSGDEMA(torch.optim.Optimizer):
         if self.ema_arena is not None and self.n_total > self.n_params:
             rows.append((self.n_params, 0, 0, self.n_total - self.n_params, 0, 0))
         return tuple(rows)
-
-    def ensure_runs_table(self) -> None:
-        """device table of the CURRENT run structure (as the last backward left the touched flags), created now: call after the
-        warm-up steps and before entering a private pool, next to ``ensure_hyper``"""
-        sig = self._run_rows(self._runs(commit=False))
-        if sig:
-            self._runs_dev = self._runs_table(sig)
-
-    def _runs_table(self, sig: tuple) -> tuple:
-        """(signature, device table) for a run structure.  Tables are cached per signature and never freed: a recorded launch list or
-        a captured graph holds the raw device pointer of the table it was recorded with, and a later eager step with another
-        structure (a freeze change, a different touched set) must not hand that block back to the allocator"""
-        cache = self.__dict__.setdefault("_runs_cache", {})
-        tab = cache.get(sig)
-        if tab is None:
-            n_tot = self.n_total
-            for off, _nd, _np, n, _gi, _fl in sig:      # rows index the arenas unchecked in the kernel: validate them here
-                if off < 0 or n < 0 or off + n > n_tot:
-                    raise RuntimeError(f"optimizer run table row ({off}, {n}) outside the arenas ({n_tot})")
-            tab = (sig, torch.tensor(sig, dtype=torch.int64).to(self.params_arena.device))
-            cache[sig] = tab
-        return tab
 
     @torch.no_grad()
     def step_device_hyper(self) -> None:
@@ -315,55 +378,243 @@ class FlatSGDEMA(torch.optim.Optimizer):
             self._has_buf[id(p)] = bool(h)
         self.updates = int(sd.get("updates", 0))
 
-    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        """restore the EMA shadow from a ``state_dict`` (smart_resume: ``ema.ema.load_state_dict(ckpt['ema']...)``)"""
-        if self.ema_arena is None:
-            raise RuntimeError("EMA disabled")
-        cur = self.ema_state_dict()
-        by_ptr = {}
-        for p, off, n, _g in self._slots:
-            by_ptr[p.data_ptr()] = (off, n)
-        for b, off, n in self._buf_slots:
-            by_ptr[b.data_ptr()] = (off, n)
-        for k, v in self.model.state_dict().items():
-            slot = by_ptr.get(v.data_ptr())
-            if slot is None or not v.dtype.is_floating_point or k not in sd or tuple(sd[k].shape) != tuple(cur[k].shape):
-                continue
-            off, n = slot
-            src = sd[k].float().to(self.ema_arena.device)
-            if v.dim() == 4:
-                src = src.permute(0, 2, 3, 1).contiguous()
-            self.ema_arena[off:off + n].copy_(src.reshape(-1))
 
-    # ------------------------------------------------------------------ EMA access (ModelEMA.ema equivalent)
-    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
-        """state_dict of the EMA shadow (same keys as model.state_dict(); integer buffers are copied as is)."""
+class _FlatAdaptiveEMA(FlatArenaOptimizer):
+    """Adam / AdamW / RMSProp over the arenas: torch.optim's single-tensor update per element (csrc/optim.hip), two state arenas
+    (``state1_arena``: exp_avg | momentum buffer, ``state2_arena``: exp_avg_sq | square_avg), a step count per slot.
+
+    Like torch, a parameter without a gradient this step is skipped entirely (no decay, no state update, its step count ``t`` does not
+    advance), so parameters can sit at different ``t``.  Everything torch derives from ``t`` in Python double precision — the bias
+    corrections, ``lr / (1 - beta1^t)``, ``1 - lr*wd`` — is computed here in double and reaches the kernels rounded once to f32.
+    Parameters with the same ``t`` form a bias-correction class; runs never span two classes."""
+    RULE = 0
+    FORMAT = ""
+    _HYPER_FLOATS = L.OPT_HYPER_FLOATS
+
+    def _init_adaptive(self, model, defaults: dict, weight_decay: float, ema, ema_decay, ema_tau, ema_updates) -> None:
+        g0, g1, g2, dev = self._init_arenas(model, 2, ema, ema_decay, ema_tau, ema_updates)
+        self.state1_arena, self.state2_arena = self._state_arenas
+        self._steps: List[int] = [0] * len(self._slots)          # torch's state['step'] of every slot
+        self._init_groups(g0, g1, g2, dev, defaults, weight_decay)
+
+    # ------------------------------------------------------------------ per-step numbers (host, double precision)
+    def _betas(self) -> Tuple[float, float, float]:
+        """(beta1 | momentum, beta2 | alpha, eps) of the weights group"""
+        g = self.param_groups[1]
+        if self.RULE == L.OPT_RMSPROP:
+            return float(g["momentum"]), float(g["alpha"]), float(g["eps"])
+        return float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+
+    def _corrections(self, t: int, lr: float) -> Tuple[float, float]:
+        """(step_size, bc2_sqrt) of a parameter at step count ``t`` with learning rate ``lr``"""
+        if self.RULE == L.OPT_RMSPROP:
+            return lr, 1.0
+        b1, b2, _eps = self._betas()
+        return lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5
+
+    def _ema_d(self, off: float) -> float:
         if self.ema_arena is None:
-            raise RuntimeError("EMA disabled")
-        by_ptr = {}
-        for p, off, n, _g in self._slots:
-            by_ptr[p.data_ptr()] = (off, n)
-        for b, off, n in self._buf_slots:
-            by_ptr[b.data_ptr()] = (off, n)
-        out = {}
-        for k, v in self.model.state_dict().items():
-            slot = by_ptr.get(v.data_ptr())
-            if slot is None or not v.dtype.is_floating_point:
-                out[k] = v.clone()
-                continue
-            off, n = slot
-            flat = self.ema_arena[off:off + n]
-            if v.dim() == 4:
-                O, I, kh, kw = v.shape
-                out[k] = flat.view(O, kh, kw, I).permute(0, 3, 1, 2).clone()
+            return off
+        self.updates += 1
+        return self.ema_decay * (1.0 - math.exp(-self.updates / self.ema_tau))
+
+    def _advance(self) -> None:
+        """step_t += 1 of every parameter that received a gradient"""
+        for i, (p, *_r) in enumerate(self._slots):
+            if getattr(p, "_ydl_touched", False):
+                self._steps[i] += 1
+
+    def _classes(self) -> Dict[int, int]:
+        """step count -> bias-correction class, over the live parameters, in ascending order of the count: while the same set of
+        parameters stays live every count advances together, so a recorded / captured class index keeps its meaning"""
+        if self.RULE == L.OPT_RMSPROP:
+            return {}
+        ts = sorted({t for (p, *_r), t in zip(self._slots, self._steps) if getattr(p, "_ydl_touched", False)})
+        return {t: c for c, t in enumerate(ts)}
+
+    def _runs(self, commit: bool = False) -> List[List]:
+        """maximal runs of consecutive slots with identical (touched, group, step count) state.  ``commit`` is accepted for the
+        protocol of FlatSGDEMA and ignored: the step counts advance in ``step`` / ``prepare_step``"""
+        runs: List[List] = []
+        rms = self.RULE == L.OPT_RMSPROP
+        for (p, off, n, gi), t in zip(self._slots, self._steps):
+            touched = bool(getattr(p, "_ydl_touched", False))
+            key = (touched, gi, t if touched and not rms else 0)
+            if runs and runs[-1][0] == key and runs[-1][2] == off:
+                runs[-1][2] = off + n
             else:
-                out[k] = flat.view(v.shape).clone()
-        return out
+                runs.append([key, off, off + n])
+        return runs
+
+    def _run_rows(self, runs) -> tuple:
+        """rows {offset, n_decay, n_params, n_total, lr index, flags, bias-correction class, 0} of ydl_optim_ema_step_multi"""
+        cls = self._classes()
+        rows = []
+        for (touched, gi, t), a, b in runs:
+            n = b - a
+            if touched:
+                rows.append((a, n if gi == 0 else 0, n, n, gi, 1 if gi == 0 else 0, cls.get(t, 0), 0))
+            elif self.ema_arena is not None:
+                rows.append((a, 0, 0, n, 0, 0, 0, 0))
+        if self.ema_arena is not None and self.n_total > self.n_params:
+            rows.append((self.n_params, 0, 0, self.n_total - self.n_params, 0, 0, 0, 0))
+        return tuple(rows)
+
+    # ------------------------------------------------------------------ graph-capturable step
+    def prepare_step(self, grad_scale: float = 1.0) -> None:
+        """host half of a step: advance the EMA counter and the step counts of the live parameters, and push the hyper-parameters,
+        the bias corrections of every class and the EMA decay to the device vector the captured kernels read (call OUTSIDE the
+        graph, before replaying it; layout: ydl.h, ydl_optim_ema_step_dev)"""
+        lr_bias, lr_w, lr_bn = (float(g["lr"]) for g in self.param_groups)
+        lrs = (lr_w, lr_bn, lr_bias)
+        d = self._ema_d(0.0)
+        self._advance()
+        cls = self._classes()
+        if len(cls) > L.OPT_MAX_CLASSES:
+            raise RuntimeError(f"{len(cls)} distinct step counts among the live parameters: the device hyper vector holds "
+                               f"{L.OPT_MAX_CLASSES} bias-correction classes (use step(), which has no such limit)")
+        b1, b2, eps = self._betas()
+        wd = float(self.param_groups[1]["weight_decay"])
+        vals = [0.0] * self._HYPER_FLOATS
+        vals[0:12] = [lr_w, lr_bn, lr_bias, b1, wd, grad_scale, d, b2, eps, 1.0 - b1, 1.0 - b2, 1.0 - lr_w * wd]
+        for t, c in cls.items():
+            for i in range(3):
+                vals[12 + 4 * c + i], vals[12 + 4 * c + 3] = self._corrections(t, lrs[i])
+        self.ensure_hyper()
+        i = self._hyper_slot
+        self._hyper_slot = (i + 1) % len(self._hyper_ring)
+        h, ev = self._hyper_ring[i]
+        if self._hyper_used[i]:
+            ev.synchronize()              # normally long complete (8 steps ago)
+        h.copy_(torch.tensor(vals, dtype=torch.float64))         # one rounding, double -> f32
+        self._hyper_dev.copy_(h, non_blocking=True)
+        ev.record()
+        self._hyper_used[i] = True
+
+    @torch.no_grad()
+    def step_device_hyper(self) -> None:
+        """device half: the update with everything read from ``_hyper_dev`` (capturable).  Changes no host state: ``prepare_step``
+        has advanced the counters"""
+        st = _stream()
+        pa, ga, s1, s2, ea = self.params_arena, self.grads_arena, self.state1_arena, self.state2_arena, self.ema_arena
+        use_ema = 1 if ea is not None else 0
+        hp = _p(self._hyper_dev)
+        rows = self._run_rows(self._runs())
+        # one launch for all runs; inside a recording / capture pass a NEW table must not be allocated (private pool), so a miss
+        # there takes the per-run launches below (see FlatSGDEMA.step_device_hyper)
+        tab = getattr(self, "_runs_dev", None)
+        if (tab is None or tab[0] != rows) and rows and L.recorder() is None and not torch.cuda.is_current_stream_capturing():
+            tab = self._runs_table(rows)
+            self._runs_dev = tab
+        if tab is not None and tab[0] == rows:
+            if rows:
+                L.call("ydl_optim_ema_step_multi", self.RULE, _p(pa), _p(ga), _p(s1), _p(s2), _p(ea) if ea is not None else None,
+                       _p(tab[1]), len(rows), max(r[3] for r in rows), hp, use_ema, st)
+            config.bump_weight_epoch()
+            return
+        for off, nd, npar, n, gi, fl, c, _z in rows:
+            if npar:
+                L.call("ydl_optim_ema_step_dev", self.RULE, _p(pa[off:]), _p(ga[off:]), _p(s1[off:]), _p(s2[off:]),
+                       _p(ea[off:]) if ea is not None else None, nd, npar, n, hp, gi, c, fl & 1, use_ema, st)
+            else:                       # EMA only (dead parameters, float buffers): gradients and state are not read
+                L.call("ydl_optim_ema_step_dev", self.RULE, _p(pa[off:]), _p(ga), _p(s1), _p(s2), _p(ea[off:]), 0, 0, n, hp, 0, 0, 0, 1, st)
+        config.bump_weight_epoch()
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale: float = 1.0):
+        lr_bias, lr_w, lr_bn = (float(g["lr"]) for g in self.param_groups)
+        lrs = (lr_w, lr_bn, lr_bias)
+        b1, b2, eps = self._betas()
+        wd = float(self.param_groups[1]["weight_decay"])
+        d = self._ema_d(-1.0)
+        self._advance()
+        st = _stream()
+        pa, ga, s1, s2, ea = self.params_arena, self.grads_arena, self.state1_arena, self.state2_arena, self.ema_arena
+        for (touched, gi, t), a, b in self._runs():
+            n = b - a
+            eptr = _p(ea[a:b]) if ea is not None else None
+            if touched:
+                step_size, bc2s = self._corrections(t, lrs[gi])
+                L.call("ydl_optim_ema_step", self.RULE, _p(pa[a:b]), _p(ga[a:b]), _p(s1[a:b]), _p(s2[a:b]), eptr, n if gi == 0 else 0, n, n,
+                       step_size, bc2s, 1.0 - lr_w * wd, wd if gi == 0 else 0.0, b1, b2, 1.0 - b1, 1.0 - b2, eps, grad_scale, d, st)
+            elif ea is not None:
+                L.call("ydl_optim_ema_step", self.RULE, _p(pa[a:b]), _p(ga), _p(s1), _p(s2), eptr, 0, 0, n,
+                       0.0, 1.0, 1.0, 0.0, b1, b2, 1.0 - b1, 1.0 - b2, eps, 1.0, d, st)
+        if ea is not None and self.n_total > self.n_params:
+            a, b = self.n_params, self.n_total
+            L.call("ydl_optim_ema_step", self.RULE, _p(pa[a:b]), _p(ga), _p(s1), _p(s2), _p(ea[a:b]), 0, 0, b - a,
+                   0.0, 1.0, 1.0, 0.0, b1, b2, 1.0 - b1, 1.0 - b2, eps, 1.0, d, st)
+        config.bump_weight_epoch()
+        return None
+
+    # ------------------------------------------------------------------ checkpoint state
+    def state_dict(self):
+        """hyper-parameters per group, both state arenas, the step count of every slot and the EMA update counter (plain tensors /
+        numbers only, so the file loads with ``torch.load(..., weights_only=True)``); ``format`` names the rule"""
+        return {"format": self.FORMAT,
+                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
+                "state1": self.state1_arena.detach().cpu().clone(),
+                "state2": self.state2_arena.detach().cpu().clone(),
+                "steps": torch.tensor(self._steps, dtype=torch.int64),
+                "updates": int(self.updates)}
+
+    def load_state_dict(self, sd) -> None:
+        if sd.get("format") != self.FORMAT:
+            raise ValueError(f"optimizer state was not written by yolo_dual_amd.{type(self).__name__} "
+                             f"(format {sd.get('format')!r}, expected {self.FORMAT!r})")
+        if (sd["state1"].numel() != self.state1_arena.numel() or sd["state2"].numel() != self.state2_arena.numel()
+                or sd["steps"].numel() != len(self._slots)):
+            raise ValueError("optimizer state belongs to a different model (arena size or slot count differs)")
+        for g, gs in zip(self.param_groups, sd["param_groups"]):
+            g.update(gs)
+            if "betas" in g:
+                g["betas"] = tuple(g["betas"])
+        self.state1_arena.copy_(sd["state1"].to(self.state1_arena.device))
+        self.state2_arena.copy_(sd["state2"].to(self.state2_arena.device))
+        self._steps = [int(t) for t in sd["steps"].tolist()]
+        self.updates = int(sd.get("updates", 0))
+
+
+class FlatAdamEMA(_FlatAdaptiveEMA):
+    """torch.optim.Adam(betas=(momentum, 0.999)) — weight decay coupled (added to the gradient), on the weights group only"""
+    RULE, FORMAT = L.OPT_ADAM, "ydl-flat-adam-ema-1"
+
+    def __init__(self, model: nn.Module, lr: float = 0.001, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, ema: bool = True, ema_decay: float = 0.9999, ema_tau: float = 2000.0, ema_updates: int = 0):
+        self._init_adaptive(model, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0.0, amsgrad=False, maximize=False),
+                            weight_decay, ema, ema_decay, ema_tau, ema_updates)
+
+
+class FlatAdamWEMA(_FlatAdaptiveEMA):
+    """torch.optim.AdamW(betas=(momentum, 0.999)) — weight decay decoupled (``p *= 1 - lr*wd``), on the weights group only"""
+    RULE, FORMAT = L.OPT_ADAMW, "ydl-flat-adamw-ema-1"
+
+    def __init__(self, model: nn.Module, lr: float = 0.001, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, ema: bool = True, ema_decay: float = 0.9999, ema_tau: float = 2000.0, ema_updates: int = 0):
+        self._init_adaptive(model, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0.0, amsgrad=False, maximize=False),
+                            weight_decay, ema, ema_decay, ema_tau, ema_updates)
+
+
+class FlatRMSPropEMA(_FlatAdaptiveEMA):
+    """torch.optim.RMSprop(momentum=momentum) — alpha 0.99, not centered; weight decay coupled, on the weights group only"""
+    RULE, FORMAT = L.OPT_RMSPROP, "ydl-flat-rmsprop-ema-1"
+
+    def __init__(self, model: nn.Module, lr: float = 0.01, alpha: float = 0.99, eps: float = 1e-8, momentum: float = 0.0,
+                 weight_decay: float = 0.0, ema: bool = True, ema_decay: float = 0.9999, ema_tau: float = 2000.0, ema_updates: int = 0):
+        self._init_adaptive(model, dict(lr=lr, alpha=alpha, eps=eps, momentum=momentum, centered=False, weight_decay=0.0, maximize=False),
+                            weight_decay, ema, ema_decay, ema_tau, ema_updates)
 
 
 def smart_optimizer(model: nn.Module, name: str = "SGD", lr: float = 0.001, momentum: float = 0.9,
-                    decay: float = 1e-5, ema: bool = True) -> FlatSGDEMA:
-    """utils/torch_utils.py:318-346 signature; only the SGD-nesterov branch (what the seg scripts use) has a HIP path."""
-    if name != "SGD":
-        raise NotImplementedError(f"optimizer {name}: the fused HIP step implements the scripts' SGD(nesterov) only")
-    return FlatSGDEMA(model, lr=lr, momentum=momentum, weight_decay=decay, ema=ema)
+                    decay: float = 1e-5, ema: bool = True) -> FlatArenaOptimizer:
+    """utils/torch_utils.py:318-346 signature and names: Adam / AdamW take ``betas=(momentum, 0.999)``, RMSProp and SGD take
+    ``momentum``, SGD is nesterov; every name runs the fused HIP step."""
+    if name == "Adam":
+        return FlatAdamEMA(model, lr=lr, betas=(momentum, 0.999), weight_decay=decay, ema=ema)
+    if name == "AdamW":
+        return FlatAdamWEMA(model, lr=lr, betas=(momentum, 0.999), weight_decay=decay, ema=ema)
+    if name == "RMSProp":
+        return FlatRMSPropEMA(model, lr=lr, momentum=momentum, weight_decay=decay, ema=ema)
+    if name == "SGD":
+        return FlatSGDEMA(model, lr=lr, momentum=momentum, weight_decay=decay, ema=ema)
+    raise NotImplementedError(f'Optimizer {name} not implemented.')

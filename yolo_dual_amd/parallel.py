@@ -29,7 +29,7 @@ import torch
 import torch.distributed as dist
 
 from . import config
-from .optim import FlatSGDEMA
+from .optim import FlatArenaOptimizer
 
 
 def _local_ops(t: torch.Tensor):
@@ -84,7 +84,7 @@ def pin_rank_to_cores(local_rank: int, local_world: int) -> list:
 
 
 class GradBucketReducer:
-    def __init__(self, opt: FlatSGDEMA, bucket_bytes: int = 16 << 20, group=None, algo: str = "allreduce", wire: str = "f32"):
+    def __init__(self, opt: FlatArenaOptimizer, bucket_bytes: int = 16 << 20, group=None, algo: str = "allreduce", wire: str = "f32"):
         if algo not in ("allreduce", "rs_ag") or wire not in ("f32", "bf16"):
             raise ValueError("algo must be 'allreduce' or 'rs_ag', wire 'f32' or 'bf16'")
         self.opt = opt
@@ -313,7 +313,7 @@ class DataParallel:
     """Thin training-step helper: ``dp = DataParallel(model, opt)``; per step ``dp.begin(); loss.backward();
     scale = dp.finish(); opt.step(grad_scale=scale)``."""
 
-    def __init__(self, model, opt: FlatSGDEMA, bucket_bytes: int = 16 << 20, group=None, broadcast: bool = True,
+    def __init__(self, model, opt: FlatArenaOptimizer, bucket_bytes: int = 16 << 20, group=None, broadcast: bool = True,
                  algo: str = "allreduce", wire: str = "f32"):
         self.model, self.opt = model, opt
         self.reducer = GradBucketReducer(opt, bucket_bytes, group, algo=algo, wire=wire)

@@ -30,7 +30,7 @@ import torch
 from . import _lib as L
 from . import config
 from .modules import _BNHolder
-from .optim import FlatSGDEMA
+from .optim import FlatArenaOptimizer
 
 _G = L._G
 
@@ -128,7 +128,7 @@ class ReplayedTrainStep:
     With a data-parallel wrapper (``dp``) the list is cut where the eager step launches a gradient bucket: a replay alternates
     "segment, bucket collective" exactly like eager mode, collectives overlapping the remaining backward segments."""
 
-    def __init__(self, model, criterion, optimizer: FlatSGDEMA, imgs: torch.Tensor, targets: torch.Tensor, dp=None, warmup: int = 2,
+    def __init__(self, model, criterion, optimizer: FlatArenaOptimizer, imgs: torch.Tensor, targets: torch.Tensor, dp=None, warmup: int = 2,
                  prioritize: bool = False):
         if getattr(criterion, "sync", False):
             raise ValueError("a launch list needs a loss that does not sync: SegmentationLoss(..., sync=False)")
