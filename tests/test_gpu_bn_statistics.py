@@ -20,7 +20,8 @@ Bounds (mean errors in units of the channel's standard deviation sigma_c, varian
 an MI355X, capped at 1e-4 (the bound of the analysis: the partial-row merges run in double, the only f32 cancellation is within a
 tile of <= 256 pixels).  Replica sums add raw f32 sums of squares: their variance error grows as 3e-7 x r^2 (measured) and
 is not asserted at r = 32.  Kernels whose statistics are those of bf16-ROUNDED values (the accumulating point-wise launch on its
-transposed-store path, the weights-in-registers kernel) keep the 1e-4 bounds: the rounding alone is 2^-9 per value."""
+transposed-store path) keep the 1e-4 bounds: the rounding alone is 2^-9 per value.  (The weights-in-registers kernel used to be
+one of them; it reduces its f32 accumulators now and is held to the f32 bounds.)"""
 import ctypes
 
 import numpy as np
@@ -364,7 +365,7 @@ def test_partial_rows_contract(tag):
 SUMS_EXPECT = {"wreg_refused": "igemm2w_kernel<64"}
 # statistics of bf16-rounded values: (tag, form)
 BF16_STATS = {"pw_bf16_acc"}
-BF16_STATS_SUMS = {"pw_bf16_acc", "wreg_refused"}
+BF16_STATS_SUMS = {"pw_bf16_acc"}
 
 
 @pytest.mark.parametrize("tag", ROW_IDS)

@@ -256,13 +256,14 @@ def test_full_size_bf16_training_tracks_the_f32_parity_mode():
     assert abs(f32f.mean() - bf16f.mean()) <= 0.05, (f32f, bf16f)        # (the north star allows 0.1)
 
 
-@pytest.mark.parametrize("hw,bs", [((95, 81), 1), ((64, 96), 3), ((160, 128), 2), ((320, 320), 2)])
+@pytest.mark.parametrize("hw,bs", [((95, 81), 1), ((64, 96), 3), ((160, 128), 2), ((320, 320), 2), ((640, 640), 2)])
 def test_ragged_input_sizes_match_the_oracle(hw, bs):
     """odd / non-square inputs and batch 1 through the whole yolov5 model in parity mode: every layer size becomes ragged
     (odd strides-2 outputs, bilinear concat alignment between unequal maps, the stem falls back from the space-to-depth
     form when a side is odd), forward logits, loss and the gradient of every live parameter against the CPU oracle.
     320x320 at batch 2 is the whole model at half the benchmark's linear size: its 160x160 / 80x80 layers run the 128-pixel
-    tiles and the point-wise streaming kernel of the benchmark (51 200 ... 204 800 pixels per layer)."""
+    tiles and the point-wise streaming kernel of the benchmark (51 200 ... 204 800 pixels per layer); 640x640 at batch 2 is the
+    benchmark's own resolution."""
     import yolo_dual_amd as ydl
     from tests.util import l2_err, rel_err
     cfg = _cfg()

@@ -1801,9 +1801,11 @@ __global__ __launch_bounds__(NW * 64) void igemm2hs_kernel(const IgemmArgs p) {
 // fragment is one image row of the block: 32 consecutive patch rows, conflict-free under the (row >> 1) & 7 chunk swizzle at any
 // offset).  8 waves = CG channel groups x PG pixel groups, two image rows per wave; per block 72 MFMAs and 72 ds_read_b128 per
 // wave (LDS at 50 % of its bandwidth), one DMA wait + two barriers.  Epilogue: bf16 through a swizzled LDS tile into whole pixel rows
-// (asm stores, counted vmcnt); BatchNorm statistics (replica-sum mode only) are taken from that tile in the row layout — a thread
-// owns one 16-byte channel chunk for the whole kernel: (sum, sum of squares) of the STORED values in 16 registers, one atomic pass per
-// CTA.  The layers are then bound by HBM (64 -> 128: 157 MB) rather than by the staging path.
+// (asm stores, counted vmcnt); BatchNorm statistics (replica-sum mode only) are taken from the f32 ACCUMULATORS in the MFMA layout,
+// before the rounding to bf16, like every other forward kernel of this file — a lane owns 16 channels for the whole kernel: (sum, sum
+// of squares) in 32 registers, one cross-lane reduction and one atomic pass per CTA.  (They used to be taken from the bf16 tile:
+// the sum of n rounded values is off by 1.7e-3 sqrt(sum of squares) rms, which the launch census saw at 5.07e-3 on one channel of
+// ResNet50's 32 x 160 x 160 x 64 layer, above the 5e-3 every statistics launch is held to.)  The layers are then bound by HBM (64 -> 128: 157 MB) rather than by the staging path.
 // ------------------------------------------------------------------------------------------------------
 // A 16-byte store issued from inline asm: the hardware reads the four data registers over two cycles AFTER issue, and a vector
 // instruction that rewrites one of them in the next cycle wins the race (the compiler's hazard recognizer pads a store it knows with
@@ -1829,7 +1831,7 @@ __global__ __launch_bounds__(NW * 64, 2) void igemm2w_kernel(const IgemmArgs p, 
     static_assert(BPX * NCH == 4 * NT && NT % NCH == 0, "four 16-byte store slots per thread, a fixed channel chunk per thread");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const stage = smem + 2 * PBYTES;                       // [BPX][ORB], chunk q of pixel x at slot q ^ (x & (NCH - 1))
-    float* const sred = (float*)smem;                                     // (after the last block) [NW waves][CO][2]
+    float* const sred = (float*)smem;                                     // (after the last block) [PG pixel groups][CO][2]
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int cg = wave % CG, pg = wave / CG;
@@ -1891,9 +1893,9 @@ __global__ __launch_bounds__(NW * 64, 2) void igemm2w_kernel(const IgemmArgs p, 
     int tapd[9];
 #pragma unroll
     for (int tp = 0; tp < 9; ++tp) tapd[tp] = (int)p.dh[tp] * WR_PW + (int)p.dw[tp];
-    float s1[STATS ? 8 : 1], s2[STATS ? 8 : 1];
+    float s1[STATS ? 16 : 1], s2[STATS ? 16 : 1];                         // channel cg * 32 + 8 g + 4 lh + e at index 4 g + e
 #pragma unroll
-    for (int e = 0; e < (STATS ? 8 : 1); ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+    for (int e = 0; e < (STATS ? 16 : 1); ++e) { s1[e] = 0.f; s2[e] = 0.f; }
     const bool want_stats = STATS && p.stats != nullptr;
     int ridx_base = (pg * RW + 1) * WR_PW + ln + 1;                       // patch pixel of (this wave's first row, column ln), tap (0, 0)
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");          // the first patch (and the weights) have landed
@@ -1931,6 +1933,14 @@ __global__ __launch_bounds__(NW * 64, 2) void igemm2w_kernel(const IgemmArgs p, 
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- epilogue: lane = pixel column ln of rows pg * RW + rb, channels cg * 32 + 8 g + 4 lh + e
+        if constexpr (STATS) {
+            if (want_stats) {
+#pragma unroll
+                for (int rb = 0; rb < RW; ++rb)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) { s1[e] += acc[rb][e]; s2[e] = fmaf(acc[rb][e], acc[rb][e], s2[e]); }
+            }
+        }
 #pragma unroll
         for (int rb = 0; rb < RW; ++rb) {
             const int px = (pg * RW + rb) * 32 + ln;
@@ -1952,14 +1962,6 @@ __global__ __launch_bounds__(NW * 64, 2) void igemm2w_kernel(const IgemmArgs p, 
                 const int idx = t + NT * j;
                 const int px = idx / NCH, ch = idx % NCH;                 // (ch = t % NCH for every j)
                 const uint4 v = *(const uint4*)(stage + px * ORB + ((ch ^ (px & (NCH - 1))) << 4));
-                if constexpr (STATS) {
-                    if (want_stats) {
-                        float f[8];
-                        unpack16<T>(v, f);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) { s1[e] += f[e]; s2[e] = fmaf(f[e], f[e], s2[e]); }
-                    }
-                }
                 const unsigned m = (unsigned)((n * p.Ho + h0 + (px >> 5)) * p.Wo + w0 + (px & 31));
                 const unsigned off = ch * 8 < p.Cst ? (m * (unsigned)p.ldc + (unsigned)(ch * 8)) * 2u : 0xFFFFFFFFu;
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1974,24 +1976,25 @@ __global__ __launch_bounds__(NW * 64, 2) void igemm2w_kernel(const IgemmArgs p, 
         return;
     }
     if (want_stats) {
-        // a thread's chunk ch = t % NCH holds channels ch * 8 .. + 7: lanes with equal (lane % NCH), then the CTA's waves through LDS
+        // the 32 pixel columns of a half-wave hold the same 16 channels: sum over ln, then the CTA's pixel groups through LDS
 #pragma unroll
-        for (int e = 0; e < (STATS ? 8 : 1); ++e)
+        for (int e = 0; e < (STATS ? 16 : 1); ++e)
 #pragma unroll
-            for (int o = NCH; o < 64; o <<= 1) { s1[e] += __shfl_xor(s1[e], o, 64); s2[e] += __shfl_xor(s2[e], o, 64); }
+            for (int o = 1; o < 32; o <<= 1) { s1[e] += __shfl_xor(s1[e], o, 64); s2[e] += __shfl_xor(s2[e], o, 64); }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // trailing DMAs landed: the patch area is free
-        if (lane < NCH) {
+        if (ln == 0) {
 #pragma unroll
-            for (int e = 0; e < (STATS ? 8 : 1); ++e) {
-                sred[(wave * CO + lane * 8 + e) * 2] = s1[e];
-                sred[(wave * CO + lane * 8 + e) * 2 + 1] = s2[e];
+            for (int e = 0; e < (STATS ? 16 : 1); ++e) {
+                const int c = cg * 32 + (e >> 2) * 8 + lh * 4 + (e & 3);
+                sred[(pg * CO + c) * 2] = s1[e];
+                sred[(pg * CO + c) * 2 + 1] = s2[e];
             }
         }
         __syncthreads();
         if (t < CO && t < p.Cout) {
             float a = 0.f, b2 = 0.f;
 #pragma unroll
-            for (int w = 0; w < NW; ++w) { a += sred[(w * CO + t) * 2]; b2 += sred[(w * CO + t) * 2 + 1]; }
+            for (int w = 0; w < PG; ++w) { a += sred[(w * CO + t) * 2]; b2 += sred[(w * CO + t) * 2 + 1]; }
             float* dst = p.stats + (size_t)(blockIdx.x & (YDL_BN_REPLICAS - 1)) * 2 * p.stats_ld;
             atomicAdd(dst + t, a);
             atomicAdd(dst + p.stats_ld + t, b2);
