@@ -447,6 +447,37 @@ int ydl_letterbox_image(const void* src, int h, int w, void* tmp, float* dst, in
 int ydl_letterbox_mask(const void* src, int h, int w, int64_t* dst, int S, int new_w, int new_h, int pad_left,
                        int pad_top, const int* xtab, const int* ytab, int clip_max, void* stream);
 
+/* ---- the dataset's random augmentations on the GPU (seg_diceloss_yolov5.py:75-185): uint8 in, uint8 out, same size -------------
+ * Images are [h][w][3] RGB, label maps [h][w]; src and dst are distinct device buffers of h*w*channels bytes; sides below 32768.
+ * Every op is byte for byte what Pillow 12 computes; the values Pillow derives once per call on the host (rotation matrix, box
+ * weights, resampling tables) are arguments, built the same way in yolo_dual_amd/data.py.  Ops that leave the label map alone
+ * (brightness, contrast, blur) have no label-map entry. */
+/* ImageOps.mirror (horizontal != 0) / ImageOps.flip (horizontal == 0); channels 3 or 1 */
+int ydl_aug_flip(const void* src, void* dst, int h, int w, int channels, int horizontal, void* stream);
+/* Image.rotate(angle, BILINEAR): a0..a5 = Image.rotate's inverse affine matrix with the translation folded in (double); source
+ * position a0*(x+0.5) + a1*(y+0.5) + a2, bilinear in double without FMA contraction, truncated; 0 outside the source */
+int ydl_aug_rotate_image(const void* src, void* dst, int h, int w, double a0, double a1, double a2, double a3, double a4, double a5,
+                         void* stream);
+/* Image.rotate(angle, NEAREST): the same matrix in 16.16 fixed point, a_k = floor(v*65536 + 0.5) with a2 / a5 taken of
+ * a2 + a0/2 + a1/2 (a5 + a3/2 + a4/2); source index (a2 + a1*y + a0*x) >> 16; 0 outside */
+int ydl_aug_rotate_mask(const void* src, void* dst, int h, int w, int64_t a0, int64_t a1, int64_t a2, int64_t a3, int64_t a4,
+                        int64_t a5, void* stream);
+/* ImageEnhance.Brightness(img).enhance(factor): float(factor * px), clamped to [0, 255], truncated */
+int ydl_aug_brightness(const void* src, void* dst, int h, int w, float factor, void* stream);
+/* ImageEnhance.Contrast(img).enhance(factor): d = int(mean(convert("L")) + 0.5), then d + factor*(px - d) in single precision.
+ * sum_ws: 16 bytes of device memory, 8-byte aligned (cleared, then the exact integer luminance sum and d, formed on the device) */
+int ydl_aug_contrast(const void* src, void* dst, int h, int w, float factor, void* sum_ws, void* stream);
+/* one box pass of ImageFilter.GaussianBlur (BoxBlur.c) along x (vertical == 0) or y: radius = int(fr), ww = uint32(2^24 / (2 fr + 1))
+ * with the division in float, fw = (2^24 - (2 radius + 1) ww) / 2; a Gaussian blur is three x passes, then three y passes */
+int ydl_aug_box_blur(const void* src, void* dst, int h, int w, int vertical, int radius, int ww, int fw, void* stream);
+/* img.crop((x1, y1, x1+cw, y1+ch)).resize((w, h), BILINEAR): ydl_letterbox_image's resampler on the box, tables for cw -> w and
+ * ch -> h (NULL for a side that does not change); tmp: uint8 [ch][w][3] scratch, distinct from src and dst (may be NULL when cw == w) */
+int ydl_aug_crop_image(const void* src, int h, int w, int x1, int y1, int cw, int ch, void* tmp, void* dst, const int* xbounds,
+                       const int* xcoef, int xksize, const int* ybounds, const int* ycoef, int yksize, void* stream);
+/* mask.crop(...).resize((w, h), NEAREST): xtab int[w] / ytab int[h] index the box (ydl_letterbox_mask's tables for cw -> w, ch -> h) */
+int ydl_aug_crop_mask(const void* src, int h, int w, int x1, int y1, int cw, int ch, void* dst, const int* xtab, const int* ytab,
+                      void* stream);
+
 /* ---- zero fills (the taped region issues no ATen kernel: buffers that need defined contents are cleared through these) ----
  * ydl_fill_zero: `bytes` bytes at dst (hipMemsetAsync);  ydl_zero2d: dst[p][0:C] = 0 for npix rows of pixel stride ldd */
 int ydl_fill_zero(void* dst, int64_t bytes, void* stream);

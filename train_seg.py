@@ -3,8 +3,9 @@
 
 Mirrors the argument list and the loop of unet-lite/yolo5-seg/seg_diceloss_yolov5.py (:1235-1287 CLI, :940-952 intersect-load of
 ``--weights``, :966-980 accumulate / weight-decay scaling / LambdaLR, :1084-1103 hot loop, :1204-1212 checkpoint dict, :1229
-strip_optimizer).  What the reference does around the hot path — JSON datasets, augmentation, TensorBoard, early stopping — is outside this
-repository's scope: batches are synthetic "blobby" masks generated on the device, validation is the
+strip_optimizer).  What the reference does around the hot path — JSON datasets, TensorBoard, early stopping — is outside this
+repository's scope: batches are synthetic "blobby" masks generated on the device (``--raw-size``: as uint8
+samples that go through the GPU letterbox; ``--augment``: through the dataset's random augmentations on the GPU first), validation is the
 confusion-matrix mIoU of val_diceloss.py:37-75 on held-out synthetic batches.
 
 Multi-GPU: where the reference wraps the model in nn.DataParallel (:988-992; its SyncBN branch is dead code), this entry runs one
@@ -69,6 +70,8 @@ def parse_opt(argv=None):
     p.add_argument("--weight-decay", type=float, default=0.0005)
     p.add_argument("--raw-size", type=str, default="", help="WxH: synthetic samples are generated as uint8 arrays of this size and go "
                    "through the GPU letterbox (yolo_dual_amd.data.LetterboxGPU = the dataset's _resize_and_pad + /255)")
+    p.add_argument("--augment", action="store_true", help="with --raw-size: draw the dataset's random augmentations per sample from the run's seed "
+                   "and apply them on the GPU in front of the letterbox (yolo_dual_amd.data.AugmentGPU = _apply_augmentations)")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when WORLD_SIZE > 1 (nccl = RCCL; gloo for rehearsals)")
     p.add_argument("--dp-algo", default="allreduce", choices=["allreduce", "rs_ag"])
     p.add_argument("--dp-serial-phase2", action="store_true", help="rs_ag: all-gathers at the end of backward, not overlapped with it")
@@ -76,7 +79,10 @@ def parse_opt(argv=None):
     p.add_argument("--one-gpu", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --dist-backend gloo)")
     p.add_argument("--emulate-world", type=int, default=0, help="debugging aid (single process): play N data-parallel ranks in turn — rank "
                    "r's batches, gradients summed over the ranks and averaged in the step; parameters then equal an N-rank run's to rounding")
-    return p.parse_args(argv)
+    opt = p.parse_args(argv)
+    if opt.augment and not opt.raw_size:
+        p.error("--augment needs --raw-size: the augmentations work on the uint8 samples in front of the letterbox")
+    return opt
 
 
 def class_weights(spec: str, nc: int):
@@ -94,9 +100,10 @@ def class_weights(spec: str, nc: int):
     return torch.tensor(vals, dtype=torch.float32)
 
 
-def blobby_batch(gen, n: int, size: int, nc: int, device, palette, letterbox=None, raw=None):
+def blobby_batch(gen, n: int, size: int, nc: int, device, palette, letterbox=None, raw=None, augment=None, rng=None):
     """8x8 random class grid nearest-upsampled to size x size; the image is a class colour plus noise.
-    With ``letterbox`` the samples are made as uint8 HWC arrays of the raw size and prepared like the reference's dataset does."""
+    With ``letterbox`` the samples are made as uint8 HWC arrays of the raw size and prepared like the reference's dataset does;
+    with ``augment`` (an AugmentGPU) each sample first gets a plan of random augmentations drawn from ``rng``."""
     import torch
     if letterbox is not None:
         rw, rh = raw
@@ -104,6 +111,13 @@ def blobby_batch(gen, n: int, size: int, nc: int, device, palette, letterbox=Non
         tgt = grid.repeat_interleave((rh + 7) // 8, 1).repeat_interleave((rw + 7) // 8, 2)[:, :rh, :rw]
         img = palette[tgt] * 0.8 + 0.2 * torch.rand(n, rh, rw, 3, device=device, generator=gen)
         u8 = (img * 255).to(torch.uint8)
+        if augment is not None:
+            m8 = tgt.to(torch.uint8)
+            out_i = torch.empty((n, 3, size, size), dtype=torch.float32, device=device)
+            out_m = torch.empty((n, size, size), dtype=torch.int64, device=device)
+            for i in range(n):
+                letterbox(*augment(u8[i], m8[i], augment.plan(rw, rh, rng)), out_i[i], out_m[i])
+            return out_i, out_m
         return letterbox.batch([u8[i] for i in range(n)], [tgt[i].to(torch.uint8) for i in range(n)])
     grid = torch.randint(0, nc - 1, (n, 8, 8), device=device, generator=gen)
     rep = (size + 7) // 8
@@ -207,6 +221,11 @@ def train(opt) -> float:
     if opt.raw_size:
         raw = tuple(int(v) for v in opt.raw_size.lower().split("x"))
         lb = ydl.LetterboxGPU(opt.imgsz, num_classes=nc, device=device)
+    aug, aug_rngs = None, None
+    if opt.augment:                                                     # training batches only, like the reference's augment=True split
+        import random
+        aug = ydl.AugmentGPU(device=device)
+        aug_rngs = [random.Random(2000 + opt.seed + 7919 * r) for r in (range(emu) if emu else [rank])]
     val_batches = [blobby_batch(val_gen, bs, opt.imgsz, nc, device, palette, lb, raw) for _ in range(2)]
 
     t0 = time.time()
@@ -221,8 +240,8 @@ def train(opt) -> float:
                 dp.reducer.enabled = stepping
                 if stepping:
                     dp.begin()
-            for g_r in (emu_gens if emu else [gen]):                                    # (emulation: the ranks' micro-batches in turn)
-                imgs, targets = blobby_batch(g_r, bs, opt.imgsz, nc, device, palette, lb, raw)
+            for r_i, g_r in enumerate(emu_gens if emu else [gen]):                      # (emulation: the ranks' micro-batches in turn)
+                imgs, targets = blobby_batch(g_r, bs, opt.imgsz, nc, device, palette, lb, raw, aug, aug_rngs[r_i] if aug else None)
                 pred = model(imgs)                                                      # :1084-1092
                 loss, items_r = criterion(pred, targets)
                 loss.backward()

@@ -33,7 +33,7 @@ class BnRed(C.Structure):
                 ("invstd", C.c_void_p * 2), ("sums", C.c_void_p * 2)]
 
 
-_vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
+_vp, _i, _f, _i64, _d = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_double
 _G = C.POINTER(ConvGeom)
 _R = C.POINTER(BnRed)
 
@@ -129,6 +129,14 @@ SIGNATURES = {
     "ydl_cast_to_f32": (_i, [_i, _vp, _vp, _i64, _i, _vp]),
     "ydl_letterbox_image": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "ydl_letterbox_mask": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "ydl_aug_flip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "ydl_aug_rotate_image": (_i, [_vp, _vp, _i, _i, _d, _d, _d, _d, _d, _d, _vp]),
+    "ydl_aug_rotate_mask": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "ydl_aug_brightness": (_i, [_vp, _vp, _i, _i, _f, _vp]),
+    "ydl_aug_contrast": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
+    "ydl_aug_box_blur": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ydl_aug_crop_image": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "ydl_aug_crop_mask": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ydl_fill_zero": (_i, [_vp, _i64, _vp]),
     "ydl_zero2d": (_i, [_i, _vp, _i, _i64, _i, _vp]),
     "ydl_replay_create": (_vp, []),

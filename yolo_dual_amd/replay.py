@@ -94,7 +94,7 @@ class Recorder:
                 vals.append(ctypes.addressof(obj))
             elif t is L._vp or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
                 vals.append(self._ptr(a))
-            elif t is L._f:
+            elif t is L._f or t is L._d:
                 vals.append(struct.unpack("<q", struct.pack("<d", float(getattr(a, "value", a))))[0])
             else:
                 vals.append(int(getattr(a, "value", a)))
