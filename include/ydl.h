@@ -399,6 +399,36 @@ int ydl_deform_bwd(int dtype, const void* x, int ldx, const void* offset, int ld
                    const void* dcol, int ldc, float* grad_input, float* grad_offset, float* grad_mask, int N, int H, int W, int C,
                    int Ho, int Wo, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int G, void* stream);
 
+/* ---- local (windowed) self-attention: AttentionConv / AttentionStem (models/common.py:1509-1627) --------------------------------
+ * NHWC rows of ld* elements in the compute dtype, f32 arithmetic.  q, k: [pix][C]; v: m value tensors, V^mm at v + mm * v_stride
+ * elements (m = 1 for AttentionConv).  Per sample, channel c and pixel (h, w), over the ks*ks taps t = i*ks + j that read position
+ * (h + i - ks/2, w + j - ks/2) (K and V count as 0 outside the image, the tap stays in the softmax; stride 1, 'same' padding):
+ *     logit_t = q[c] * (K_t[c] + r[c][t]),  P = softmax_t(logit),  out[c] = sum_t P_t * U_t[c],  U_t = sum_mm emb[mm][t] * V^mm_t[c]
+ * rel_h, rel_w: f32 [C/2][ks] each, r[c][(i,j)] = rel_h[c][i] for c < C/2 and rel_w[c - C/2][j] otherwise; both NULL: r = 0.
+ * emb: f32 [m][ks*ks] (ydl_attn_stem_table_fwd), NULL: weights 1 (m must be 1).  ks in {1,3,5,7}, m <= 8, m*ks*ks <= 196.
+ * lse: f32 [pix][round_up(C,8)], max + log(sum) of the softmax per (pixel, channel), kept for the backward (may be NULL in
+ * inference).  Rows that are not 16-byte aligned, and a last channel group of fewer than 8, move element by element: nothing
+ * outside [0, C) of a row is read or written. */
+int ydl_local_attn_fwd(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int64_t v_stride, int m,
+                       const float* rel_h, const float* rel_w, const float* emb, void* out, int ldo, float* lse,
+                       int N, int H, int W, int C, int ks, void* stream);
+/* Backward in gather form, no atomics, bitwise reproducible.  dq, dk, dv (rows of ldd elements; dV^mm at dv + mm * dv_stride) are written, or added into
+ * with accumulate != 0.  d_rel_h / d_rel_w (f32 [C/2][ks], both or neither) and the parameter sums they need are ADDED into (zero
+ * them first, or keep the running sum); demb f32 [m][ks*ks] is overwritten with dE (feed it to ydl_attn_stem_table_bwd); either
+ * may be NULL.  Both go through per-block partials in ws (ydl_local_attn_bwd_ws_bytes, needed when either is asked for), merged in
+ * block order. */
+int64_t ydl_local_attn_bwd_ws_bytes(int C, int ks, int m);
+int ydl_local_attn_bwd(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int64_t v_stride, int m,
+                       const float* rel_h, const float* rel_w, const float* emb, const void* out, int ldo, const float* lse,
+                       const void* dout, int lddo, void* dq, void* dk, void* dv, int ldd, int64_t dv_stride, int accumulate, float* d_rel_h, float* d_rel_w, float* demb, float* ws,
+                       int N, int H, int W, int C, int ks, void* stream);
+/* AttentionStem's mixing table (models/common.py:1600-1603): emb[mm][i*ks + j] = softmax over mm of (emb_mix @ emb_a)[mm][i] +
+ * (emb_mix @ emb_b)[mm][j]; emb_mix f32 [m][Cg], emb_a / emb_b f32 [Cg][ks].  The backward ADDS the three parameter gradients. */
+int ydl_attn_stem_table_fwd(const float* emb_mix, const float* emb_a, const float* emb_b, float* emb, int m, int Cg, int ks,
+                            void* stream);
+int ydl_attn_stem_table_bwd(const float* emb_mix, const float* emb_a, const float* emb_b, const float* emb, const float* demb,
+                            float* d_emb_mix, float* d_emb_a, float* d_emb_b, int m, int Cg, int ks, void* stream);
+
 /* ---- pieces of the DCNv3 module around the sampling op (models/ops_dcnv3/build/.../modules/dcnv3.py:50-136) ------------
  * depth-wise k x k convolution, stride 1, 'same' padding (the `dw_conv = Conv(c, c, k, g=c)` branch, :89);
  * w is the f32 master weight [C][k*k] (= nn.Conv2d(C, C, k, groups=C).weight, shape [C,1,k,k]); k in {1,3,5,7}. */

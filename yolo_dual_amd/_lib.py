@@ -113,6 +113,12 @@ SIGNATURES = {
                            _i, _i, _i, _i, _i, _vp]),
     "ydl_deform_gather": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i] + [_i] * 15 + [_vp]),
     "ydl_deform_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp] + [_i] * 15 + [_vp]),
+    "ydl_local_attn_fwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ydl_local_attn_bwd_ws_bytes": (_i64, [_i, _i, _i]),
+    "ydl_local_attn_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i,
+                                _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ydl_attn_stem_table_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ydl_attn_stem_table_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ydl_dwconv_fwd": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_dwconv_dgrad": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_dwconv_wgrad_ws_bytes": (_i64, [_i, _i]),

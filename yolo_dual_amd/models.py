@@ -24,7 +24,7 @@ import torch.nn as nn
 import yaml
 
 from . import _lib as L
-from .modules import (GAM, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C2f_DCN, C3, C3_DCN, C3_DCNCommon, C3_DCNV3,
+from .modules import (GAM, AttentionConv, AttentionStem, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C2f_DCN, C3, C3_DCN, C3_DCNCommon, C3_DCNV3,
                       C3Common, C3k2, Concat,
                       Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region)
 from .tape import Tape, Var
@@ -524,12 +524,14 @@ def make_divisible(x, divisor):
 
 
 _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": SPPF, "Concat": Concat,
-                "nn.Upsample": Upsample, "Upsample": Upsample, "C3_DCNV3": C3_DCNV3, "Bottleneck_DCNV3": Bottleneck_DCNV3}
+                "nn.Upsample": Upsample, "Upsample": Upsample, "C3_DCNV3": C3_DCNV3, "Bottleneck_DCNV3": Bottleneck_DCNV3,
+                "AttentionConv": AttentionConv, "AttentionStem": AttentionStem}
 
 
 def parse_model(d: dict, ch: List[int], deformable: bool = False):
     """models/yolo.py:299-382 for the block set of this path: resolves module names, applies depth/width gains
-    (``n = max(round(n*gd), 1)``, ``c2 = make_divisible(c2*gw, 8)``), inserts ``n`` for C3, and tags every layer
+    (``n = max(round(n*gd), 1)``, ``c2 = make_divisible(c2*gw, 8)``), inserts ``n`` for C3 (AttentionConv / AttentionStem get none:
+    n > 1 is a Sequential of identical constructions, models/yolo.py:318-329,369), and tags every layer
     with ``.i .f .type .np``.  Returns (nn.Sequential, sorted save-list).  ``deformable``: resolve ``C3_DCN`` to models/common.py's
     DCNv2 block (C3_DCNCommon, n inserted like C3: models/yolo.py:321,327)."""
     gd, gw = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0)
@@ -542,7 +544,7 @@ def parse_model(d: dict, ch: List[int], deformable: bool = False):
         cls = table[m]
         args = [None if a == "None" else a for a in args]
         n = n_ = max(round(n * gd), 1) if n > 1 else n
-        if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3, C3_DCNCommon):
+        if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3, C3_DCNCommon, AttentionConv, AttentionStem):
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)

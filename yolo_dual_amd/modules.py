@@ -26,7 +26,7 @@ from .tape import Tape, Var, round_up, _p, _stream, zero_
 __all__ = ["autopad", "Conv", "C3", "C3Common", "Bottleneck", "C2f", "C3k2", "GAM", "SPPF", "Concat", "Upsample",
            "BasicBlock", "BottleneckBlock", "SegmentHead", "run_region", "Linear", "DCNv3", "DCNV3_YoLo", "Bottleneck_DCNV3",
            "C3_DCNV3", "DeformConv2d", "C3_DCN", "C2f_DCN", "DCNv2",
-           "Bottleneck_DCN", "C3_DCNCommon"]
+           "Bottleneck_DCN", "C3_DCNCommon", "AttentionConv", "AttentionStem"]
 
 
 def autopad(k, p=None, d=1):
@@ -1365,3 +1365,147 @@ class C3_DCNV3(YdlModule):
 
     def _fwd(self, tape: Tape, x: Var) -> Var:
         return _csp_forward(self, tape, x, False)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# stand-alone local self-attention layers (models/common.py:1509-1627)
+# ----------------------------------------------------------------------------------------------------------
+class _Proj1x1(_BiasConv2d):
+    """bias-free ``nn.Conv2d(c1, c2, kernel_size=1)``: one Q / K / V projection of a self-attention layer (weight [c2, c1, 1, 1], the
+    layer's own ``reset_parameters`` initialisation is kept by the yaml models' kaiming pass)"""
+
+    def __init__(self, c1, c2):
+        super().__init__(c1, c2, kernel_size=1, bias=False)
+
+
+class _LocalAttention(YdlModule):
+    """what AttentionConv and AttentionStem share: the argument checks and the parameter-side hooks of Tape.local_attention"""
+
+    def _init_common(self, in_channels, out_channels, kernel_size, stride, padding, groups, bias):
+        name = type(self).__name__
+        assert out_channels % groups == 0, "out_channels should be divided by groups. (example: out_channels: 40, groups: 4)"
+        if stride != 1:
+            raise NotImplementedError(f"{name}: stride {stride} is not implemented (the reference's forward only works for stride 1: "
+                                      "its .view fails otherwise)")
+        if kernel_size not in (1, 3, 5, 7):
+            raise NotImplementedError(f"{name}: kernel_size {kernel_size} is not implemented (the HIP kernels serve 1, 3, 5 and 7)")
+        if 2 * padding != kernel_size - 1:
+            raise NotImplementedError(f"{name}: padding {padding} with kernel_size {kernel_size} is not implemented (the reference's "
+                                      "forward only works for 2 * padding = kernel_size - 1)")
+        if bias:
+            raise NotImplementedError(f"{name}: bias=True is not implemented (a bias would make the padded positions non-zero)")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.stride, self.padding, self.groups = kernel_size, stride, padding, groups
+
+    @staticmethod
+    def grad_of(p: nn.Parameter) -> torch.Tensor:
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+        return p.grad
+
+    def rel(self):
+        return None
+
+    def table(self, tape: Tape):
+        return None
+
+    def table_trainable(self) -> bool:
+        return False
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        return tape.local_attention(x, self)
+
+    def extra_repr(self):
+        return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, "
+                f"padding={self.padding}, groups={self.groups}")
+
+
+class AttentionConv(_LocalAttention):
+    """models/common.py:1509-1561.  Per channel and pixel a softmax over the k x k neighbourhood of q * (k + rel), applied to v;
+    ``rel_h`` serves the first half of the channels (by window row), ``rel_w`` the second (by window column).  ``groups`` only
+    reshapes in the reference and has no arithmetic effect."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=1, groups=1, bias=False):
+        super().__init__()
+        self._init_common(in_channels, out_channels, kernel_size, stride, padding, groups, bias)
+        if out_channels % 2:
+            raise NotImplementedError(f"AttentionConv: odd out_channels {out_channels} is not implemented (rel_h and rel_w each "
+                                      "serve one half of the channels)")
+        self.rel_h = nn.Parameter(torch.randn(out_channels // 2, 1, 1, kernel_size, 1), requires_grad=True)
+        self.rel_w = nn.Parameter(torch.randn(out_channels // 2, 1, 1, 1, kernel_size), requires_grad=True)
+        self.key_conv = _Proj1x1(in_channels, out_channels)
+        self.query_conv = _Proj1x1(in_channels, out_channels)
+        self.value_conv = _Proj1x1(in_channels, out_channels)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_normal_(self.key_conv.weight, mode="fan_out", nonlinearity="relu")
+        nn.init.kaiming_normal_(self.value_conv.weight, mode="fan_out", nonlinearity="relu")
+        nn.init.kaiming_normal_(self.query_conv.weight, mode="fan_out", nonlinearity="relu")
+        nn.init.normal_(self.rel_h, 0, 1)
+        nn.init.normal_(self.rel_w, 0, 1)
+
+    def projections(self):
+        return [self.query_conv, self.key_conv, self.value_conv]
+
+    def rel(self):
+        return self.rel_h, self.rel_w
+
+
+class AttentionStem(_LocalAttention):
+    """models/common.py:1563-1627.  ``m`` value projections mixed per window position by E = softmax over m of
+    (emb_mix @ emb_a)[m, i] + (emb_mix @ emb_b)[m, j]; no positional term in the logits.  The reference's default ``padding=0``
+    is a combination its own forward cannot run; the yaml files always pass ``[c2, 3, 1, 1]``."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, groups=1, m=4, bias=False):
+        super().__init__()
+        self._init_common(in_channels, out_channels, kernel_size, stride, padding, groups, bias)
+        if not 1 <= m <= 8 or m * kernel_size * kernel_size > 196:
+            raise NotImplementedError(f"AttentionStem: m={m} with kernel_size {kernel_size} is not implemented (the HIP kernels serve "
+                                      "1 <= m <= 8 with m * kernel_size^2 <= 196)")
+        self.m = m
+        self.emb_a = nn.Parameter(torch.randn(out_channels // groups, kernel_size), requires_grad=True)
+        self.emb_b = nn.Parameter(torch.randn(out_channels // groups, kernel_size), requires_grad=True)
+        self.emb_mix = nn.Parameter(torch.randn(m, out_channels // groups), requires_grad=True)
+        self.key_conv = _Proj1x1(in_channels, out_channels)
+        self.query_conv = _Proj1x1(in_channels, out_channels)
+        self.value_conv = nn.ModuleList([_Proj1x1(in_channels, out_channels) for _ in range(m)])
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_normal_(self.key_conv.weight, mode="fan_out", nonlinearity="relu")
+        nn.init.kaiming_normal_(self.query_conv.weight, mode="fan_out", nonlinearity="relu")
+        for v in self.value_conv:
+            nn.init.kaiming_normal_(v.weight, mode="fan_out", nonlinearity="relu")
+        nn.init.normal_(self.emb_a, 0, 1)
+        nn.init.normal_(self.emb_b, 0, 1)
+        nn.init.normal_(self.emb_mix, 0, 1)
+
+    def projections(self):
+        return [self.query_conv, self.key_conv, *self.value_conv]
+
+    def _embs(self):
+        return self.emb_mix, self.emb_a, self.emb_b
+
+    def table(self, tape: Tape):
+        """the mixing table E, f32 [m][k*k], recomputed from the parameters by one single-block launch per forward pass"""
+        E = self.__dict__.get("_table")
+        if E is None or E.device != self.emb_mix.device:
+            E = self.__dict__["_table"] = torch.empty((self.m, self.kernel_size ** 2), dtype=torch.float32, device=self.emb_mix.device)
+        mix, ea, eb = (p.detach() for p in self._embs())
+        L.call("ydl_attn_stem_table_fwd", _p(mix), _p(ea), _p(eb), _p(E), self.m, mix.shape[1], self.kernel_size, _stream())
+        return E
+
+    def table_trainable(self) -> bool:
+        return any(p.requires_grad for p in self._embs())
+
+    def table_backward(self, tape: Tape, E: torch.Tensor, dE: torch.Tensor, st) -> None:
+        mix, ea, eb = self._embs()
+        # a frozen parameter's share lands in a scratch row
+        gs = [self.grad_of(p) if p.requires_grad else zero_(torch.empty_like(p), st) for p in (mix, ea, eb)]
+        L.call("ydl_attn_stem_table_bwd", _p(mix.detach()), _p(ea.detach()), _p(eb.detach()), _p(E), _p(dE), _p(gs[0]), _p(gs[1]), _p(gs[2]),
+               self.m, mix.shape[1], self.kernel_size, st)
+        tape._keep.extend(gs)
+        for p in (mix, ea, eb):
+            if p.requires_grad:
+                config.mark_touched(p)

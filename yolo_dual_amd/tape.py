@@ -1374,6 +1374,79 @@ class Tape:
         gm.mark_step(self)
         return self.conv_bn_act(col, gm, 1, 0, act, out=out, res=res, res_mode=res_mode)
 
+    def local_attention(self, x: Var, mod) -> Var:
+        """AttentionConv / AttentionStem (models/common.py:1509-1627): the bias-free 1x1 projections Q, K, V^0..V^{m-1} of x as
+        implicit-GEMM launches into channel blocks of ONE buffer, then the windowed softmax-and-sum (ydl_local_attn_fwd).  ``mod`` is
+        a yolo_dual_amd.modules._LocalAttention: ``projections()`` = [query, key, value...] weight holders, ``rel()`` = (rel_h, rel_w)
+        or None, ``table(tape)`` = the AttentionStem mixing table E (f32 [m][k*k], ydl_attn_stem_table_fwd) or None.  Backward: the
+        gather-form kernels write dQ | dK | dV^m into one buffer of the same layout, d rel_* and the table's three gradients are
+        deterministic reductions, and every projection gets its weight gradient and adds its input gradient."""
+        x = self._flat(x)
+        projs = mod.projections()
+        C, ks, m = mod.out_channels, mod.kernel_size, len(projs) - 2
+        Cin = mod.in_channels
+        if x.C != Cin:
+            raise RuntimeError(f"{type(mod).__name__} input channel mismatch: got {x.C}, weights expect {Cin}")
+        N, H, W = x.N, x.H, x.W
+        Cp = round_up(C, 8)
+        st = _stream()
+        es = 4 if self.dt == L.YDL_F32 else 2
+        qkv = self.new(N, len(projs) * Cp, H, W, zero=(Cp != C))
+        geom = L.ConvGeom(N, H, W, Cin, H, W, C, 1, 1, 0, x.ld, qkv.ld, 0)
+        gp = ctypes.byref(geom)
+        base = qkv.t.data_ptr()
+        blk = [ctypes.c_void_p(base + i * Cp * es) for i in range(len(projs))]
+        wts = []
+        for pr, dst in zip(projs, blk):
+            w, wt = pr.compute_weights(self)
+            wts.append(wt)
+            L.call("ydl_conv_fwd", gp, self.dt, _p(x.t), _p(w), dst, None, 0, st)
+        rel = mod.rel()
+        emb = mod.table(self)
+        rh, rw = (_p(rel[0].detach()), _p(rel[1].detach())) if rel is not None else (None, None)
+        out = self.new(N, C, H, W)
+        lse = torch.empty((x.npix, Cp), dtype=torch.float32, device=self.device) if self.record else None
+        L.call("ydl_local_attn_fwd", self.dt, blk[0], qkv.ld, blk[1], qkv.ld, blk[2], qkv.ld, Cp, m, rh, rw, _p(emb), _p(out.t), out.ld,
+               _p(lse), N, H, W, C, ks, st)
+        if self.record:
+            if x.need:
+                self._use(x)
+
+            def bw():
+                if not out.is_set():
+                    return
+                from . import config as _cfg
+                st2 = _stream()
+                dqkv = self.new(N, len(projs) * Cp, H, W, need=False, zero=(Cp != C))
+                dbase = dqkv.t.data_ptr()
+                dblk = [ctypes.c_void_p(dbase + i * Cp * es) for i in range(len(projs))]
+                drh = drw = demb = ws = None
+                want_rel = rel is not None and (rel[0].requires_grad or rel[1].requires_grad)
+                want_tab = emb is not None and mod.table_trainable()
+                if want_rel:
+                    drh, drw = mod.grad_of(rel[0]), mod.grad_of(rel[1])
+                if want_tab:
+                    demb = torch.empty_like(emb)
+                if want_rel or want_tab:
+                    ws = torch.empty(L.lib().ydl_local_attn_bwd_ws_bytes(C, ks, m) // 4, dtype=torch.float32, device=self.device)
+                L.call("ydl_local_attn_bwd", self.dt, blk[0], qkv.ld, blk[1], qkv.ld, blk[2], qkv.ld, Cp, m, rh, rw, _p(emb),
+                       _p(out.t), out.ld, _p(lse), _p(self._gbuf(out)), out.ld, dblk[0], dblk[1], dblk[2], dqkv.ld, Cp, 0,
+                       _p(drh), _p(drw), _p(demb), _p(ws), N, H, W, C, ks, st2)
+                if want_rel:
+                    _cfg.mark_touched(rel[0])
+                    _cfg.mark_touched(rel[1])
+                if want_tab:
+                    mod.table_backward(self, emb, demb, st2)
+                for i, pr in enumerate(projs):
+                    dy = Var(self, dqkv.t[:, i * Cp:i * Cp + C], dqkv.ld, False)
+                    pr.wgrad(self, gp, x, dy, st2)
+                    if x.need:
+                        gx, acc = self.grad_target(x)
+                        L.call("ydl_conv_dgrad", gp, self.dt, dblk[i], _p(wts[i]), _p(gx), acc, st2)
+                self._keep.extend((geom, qkv, dqkv, ws, demb))
+            self.bw.append(bw)
+        return out
+
     def scale_channels(self, x: Var, gate: torch.Tensor) -> Var:
         x = self.materialize(x)
         out = self.new_like(x)
