@@ -440,6 +440,21 @@ int ydl_dwconv_dgrad(int dtype, const void* dy, int lddy, const float* w, void* 
 int64_t ydl_dwconv_wgrad_ws_bytes(int C, int k);
 int ydl_dwconv_wgrad(int dtype, const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, int N, int H, int W, int C,
                      int k, int p, void* stream);
+/* ---- strided depth-wise convolution of the Ghost blocks (models/common.py:67-70, 253-279): stride s in {1,2}, padding k/2,
+ * Ho = (H + 2*(k/2) - k)/s + 1 (Wo likewise); any C; pixel strides >= C rounded up to a 16-byte chunk and multiples of a chunk, so a
+ * tensor may be a channel slice of a wider buffer (channels >= C of y / dx are never written).  (H, W) is always the INPUT size.
+ * ydl_dwconv2_fwd: with stats_ws != NULL the same launch writes the per-block (sum, M2) rows of the STORED output in the format of
+ * ydl_bn_stats (blocks of ydl_bn_stats_block_m() output pixels, row stride round_up(C, 8), workspace of ydl_bn_stats_ws_bytes):
+ * the rows equal ydl_bn_stats(y) bit for bit.  At s = 1 the output equals ydl_dwconv_fwd and the input gradient ydl_dwconv_dgrad. */
+int ydl_dwconv2_fwd(int dtype, const void* x, int ldx, const float* w, void* y, int ldy, float* stats_ws, int N, int H, int W, int C,
+                    int k, int s, void* stream);
+/* dx[h][w] (+)= sum w[r][t] * dy[(h+p-r)/s][(w+p-t)/s] over exact quotients inside the output (gather, no atomics) */
+int ydl_dwconv2_dgrad(int dtype, const void* dy, int lddy, const float* w, void* dx, int lddx, int accumulate, int N, int H, int W,
+                      int C, int k, int s, void* stream);
+/* dw[C][k*k] += sum over output pixels; deterministic (per-block partials in ws, fixed-order merge) */
+int64_t ydl_dwconv2_wgrad_ws_bytes(int C, int k);
+int ydl_dwconv2_wgrad(int dtype, const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, int N, int H, int W, int C,
+                      int k, int s, void* stream);
 /* BN partial statistics of any NHWC tensor in the format ydl_bn_finalize consumes: nblocks = ceil(npix / block_m) rows of
  * (sum, M2) with block_m = ydl_bn_stats_block_m() */
 int ydl_bn_stats_block_m(void);

@@ -13,7 +13,8 @@ from .loss import JaccardSegmentationLoss, SegmentationLoss
 from .models import (ResNet18, ResNet18Seg, ResNet50, ResNet50Seg, ResNet50SegYaml, SegYoloModel, YOLOv5Seg, YOLOv8Seg,
                      YOLOv9Seg, parse_model)
 from .modules import (GAM, AttentionConv, AttentionStem, C2f, C3, C3k2, C3_DCNV3, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C3Common, Concat,
-                      Conv, C2f_DCN, C3_DCN, C3_DCNCommon, Bottleneck_DCN, DCNv2, DCNv3, DCNV3_YoLo, DeformConv2d, Linear, MaxPool2d, SegmentHead, SPPF, Upsample, autopad)
+                      Conv, C2f_DCN, C3_DCN, C3_DCNCommon, Bottleneck_DCN, DCNv2, DCNv3, DCNV3_YoLo, DeformConv2d, Linear, MaxPool2d, SegmentHead, SPPF, Upsample, autopad,
+                      C3Ghost, DWConv, GhostBottleneck, GhostConv)
 from .deform import deform_conv2d
 from .optim import FlatAdamEMA, FlatAdamWEMA, FlatArenaOptimizer, FlatRMSPropEMA, FlatSGDEMA, smart_optimizer
 

@@ -123,6 +123,10 @@ SIGNATURES = {
     "ydl_dwconv_dgrad": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_dwconv_wgrad_ws_bytes": (_i64, [_i, _i]),
     "ydl_dwconv_wgrad": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ydl_dwconv2_fwd": (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ydl_dwconv2_dgrad": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ydl_dwconv2_wgrad_ws_bytes": (_i64, [_i, _i]),
+    "ydl_dwconv2_wgrad": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_bn_stats_block_m": (_i, []),
     "ydl_bn_stats_ws_bytes": (_i64, [_i64, _i]),
     "ydl_bn_stats": (_i, [_i, _vp, _i, _vp, _i64, _i, _vp]),

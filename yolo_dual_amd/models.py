@@ -25,7 +25,7 @@ import yaml
 
 from . import _lib as L
 from .modules import (GAM, AttentionConv, AttentionStem, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C2f_DCN, C3, C3_DCN, C3_DCNCommon, C3_DCNV3,
-                      C3Common, C3k2, Concat,
+                      C3Common, C3Ghost, C3k2, Concat, DWConv, GhostBottleneck, GhostConv,
                       Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region)
 from .tape import Tape, Var
 
@@ -525,7 +525,8 @@ def make_divisible(x, divisor):
 
 _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": SPPF, "Concat": Concat,
                 "nn.Upsample": Upsample, "Upsample": Upsample, "C3_DCNV3": C3_DCNV3, "Bottleneck_DCNV3": Bottleneck_DCNV3,
-                "AttentionConv": AttentionConv, "AttentionStem": AttentionStem}
+                "AttentionConv": AttentionConv, "AttentionStem": AttentionStem, "DWConv": DWConv, "GhostConv": GhostConv,
+                "GhostBottleneck": GhostBottleneck, "C3Ghost": C3Ghost}
 
 
 def parse_model(d: dict, ch: List[int], deformable: bool = False):
@@ -544,12 +545,13 @@ def parse_model(d: dict, ch: List[int], deformable: bool = False):
         cls = table[m]
         args = [None if a == "None" else a for a in args]
         n = n_ = max(round(n * gd), 1) if n > 1 else n
-        if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3, C3_DCNCommon, AttentionConv, AttentionStem):
+        if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3, C3_DCNCommon, AttentionConv, AttentionStem,
+                   DWConv, GhostConv, GhostBottleneck, C3Ghost):
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)
             args = [c1, c2, *args[1:]]
-            if cls in (C3Common, C3_DCNV3, C3_DCNCommon):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
+            if cls in (C3Common, C3_DCNV3, C3_DCNCommon, C3Ghost):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
                 args.insert(2, n)
                 n = 1
         elif cls is Concat:

@@ -26,7 +26,7 @@ from .tape import Tape, Var, round_up, _p, _stream, zero_
 __all__ = ["autopad", "Conv", "C3", "C3Common", "Bottleneck", "C2f", "C3k2", "GAM", "SPPF", "Concat", "Upsample",
            "BasicBlock", "BottleneckBlock", "SegmentHead", "run_region", "Linear", "DCNv3", "DCNV3_YoLo", "Bottleneck_DCNV3",
            "C3_DCNV3", "DeformConv2d", "C3_DCN", "C2f_DCN", "DCNv2",
-           "Bottleneck_DCN", "C3_DCNCommon", "AttentionConv", "AttentionStem"]
+           "Bottleneck_DCN", "C3_DCNCommon", "AttentionConv", "AttentionStem", "DWConv", "GhostConv", "GhostBottleneck", "C3Ghost"]
 
 
 def autopad(k, p=None, d=1):
@@ -233,8 +233,8 @@ class Conv(YdlModule):
         self.depthwise = g > 1 and g == c1 == c2
         if d != 1 or (g != 1 and not self.depthwise):
             raise NotImplementedError("the HIP path implements groups=1 (implicit GEMM) and groups=c1=c2 (depth-wise), dilation=1")
-        if self.depthwise and (s != 1 or k not in (1, 3, 5, 7) or autopad(k, p) != k // 2):
-            raise NotImplementedError("depth-wise Conv: stride 1, k in {1,3,5,7}, 'same' padding (the DCNv3 dw_conv branch)")
+        if self.depthwise and (s not in (1, 2) or k not in (1, 3, 5, 7) or autopad(k, p) != k // 2):
+            raise NotImplementedError(f"depth-wise Conv: stride s in {{1,2}}, k in {{1,3,5,7}}, 'same' padding p = k // 2 (got s={s}, k={k}, p={p})")
         self.c1, self.c2, self.k, self.s = c1, c2, k, s
         self.p = autopad(k, p)
         self.conv = nn.Conv2d(c1, c2, k, s, self.p, groups=g, bias=False)
@@ -243,6 +243,9 @@ class Conv(YdlModule):
         self.act = nn.SiLU() if act is True else (act if isinstance(act, nn.Module) else nn.Identity())
         self.act_code = _act_code(self.act)
         self._wcache = {}
+        # depth-wise layers: the DCNv3 dw_conv branch keeps Tape.dwconv_bn_act (stride 1, separate statistics pass); the Ghost
+        # blocks (DWConv, GhostConv.cv2) and every stride-2 layer run Tape.dw_bn_act (statistics from the convolution launch)
+        self.dw_fused_stats = self.depthwise and s != 1
 
     # -- parameters in compute layout -------------------------------------------------------------------
     def _master_krsc(self) -> torch.Tensor:
@@ -358,6 +361,8 @@ class Conv(YdlModule):
              res_mode: int = L.RES_NONE, act_code: Optional[int] = None) -> Var:
         self.mark_step(tape)
         act = self.act_code if act_code is None else act_code
+        if self.depthwise and self.dw_fused_stats:
+            return tape.dw_bn_act(x, self, self.s, act, out=out, res=res, res_mode=res_mode)
         if self.depthwise:
             if res is not None:
                 raise NotImplementedError("depth-wise Conv with a fused residual")
@@ -701,6 +706,82 @@ class C2f(YdlModule):
         if self.add:
             return self.cv2._fwd(tape, cat, res=x, res_mode=L.RES_AFTER_ACT)
         return self.cv2._fwd(tape, cat)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# Ghost blocks (models/common.py:67-70, 199-204, 253-279)
+# ----------------------------------------------------------------------------------------------------------
+class DWConv(Conv):
+    """models/common.py:67-70: ``Conv`` with g = gcd(c1, c2).  The HIP path serves the depth-wise form g == c1 == c2."""
+
+    def __init__(self, c1, c2, k=1, s=1, d=1, act=True):
+        g = math.gcd(c1, c2)
+        if not (g == c1 == c2):
+            raise NotImplementedError(f"DWConv: c1={c1}, c2={c2} give g = gcd(c1, c2) = {g}; only the depth-wise form g == c1 == c2 is "
+                                      "implemented on the HIP path")
+        if d != 1:
+            raise NotImplementedError(f"DWConv: dilation d={d} is not implemented on the HIP path")
+        super().__init__(c1, c2, k, s, None, g, d, act)
+        self.dw_fused_stats = self.depthwise
+
+
+class GhostConv(YdlModule):
+    """models/common.py:253-263: cat(y, cv2(y)) with y = cv1(x), cv2 a 5x5 depth-wise Conv.  Both halves are written straight into
+    one buffer when the half width c_ is a whole number of 8-channel groups (the granularity of the BatchNorm kernels, 16 bytes in
+    bf16); other widths go through the concat copies."""
+
+    def __init__(self, c1, c2, k=1, s=1, g=1, act=True):
+        super().__init__()
+        if g != 1:
+            raise NotImplementedError(f"GhostConv: groups g={g} is not implemented on the HIP path (g = 1 only)")
+        c_ = c2 // 2
+        self.cv1 = Conv(c1, c_, k, s, None, g, act=act)
+        self.cv2 = Conv(c_, c_, 5, 1, None, c_, act=act)
+        self.cv2.dw_fused_stats = self.cv2.depthwise
+        self.c_ = c_
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        c_, cv1 = self.c_, self.cv1
+        if c_ % 8 == 0 and (out is None or out.aligned()):
+            Ho = (x.LH + 2 * cv1.p - cv1.k) // cv1.s + 1
+            Wo = (x.LW + 2 * cv1.p - cv1.k) // cv1.s + 1
+            cat = out if out is not None else tape.new(x.N, 2 * c_, Ho, Wo)
+            a = cv1._fwd(tape, x, out=cat.slice(0, c_))
+            self.cv2._fwd(tape, a, out=cat.slice(c_, 2 * c_))
+            return cat
+        a = cv1._fwd(tape, x)
+        cat = tape.concat([a, self.cv2._fwd(tape, a)])
+        return cat if out is None else tape.copy(cat, out)
+
+
+class GhostBottleneck(YdlModule):
+    """models/common.py:266-279: conv(x) + shortcut(x)."""
+
+    def __init__(self, c1, c2, k=3, s=1):
+        super().__init__()
+        c_ = c2 // 2
+        self.conv = nn.Sequential(GhostConv(c1, c_, 1, 1),
+                                  DWConv(c_, c_, k, s, act=False) if s == 2 else nn.Identity(),
+                                  GhostConv(c_, c2, 1, 1, act=False))
+        self.shortcut = nn.Sequential(DWConv(c1, c1, k, s, act=False), Conv(c1, c2, 1, 1, act=False)) if s == 2 else nn.Identity()
+        self.s = s
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        h = self.conv[0]._fwd(tape, x)
+        if self.s == 2:
+            h = self.conv[1]._fwd(tape, h)
+        h = self.conv[2]._fwd(tape, h)
+        if self.s == 2:                                  # the shortcut's linear 1x1 Conv adds the main branch in its BatchNorm apply
+            return self.shortcut[1]._fwd(tape, self.shortcut[0]._fwd(tape, x), out=out, res=h, res_mode=L.RES_AFTER_ACT)
+        return tape.add(h, x, out=out)
+
+
+class C3Ghost(C3Common):
+    """models/common.py:199-204: C3 whose m is n GhostBottleneck(c_, c_)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.Sequential(*(GhostBottleneck(self.c_, self.c_) for _ in range(n)))
 
 
 # ----------------------------------------------------------------------------------------------------------

@@ -946,10 +946,13 @@ class Tape:
             self.bw.append(bw)
         return out
 
-    def add(self, a: Var, b: Var) -> Var:
-        """out = a + b (element-wise, same shape); backward hands d(out) to both"""
+    def add(self, a: Var, b: Var, out: Optional[Var] = None) -> Var:
+        """out = a + b (element-wise, same shape); backward hands d(out) to both.  ``out`` may be a concat slice."""
         a, b = self._flat(a) if (a.lazy or a.virtual) else a, self._flat(b) if (b.lazy or b.virtual) else b
-        out = self.new(a.N, a.C, a.H, a.W, f32=(a.dt == L.YDL_F32))
+        if out is None:
+            out = self.new(a.N, a.C, a.H, a.W, f32=(a.dt == L.YDL_F32))
+        elif (out.N, out.C, out.H, out.W) != (a.N, a.C, a.H, a.W):
+            raise RuntimeError("add: output slice has the wrong shape")
         st = _stream()
         L.call("ydl_copy2d", a.dt, _p(a.t), a.ld, _p(out.t), out.ld, a.npix, a.C, 0, st)
         L.call("ydl_copy2d", b.dt, _p(b.t), b.ld, _p(out.t), out.ld, b.npix, b.C, 1, st)
@@ -1219,6 +1222,90 @@ class Tape:
                     gx, acc = self.grad_target(x)
                     L.call("ydl_dwconv_dgrad", self.dt, _p(dy.t), dy.ld, _p(wm), _p(gx), x.ld, acc, x.N, x.H, x.W, C, k, p, st2)
             self.bw.append(bw)
+        return out
+
+    def dw_bn_act(self, x: Var, m, s: int, act: int, out: Optional[Var] = None, res: Optional[Var] = None,
+                  res_mode: int = L.RES_NONE) -> Var:
+        """strided depth-wise Conv+BN+act of the Ghost blocks (models/common.py:67-70, 253-279): out = act(bn(dwconv(x))) [+ res],
+        stride 1 or 2.  The convolution launch writes the BatchNorm partial rows of its own output (ydl_dwconv2_fwd), so train mode
+        goes conv -> ydl_bn_finalize -> ydl_bn_act_fwd with no statistics pass over y.  ``out`` may be a concat slice."""
+        x = self._flat(x)
+        if res is not None:
+            res = self._flat(res)
+        if out is not None and not out.aligned():       # the BatchNorm kernels work on 8-channel groups: stage an odd slice
+            return self.copy(self.dw_bn_act(x, m, s, act, None, res, res_mode), out)
+        C, k = m.c1, m.k
+        if x.C != C:
+            raise RuntimeError(f"depth-wise Conv input channel mismatch: got {x.C}, weight expects {C}")
+        Ho = (x.H + 2 * (k // 2) - k) // s + 1
+        Wo = (x.W + 2 * (k // 2) - k) // s + 1
+        y = self.new(x.N, C, Ho, Wo)
+        if out is None:
+            out = self.new(x.N, C, Ho, Wo)
+        elif (out.N, out.C, out.H, out.W) != (x.N, C, Ho, Wo):
+            raise RuntimeError("dw_bn_act: output slice has the wrong shape")
+        st = _stream()
+        wm = m.master_dw()                                   # f32 [C][k*k]
+        cf = m.coeffs(self.device)
+        npix = x.N * Ho * Wo
+        cp = round_up(C, 8)
+        if self.train:
+            ws = torch.empty(L.lib().ydl_bn_stats_ws_bytes(npix, C) // 4, dtype=torch.float32, device=self.device)
+            bm = L.lib().ydl_bn_stats_block_m()
+            L.call("ydl_dwconv2_fwd", self.dt, _p(x.t), x.ld, _p(wm), _p(y.t), y.ld, _p(ws), x.N, x.H, x.W, C, k, s, st)
+            L.call("ydl_bn_finalize", _p(ws), (npix + bm - 1) // bm, bm, npix, C, _p(m.bn.weight), _p(m.bn.bias), m.bn.eps,
+                   m.bn.momentum, _p(m.bn.running_mean), _p(m.bn.running_var), _p(cf["mean"]), _p(cf["invstd"]),
+                   _p(cf["scale"]), _p(cf["shift"]), 1, st)
+        else:
+            L.call("ydl_dwconv2_fwd", self.dt, _p(x.t), x.ld, _p(wm), _p(y.t), y.ld, None, x.N, x.H, x.W, C, k, s, st)
+            L.call("ydl_bn_eval_coeffs", C, _p(m.bn.weight), _p(m.bn.bias), _p(m.bn.running_mean), _p(m.bn.running_var),
+                   m.bn.eps, _p(cf["scale"]), _p(cf["shift"]), st)
+        L.call("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
+               res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
+        if not self.record:
+            return out
+        if not self.train:
+            raise RuntimeError("backward through eval-mode BatchNorm is not supported")
+        if x.need:
+            self._use(x)
+        if res is not None and res.need and res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
+            self._use(res)
+
+        def bw():
+            if not out.is_set():
+                return
+            st2 = _stream()
+            dy = self.new(x.N, C, Ho, Wo)
+            dout = self._gbuf(out)
+            train_w, train_g, train_b = m.trainable()
+            gw, accw = m.grad_slot(self, "gamma") if train_g else (torch.empty(cp, dtype=torch.float32, device=self.device), 0)
+            gb, accb = m.grad_slot(self, "beta") if train_b else (torch.empty(cp, dtype=torch.float32, device=self.device), 0)
+            if accb != accw:
+                zero_(gw if not train_g else gb)
+                accw = 1
+            dres_t, dres_ld, rmode = None, 0, res_mode
+            if res is not None and res.need and res_mode == L.RES_AFTER_ACT and self._alias_grad(res, out, dout):
+                pass
+            elif res is not None and res.need and res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
+                dres_t, racc = self.grad_target(res)
+                dres_ld = res.ld
+                if racc:
+                    rmode = res_mode | L.RES_GRAD_ACCUMULATE
+            ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
+            L.call("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
+                   _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rmode, act,
+                   _p(dy.t), dy.ld, _p(dres_t), dres_ld, _p(gw), _p(gb), accw, _p(ws2), npix, C, cp, st2)
+            m.touch_bn()
+            if train_w:
+                gk = m.grad_dw()
+                ws3 = torch.empty(L.lib().ydl_dwconv2_wgrad_ws_bytes(C, k) // 4, dtype=torch.float32, device=self.device)
+                L.call("ydl_dwconv2_wgrad", self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws3), x.N, x.H, x.W, C, k, s, st2)
+                from . import config as _cfg
+                _cfg.mark_touched(m.conv.weight)
+            if x.need:
+                gx, acc = self.grad_target(x)
+                L.call("ydl_dwconv2_dgrad", self.dt, _p(dy.t), dy.ld, _p(wm), _p(gx), x.ld, acc, x.N, x.H, x.W, C, k, s, st2)
+        self.bw.append(bw)
         return out
 
     def group_softmax(self, x: Var, G: int, P: int) -> Var:
