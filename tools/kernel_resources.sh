@@ -20,7 +20,11 @@ if [ $check = 0 ]; then echo "$tab"; exit 0; fi
 guard='
 igemm2_kernelILi128ELi128ELi8ELi4ELi2ELb0ELi0E 4 0
 igemm2_kernelILi256ELi128ELi8ELi4ELi3ELb0ELi1E 2 0
-igemm2_kernelILi256ELi64ELi8ELi8ELi3ELb0ELi0E 4 0
+igemm2_kernelILi64ELi128ELi4ELi2ELi3ELb0ELi0E 4 0
+igemm2_kernelILi128ELi64ELi8ELi4ELi2ELb0ELi0E 7 0
+igemm2_kernelILi128ELi128ELi8ELi4ELi2ELb1ELi0E 4 0
+igemm2_kernelILi64ELi128ELi4ELi2ELi3ELb1ELi0E 4 0
+igemm2_kernelILi128ELi64ELi8ELi4ELi2ELb1ELi0E 7 0
 igemm2w_kernelILi64ELb1ELi4E 2 0
 igemm2w_kernelILi64ELb0ELi4E 2 0
 igemm2w_kernelILi128ELb1ELi4E 2 0

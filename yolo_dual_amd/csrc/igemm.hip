@@ -14,9 +14,6 @@
 #include <type_traits>
 #include <stdlib.h>
 
-#ifndef YDL_PF
-#define YDL_PF 1     // deeper register prefetch costs an occupancy step on the 128x128 tile (measured slower)
-#endif
 #define ROWB 144      // LDS row stride in bytes (128 data + 16 pad): wgrad tiles (transposed reads)
 #define GROWB 128     // igemm tiles: unpadded rows, XOR-swizzled chunks
 #define MAXTAPS 64
@@ -48,7 +45,6 @@ struct IgemmArgs {
     int cls_ntaps[4], cls_tap0[4], cls_Hg[4], cls_Wg[4], cls_M[4], cls_h0[4], cls_w0[4];
     int grid_n;                // number of output-channel tiles (the grid is 1-D: grid_m * grid_n)
     int grid_m;                // number of pixel tiles (all classes)
-    int dbg;                   // timing experiments only (YDL_RING_DBG): 1 no DMA, 2 DMA sources collapsed onto 64 KB, 3 no epilogue
     int m_fastest;             // igemm2 tile order: 0 = channel tiles of one pixel tile are neighbours (activations shared in L2),
                                //                    1 = pixel tiles of one channel tile are neighbours (weight slab stays in L2)
     signed char dh[MAXTAPS], dw[MAXTAPS];
@@ -366,7 +362,7 @@ __global__ __launch_bounds__(NW * 64) void igemm_kernel(const IgemmArgs p) {
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, p.bytesA, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, p.bytesB, 0x00020000);
 
-    constexpr int PF = YDL_PF;
+    constexpr int PF = 1;     // deeper register prefetch costs an occupancy step on the 128x128 tile (measured slower)
     uint4 ra[PF][AR], rb[PF][BR];
     __syncthreads();   // tap tables visible
 
@@ -862,15 +858,13 @@ __global__ __launch_bounds__(NW * 64, RED ? NW / 2 : 1) void igemm2_kernel(const
         nxtA = sTapA[tap];
         nxtB = sTapB[tap];
         const unsigned base = wave_lds + (unsigned)stg * STAGE;
-        if (p.dbg == 1) return;
-        const unsigned amask = p.dbg == 2 ? 0xFFFFu : 0xFFFFFFFFu;
 #pragma unroll
         for (int i = 0; i < AR; ++i) {
-            const unsigned off = (vmask[i] & tbit) ? (rowoff[i] + (unsigned)da + kb) & amask : 0xFFFFFFFFu;
+            const unsigned off = (vmask[i] & tbit) ? rowoff[i] + (unsigned)da + kb : 0xFFFFFFFFu;
             lds_dma16(rsA, base + i * RPP * GROWB, off);
         }
 #pragma unroll
-        for (int i = 0; i < BR; ++i) lds_dma16(rsB, base + BM * GROWB + i * RPP * GROWB, (browoff[i] + (unsigned)db + kbB) & (p.dbg == 2 ? 0xF000FFFFu : 0xFFFFFFFFu));
+        for (int i = 0; i < BR; ++i) lds_dma16(rsB, base + BM * GROWB + i * RPP * GROWB, browoff[i] + (unsigned)db + kbB);
     };
 
     f32x4 acc[CT][PT];
@@ -910,35 +904,7 @@ __global__ __launch_bounds__(NW * 64, RED ? NW / 2 : 1) void igemm2_kernel(const
     if constexpr (STG != 0) {
         static_assert(NW == 8, "the stagger splits the CTA into waves 0-3 and 4-7");
         auto rd_step = [&](int stg) { rdfrag(stg, 0, af0, bf0); rdfrag(stg, 1, af1, bf1); };
-        // STG == 3: TIMING EXPERIMENT ONLY (VERDICT r4 item 1 ii; YDL_RING=19, never dispatched): the same 16 fragment reads feed 16
-        // v_mfma_f32_32x32x16_bf16 instead of 32 v_mfma_f32_16x16x32_bf16 — same FLOPs and LDS bytes per K-step, half the matrix
-        // instructions (8 of 32 issue cycles each instead of 8 of 16).  The operands are NOT the right fragments for that shape (the
-        // results are garbage); it answers whether the shape is worth its own fragment addressing and epilogue.
-        typedef __attribute__((ext_vector_type(16))) float f32x16;
-        f32x16 acc32[2][2];
-        if constexpr (STG == 3) {
-            static_assert(CT == 4 && PT == 4, "64 x 64 wave tiles");
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc32[c][j][e] = 0.f;
-        }
-        auto mma32 = [&](const uint4 (&af)[CT], const uint4 (&bfr)[PT]) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc32[c][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[2 * h + c]),
-                                                                              __builtin_bit_cast(bf16x8, bfr[2 * h + j]), acc32[c][j], 0, 0, 0);
-        };
-        auto mma_step = [&]() {
-            if constexpr (STG == 3) { mma32(af0, bf0); mma32(af1, bf1); }
-            else { mma(af0, bf0); mma(af1, bf1); }
-        };
+        auto mma_step = [&]() { mma(af0, bf0); mma(af1, bf1); };
         if (wave < NW / 2) {
             int stg = 0;
             for (int kk = 0; kk < nk; ++kk) {
@@ -952,7 +918,6 @@ __global__ __launch_bounds__(NW * 64, RED ? NW / 2 : 1) void igemm2_kernel(const
                 stg = stg + 1 == S ? 0 : stg + 1;
             }
         } else if (nk > 0) {
-            if (STG == 2) __builtin_amdgcn_s_setprio(1);
             wait_vm_barrier<L * (S - 2)>();
             issue(S - 1);
             rd_step(0);
@@ -969,15 +934,6 @@ __global__ __launch_bounds__(NW * 64, RED ? NW / 2 : 1) void igemm2_kernel(const
                 stg = stg + 1 == S ? 0 : stg + 1;
             }
             mma_step();
-            if (STG == 2) __builtin_amdgcn_s_setprio(0);
-        }
-        if constexpr (STG == 3) {              // keep the 32 x 32 accumulators live through the (unchanged) epilogue
-#pragma unroll
-            for (int c = 0; c < CT; ++c)
-#pragma unroll
-                for (int j = 0; j < PT; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[c][j][e] = acc32[c >> 1][j >> 1][((c & 1) * 2 + (j & 1)) * 4 + e];
         }
     } else {
     if (nk > 0) {
@@ -1005,15 +961,6 @@ __global__ __launch_bounds__(NW * 64, RED ? NW / 2 : 1) void igemm2_kernel(const
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     wait_vm_barrier<0>();              // the trailing all-zero DMAs must land before the epilogue reuses the LDS
-    if (p.dbg == 3) {                  // timing experiment: keep the accumulators live, skip stores and statistics
-        float sink = 0.f;
-#pragma unroll
-        for (int c = 0; c < CT; ++c)
-#pragma unroll
-            for (int j = 0; j < PT; ++j) sink += acc[c][j][0] + acc[c][j][1] + acc[c][j][2] + acc[c][j][3];
-        if (sink == 123.456f) ((float*)p.C)[0] = sink;
-        return;
-    }
     igemm2_epilogue<BM, BN, NW, WP, RED>(p, acc, smem, m0, n0, mtile, c_M, c_Wg, c_Hg, c_h0, c_w0, sCoef);
 }
 
@@ -1232,11 +1179,9 @@ static int launch_igemm2l(IgemmArgs a, hipStream_t st, int fam) {
     a.grid_m = mtiles;
     YDL_CHECK(a.bytesB < 0x08000000u, "ring kernel: weight matrix of 128 MiB or more is not supported");
     {
-        static const int forced = getenv("YDL_RING_MFAST") ? atoi(getenv("YDL_RING_MFAST")) : -1;
         const double wbytes = (double)a.Cout * a.Ttot * a.Kc * 2.0;
         const double abytes = (double)a.N * a.Hi * a.Wi * a.lda * 2.0;
         a.m_fastest = (wbytes > 2.0e6 && (double)mtiles * wbytes > (double)a.grid_n * abytes) ? 1 : 0;
-        if (forced >= 0) a.m_fastest = forced;
     }
     const size_t smem = (size_t)S * (BM + BN) * GROWB + 3 * MAXTAPS * sizeof(int);
     static const std::string nm = std::string("igemm2l_kernel<") + std::to_string(BM) + "," + std::to_string(BN) + "," + std::to_string(NW) + "+" +
@@ -2006,8 +1951,7 @@ __global__ __launch_bounds__(NW * 64, 2) void igemm2w_kernel(const IgemmArgs p, 
 
 static int g_wreg = 1;          // ydl_debug_set key 17
 static bool wreg_ok(const IgemmArgs& a) {
-    static const int env = getenv("YDL_WREG") ? atoi(getenv("YDL_WREG")) : 1;
-    if (!env || !g_wreg || a.br.nseg > 0 || a.accumulate) return false;
+    if (!g_wreg || a.accumulate) return false;
     if (a.ncls > 1 || a.ntaps != 9 || a.Ttot != 9 || a.in_mul != 1 || a.out_mul != 1 || a.out_h0 != 0 || a.out_w0 != 0) return false;
     if (a.Hi != a.Ho || a.Wi != a.Wo || a.Hg != a.Ho || a.Wg != a.Wo || a.Kc != 64) return false;
     if (a.Cst != 64 && a.Cst != 128) return false;
@@ -2022,9 +1966,11 @@ static bool wreg_ok(const IgemmArgs& a) {
     }
     return true;
 }
-template <int CO, int NW>
+// two 4-wave CTAs per CU.  Measured against one 8-wave CTA, same box: 64->64 @160^2 forward 50.0 -> 46.0 us, data gradient 45.3 -> 41.4 us,
+// 64->128 data gradient 73..82 -> 71 us (patch kernels: 53.1 / 46.6 / 88..93 us); the step +0.9 %
+template <int CO>
 static int launch_igemm2w_cfg(IgemmArgs a, hipStream_t st, int fam) {
-    constexpr int R = (NW / (CO / 32)) * 2, PR = NW * 8;
+    constexpr int NW = 4, R = (NW / (CO / 32)) * 2, PR = NW * 8;
     const int nblocks = a.N * (a.Ho / R) * (a.Wo >> 5);
     constexpr int PASSES = ((R + 2) * WR_PW + PR - 1) / PR;
     const size_t smem = 2 * (size_t)PASSES * PR * GROWB + (size_t)R * 32 * CO * 2;
@@ -2033,20 +1979,15 @@ static int launch_igemm2w_cfg(IgemmArgs a, hipStream_t st, int fam) {
     const unsigned long long bc = ((unsigned long long)(a.N * a.Ho * a.Wo - 1) * a.ldc + a.Cst) * 2ull;
     YDL_CHECK(bc < 0xFFFFFFF0ull, "output larger than 4 GiB");
     a.bytesC = (unsigned)bc;
-    static const std::string nm = std::string("igemm2w_kernel<") + std::to_string(CO) + (NW == 8 ? ">" : ",nw4>");
-    ydl_note_kernel(fam, nm.c_str());
-    const int ctas = std::min(ydl_device_cus() * (NW == 8 ? 1 : 2), nblocks);
+    ydl_note_kernel(fam, CO == 128 ? "igemm2w_kernel<128,nw4>" : "igemm2w_kernel<64,nw4>");
+    const int ctas = std::min(ydl_device_cus() * 2, nblocks);
     if (a.stats != nullptr) igemm2w_kernel<CO, true, NW><<<ctas, NW * 64, smem, st>>>(a, nblocks);
     else igemm2w_kernel<CO, false, NW><<<ctas, NW * 64, smem, st>>>(a, nblocks);
     YDL_LAUNCH_CHECK();
     return 0;
 }
 static int launch_igemm2w(const IgemmArgs& a, hipStream_t st, int fam) {
-    // two 4-wave CTAs per CU by default (YDL_WREG_NW=8: one 8-wave CTA).  Measured, same box: 64->64 @160^2 forward 50.0 -> 46.0 us,
-    // data gradient 45.3 -> 41.4 us, 64->128 data gradient 73..82 -> 71 us (patch kernels: 53.1 / 46.6 / 88..93 us); the step +0.9 %
-    static const int nw = getenv("YDL_WREG_NW") ? atoi(getenv("YDL_WREG_NW")) : 4;
-    if (nw == 4) return a.Cst == 128 ? launch_igemm2w_cfg<128, 4>(a, st, fam) : launch_igemm2w_cfg<64, 4>(a, st, fam);
-    return a.Cst == 128 ? launch_igemm2w_cfg<128, 8>(a, st, fam) : launch_igemm2w_cfg<64, 8>(a, st, fam);
+    return a.Cst == 128 ? launch_igemm2w_cfg<128>(a, st, fam) : launch_igemm2w_cfg<64>(a, st, fam);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2255,9 +2196,6 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void igemm2s_kernel(const IgemmArg
 //     cancellation at that size), converted to (mean, M2) and Chan-merged over the 16 pixel lanes with the transposing
 //     butterfly, then over the CTA's pixel waves through LDS => the same [grid_m][2][C] (sum, M2) contract.
 // ------------------------------------------------------------------------------------------------------
-#ifndef PW_LOAD_AUX
-#define PW_LOAD_AUX 0      // cache-policy bits of the activation loads (bit 1 = nt); measured: see DESIGN.md
-#endif
 struct PwArgs {
     const void* X; const void* W; void* Y; float* stats;
     int M, lda, ldc, Cout, WN, accumulate, block_m, stats_ld, stats_atomic;
@@ -2270,14 +2208,8 @@ __global__ __launch_bounds__(NW * 64) void pw_kernel(const PwArgs p) {
     constexpr int ES = sizeof(T);
     constexpr int J = RB / 64;                  // fragment groups per K row (each = 4 lane-group chunks of 16 B)
     constexpr int CPR = RB / 16;                // chunks per row
-#ifndef PW_NB_SHORT
-#define PW_NB_SHORT 4
-#endif
-#ifndef PW_NB_TS8
-#define PW_NB_TS8 2
-#endif
     // pixel tiles in flight per wave (register budget; 512-byte rows x 128-channel waves with statistics AND transposed stores: one less)
-    constexpr int NB = (J >= 8) ? ((CT == 8 && ((STATS && (TS || ACC)) || (TS && ACC))) ? PW_NB_TS8 : 3) : PW_NB_SHORT;
+    constexpr int NB = (J >= 8) ? ((CT == 8 && ((STATS && (TS || ACC)) || (TS && ACC))) ? 2 : 3) : 4;
     constexpr int NV = CT * 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* sW = smem;                                      // [Cout][RB], chunk q of row r at slot q ^ sw(r)
@@ -2303,7 +2235,7 @@ __global__ __launch_bounds__(NW * 64) void pw_kernel(const PwArgs p) {
         const unsigned base = (unsigned)m * rowbytes + (unsigned)(lgrp << 4);
 #pragma unroll
         for (int j = 0; j < J; ++j) {
-            u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsX, ok ? base + j * 64 : 0xFFFFFFFFu, 0, PW_LOAD_AUX);
+            u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsX, ok ? base + j * 64 : 0xFFFFFFFFu, 0, 0);      // (cache-policy bits 0; nt measured: see DESIGN.md)
             b[j] = make_uint4(v.x, v.y, v.z, v.w);
         }
     };
@@ -2614,8 +2546,7 @@ struct StemPlan { bool ok; int block_m, grid_m; };
 static int g_stem_enabled = 1;
 static StemPlan stem_plan(int M, int Wo) {
     StemPlan pl{};
-    static const int env = getenv("YDL_STEM") ? atoi(getenv("YDL_STEM")) : 1;
-    pl.ok = g_stem_enabled && env && Wo % 16 == 0 && M >= 4096;
+    pl.ok = g_stem_enabled && Wo % 16 == 0 && M >= 4096;
     if (!pl.ok) return pl;
     const int slots = ydl_device_cus() * 3;
     pl.block_m = round_up((M + slots - 1) / slots, 64);
@@ -2747,7 +2678,7 @@ static bool args_stem(const IgemmArgs& a) {
 struct PwPlan { bool ok; int RB, CT, WN, NW, block_m, grid_m; size_t smem, tstage; };
 static int g_pw_enabled = 1;
 static int g_pw_acc_ts = -1;     // ydl_debug_set key 14: accumulating point-wise launches: 1 transposed stores (statistics in the row layout),
-                                 // 2 transposed stores only without statistics, 0 direct stores; -1 = YDL_PW_ACC_TS / default 1
+                                 // 2 transposed stores only without statistics, 0 direct stores; -1 = the default, 1
 static int g_dgrad_merge = 1;
 // eligibility + launch geometry; a pure function of its arguments (the stats-workspace queries call it too)
 static PwPlan pw_plan(int M, int Kc, int Cout, int Cst, int es, bool pointwise) {
@@ -2763,16 +2694,13 @@ static PwPlan pw_plan(int M, int Kc, int Cout, int Cst, int es, bool pointwise) 
     // bf16: waves of 64 output channels instead of 128 wherever the weight matrix is at most 64 KB (tools/conv_bench.py: 128->128
     // @160^2 forward 59.4 -> 53.1 us, dgrad 53.1 -> 47.7; 128->256 @80^2 38.5 -> 27.6; 256->128 @80^2 29.6 -> 26.7; 64->128 @160^2
     // 40.3 -> 39.3) — but not 256->256 on 512-byte rows (42 -> 58 us: four waves would each fetch the whole activation tile).
-    // YDL_PW_CT4=0: 128-channel waves everywhere, 2: 64-channel waves for every 128-channel layer incl. f32
-    static const int ct4 = getenv("YDL_PW_CT4") ? atoi(getenv("YDL_PW_CT4")) : 1;
-    const bool split = (ct4 == 1 && es == 2 && (Cout == 128 || (Cout == 256 && RB <= 256))) || (ct4 == 2 && Cout == 128);
+    const bool split = es == 2 && (Cout == 128 || (Cout == 256 && RB <= 256));
     pl.CT = (Cout >= 128 && !split) ? 8 : 4;
     pl.WN = Cout / (pl.CT * 16);
     // 512-byte rows x 128+ channels need ~230 VGPRs: as 4-wave CTAs that is one wave per SIMD; one 8-wave CTA per CU
     // gives two
     pl.NW = (RB == 512 && pl.CT == 8) ? 8 : 4;
-    static const int slots4 = getenv("YDL_PW_SLOTS") ? atoi(getenv("YDL_PW_SLOTS")) : 2;      // CTAs per CU the 4-wave forms are sized for
-    const int slots = ydl_device_cus() * (pl.NW == 4 ? slots4 : 1);
+    const int slots = ydl_device_cus() * (pl.NW == 4 ? 2 : 1);      // CTAs per CU: the 4-wave forms are sized for two
     int bm = round_up((M + slots - 1) / slots, 16);
     pl.block_m = bm;
     pl.grid_m = (M + bm - 1) / bm;
@@ -2786,25 +2714,18 @@ static PwPlan pw_plan(int M, int Kc, int Cout, int Cst, int es, bool pointwise) 
 template <typename T, int RB, int CT, int NW>
 static int launch_pw_cfg(const PwArgs& a, const PwPlan& pl, hipStream_t st, int fam) {
     PwArgs a2 = a;
-    static const int no_t = getenv("YDL_PW_NOTSTORE") ? atoi(getenv("YDL_PW_NOTSTORE")) : 0;
     // (bf16 only: the f32 instantiations lose an occupancy step or spill with the extra staging code; parity mode keeps direct stores)
     // (an accumulating launch takes the transposed path when it carries no statistics: the input-gradient fan-in.  Its own
     //  contribution is rounded to bf16 in the staging tile before the add — one rounding more than the direct path.)
-    static const int acc_ts_env = getenv("YDL_PW_ACC_TS") ? atoi(getenv("YDL_PW_ACC_TS")) : 1;
-    const int acc_ts = g_pw_acc_ts >= 0 ? g_pw_acc_ts : acc_ts_env;       // ydl_debug_set key 14
+    const int acc_ts = g_pw_acc_ts >= 0 ? g_pw_acc_ts : 1;       // ydl_debug_set key 14
     // measured per layer (tools/conv_bench.py dgrad --acc 1): faster everywhere (-8 ... -27 %) but on 256-byte K rows with 128-channel
     // wave tiles, where the direct read-modify-write wins (128->128 @160^2: 90 vs 111 us)
     // (round 5: with statistics too, bf16 — they are taken in the row layout of the transposed store, see ROWSTATS in the kernel;
-    //  YDL_PW_ACC_TS=2 keeps the statistics launches on the direct path)
+    //  key 14 = 2 keeps the statistics launches on the direct path)
     const bool acc_ok = (a.stats == nullptr || (sizeof(T) == 2 && acc_ts == 1)) && acc_ts && !(RB == 256 && CT == 8);
     const size_t wbytes = (size_t)a.Cout * RB;
     const size_t ts_smem = wbytes + (pl.tstage > pl.smem - wbytes ? pl.tstage : pl.smem - wbytes);
-    // (512-byte rows x 128-channel waves: the transposed stores fit the register file only without the statistics' 64 registers)
-#ifndef PW_TS8_STATS
-#define PW_TS8_STATS 1
-#endif
-    const bool ts_regs = PW_TS8_STATS || !(RB == 512 && CT == 8 && a.stats != nullptr);
-    a2.tstore = (sizeof(T) == 2 && (!a.accumulate || acc_ok) && !no_t && ts_regs && ts_smem <= 160 * 1024) ? 1 : 0;
+    a2.tstore = (sizeof(T) == 2 && (!a.accumulate || acc_ok) && ts_smem <= 160 * 1024) ? 1 : 0;
     {
         // the store path is part of the recorded name: "ts" = per-wave LDS-transposed 16-byte stores, "direct" = register-layout stores
         static const std::string base = std::string("pw_kernel<") + (sizeof(T) == 4 ? "f32" : "bf16") + "," + std::to_string(RB) + "," +
@@ -2823,14 +2744,15 @@ static int launch_pw_cfg(const PwArgs& a, const PwPlan& pl, hipStream_t st, int 
         YDL_SET_MAX_LDS((pw_kernel<T, RB, CT, NW, TS_, ACC_, ST_>), 160 * 1024);      \
         pw_kernel<T, RB, CT, NW, TS_, ACC_, ST_><<<pl.grid_m, NW * 64, sm, st>>>(a2); \
     } while (0)
+    constexpr bool TS = sizeof(T) == 2;      // (the f32 kernels have no transposed-store form: tstore is 0 for them)
     if (a2.accumulate && a2.stats) {
-        if (a2.tstore) PW_LAUNCH(true, true, true); else PW_LAUNCH(false, true, true);
+        if (TS && a2.tstore) PW_LAUNCH(TS, true, true); else PW_LAUNCH(false, true, true);
     } else if (a2.accumulate) {
-        if (a2.tstore) PW_LAUNCH(true, true, false); else PW_LAUNCH(false, true, false);
+        if (TS && a2.tstore) PW_LAUNCH(TS, true, false); else PW_LAUNCH(false, true, false);
     } else if (a2.stats) {
-        if (a2.tstore) PW_LAUNCH(true, false, true); else PW_LAUNCH(false, false, true);
+        if (TS && a2.tstore) PW_LAUNCH(TS, false, true); else PW_LAUNCH(false, false, true);
     } else {
-        if (a2.tstore) PW_LAUNCH(true, false, false); else PW_LAUNCH(false, false, false);
+        if (TS && a2.tstore) PW_LAUNCH(TS, false, false); else PW_LAUNCH(false, false, false);
     }
 #undef PW_LAUNCH
     YDL_LAUNCH_CHECK();
@@ -2843,9 +2765,13 @@ static int launch_pw(const PwArgs& a, const PwPlan& pl, hipStream_t st, int fam)
         YDL_CHECK(pl.RB == 512 && pl.CT == 8, "internal: unexpected point-wise plan");
         return launch_pw_cfg<T, 512, 8, 8>(a, pl, st, fam);
     }
-    if (pl.RB == 128) return pl.CT == 8 ? launch_pw_cfg<T, 128, 8, 4>(a, pl, st, fam) : launch_pw_cfg<T, 128, 4, 4>(a, pl, st, fam);
-    if (pl.RB == 256) return pl.CT == 8 ? launch_pw_cfg<T, 256, 8, 4>(a, pl, st, fam) : launch_pw_cfg<T, 256, 4, 4>(a, pl, st, fam);
+    if constexpr (sizeof(T) == 4) {      // 128-channel waves on 128- and 256-byte rows: f32 only (pw_plan gives the bf16 layers 64-channel waves)
+        if (pl.RB == 128 && pl.CT == 8) return launch_pw_cfg<T, 128, 8, 4>(a, pl, st, fam);
+        if (pl.RB == 256 && pl.CT == 8) return launch_pw_cfg<T, 256, 8, 4>(a, pl, st, fam);
+    }
     YDL_CHECK(pl.CT == 4, "internal: unexpected point-wise plan");
+    if (pl.RB == 128) return launch_pw_cfg<T, 128, 4, 4>(a, pl, st, fam);
+    if (pl.RB == 256) return launch_pw_cfg<T, 256, 4, 4>(a, pl, st, fam);
     return launch_pw_cfg<T, 512, 4, 4>(a, pl, st, fam);
 }
 
@@ -2880,14 +2806,36 @@ static int launch_igemm(IgemmArgs a, hipStream_t st, int fam) {
     return 0;
 }
 
-struct TileCfg { int BM, BN; int ring; };
-static int g_ring_loaders = -1;   // ydl_debug_set key 19: loader-wave ring kernel where it measured faster (-1: YDL_RING_LOADERS or on)
-static int ring_loaders() {
-    static const int env = getenv("YDL_RING_LOADERS") ? atoi(getenv("YDL_RING_LOADERS")) : 1;
-    return g_ring_loaders >= 0 ? g_ring_loaders : env;
-}     // ring != 0: igemm2_kernel (bf16 LDS-DMA ring) instantiation id
+// LDS-DMA ring instantiations (bf16): one row per instantiation pick_cfg can choose.  The plan, halo_ok, ring_has_bnred and the launchers
+// all read this table.
+enum RingId { RING_NONE, RING_128x128, RING_64x128, RING_128x64, RING_256x128_STG, RING_256x128_LOADERS, RING_128x128_LOADERS,
+              RING_128x128_LOADERS_S2, RING_COUNT };
+enum RingForm { FORM_RING, FORM_STAGGERED, FORM_LOADERS };      // igemm2_kernel, igemm2_kernel<..., STG>, igemm2l_kernel
+struct RingCfg {
+    int BM, BN;
+    RingForm form;
+    bool bnred;      // has an instantiation with the fused BatchNorm-backward reduce
+    bool patch;      // a 3x3 / stride-1 layer that chose it may run on the patch-form kernels instead (halo_ok)
+};
+static const RingCfg kRing[RING_COUNT] = {
+    {0, 0, FORM_RING, false, false},
+    {128, 128, FORM_RING, true, true},           // 8 waves, 2 stages = 64 KB: two CTAs per CU
+    {64, 128, FORM_RING, true, false},           // 4 waves of 32x64, 3 stages = 72 KB: two CTAs per CU (small M)
+    {128, 64, FORM_RING, true, true},            // 8 waves of 32x32, 2 stages = 48 KB
+    {256, 128, FORM_STAGGERED, false, true},     // 64x64 wave tiles, staggered halves, 3 stages = 144 KB: one CTA per CU
+    {256, 128, FORM_LOADERS, false, true},       // 8 multipliers of 64x64 + 4 loaders, 3 stages = 144 KB
+    {128, 128, FORM_LOADERS, false, false},      // 8 multipliers of 32x64 + 4 loaders, 3 stages = 96 KB
+    {128, 128, FORM_LOADERS, false, true},       // 4 multipliers of 64x64 + 4 loaders, 2 stages: two CTAs (16 waves) per CU
+};
+// (measured and dropped — profiles/r5_ab_ring_loader_waves.log: 256 x 128 with two loaders 3..8 % behind four; 128 x 128 with two stages and two
+//  CTAs per CU: four loaders = 24 waves = 80 registers, two loaders = 16 DMAs per loader and step — both 10..60 % slower.  256 x 256 tiles
+//  spill 520..600 VGPRs.  DESIGN.md section 4 has the other forms that lost.)
+static bool ring_has_bnred(int id) { return kRing[id].bnred; }
+
+struct TileCfg { int BM, BN; int ring; };      // ring != RING_NONE: the kRing row (bf16 LDS-DMA ring), else the igemm_kernel tile
+static int g_ring_loaders = -1;   // ydl_debug_set key 19: loader-wave ring kernel where it measured faster (-1: the default, on)
 static int g_ring_enabled = 1;
-static int g_ring_persist = 1;
+static int g_ring_persist = 1;    // ydl_debug_set key 6
 
 template <int BM, int BN, int NW, int WP, int S, bool RED = false, int STG = 0>
 static int launch_igemm2(IgemmArgs a, hipStream_t st, int fam) {
@@ -2908,20 +2856,15 @@ static int launch_igemm2(IgemmArgs a, hipStream_t st, int fam) {
         // tile order (speed only): which operand would be re-fetched from beyond L2?  channel-tile-fastest streams the whole
         // weight matrix once per pixel tile when it does not fit the XCD's L2; pixel-tile-fastest keeps one weight slab in
         // L2 and re-reads the activations once per channel tile
-        static const int forced = getenv("YDL_RING_MFAST") ? atoi(getenv("YDL_RING_MFAST")) : -1;
         const double wbytes = (double)a.Cout * a.Ttot * a.Kc * 2.0;
         const double abytes = (double)a.N * a.Hi * a.Wi * a.lda * 2.0;
         a.m_fastest = (wbytes > 2.0e6 && (double)mtiles * wbytes > (double)a.grid_n * abytes) ? 1 : 0;
-        if (forced >= 0) a.m_fastest = forced;
-        static const int dbg = getenv("YDL_RING_DBG") ? atoi(getenv("YDL_RING_DBG")) : 0;
-        a.dbg = dbg;
     }
     const size_t smem = (size_t)S * (BM + BN) * GROWB + 3 * MAXTAPS * sizeof(int) + (RED ? BN * 16 : 0);
     static const std::string nm = std::string("igemm2_kernel<") + std::to_string(BM) + "," + std::to_string(BN) + "," +
                                   std::to_string(NW) + "," + std::to_string(WP) + "," + std::to_string(S) + (RED ? ",bnred>" : (STG ? ",stg>" : ">"));
     if constexpr (S == 2 && STG == 0 && BN == 128) {
         // persistent form (igemm2p_kernel): worth it when a CTA gets more than one tile; needs n_k >= 2 in every class
-        static const int persist = getenv("YDL_RING_PERSIST") ? atoi(getenv("YDL_RING_PERSIST")) : 1;
         const int spt = a.Kc >> 6;
         int min_taps = a.ntaps;
         if (a.ncls > 1) { min_taps = 1 << 30; for (int c = 0; c < a.ncls; ++c) min_taps = min(min_taps, a.cls_ntaps[c]); }
@@ -2938,7 +2881,7 @@ static int launch_igemm2(IgemmArgs a, hipStream_t st, int fam) {
         // measured (tools/conv_bench.py --persist 0/1, config-2 layers): +5..10 % with 128-wide tiles once a CTA walks >= 2.5 tiles,
         // neutral to -12 % below that (a second resident CTA overlaps better than a short walk) and with 64-wide tiles
         // (not with the fused reduce: its epilogue on top of the walk's two descriptor sets spills 41 VGPRs)
-        if (persist && g_ring_persist && !RED && BN == 128 && min_taps * spt >= 2 && G >= 8 && 2 * ntiles >= 5 * G) {
+        if (g_ring_persist && !RED && BN == 128 && min_taps * spt >= 2 && G >= 8 && 2 * ntiles >= 5 * G) {
             static const std::string nmp = nm + ":persistent";
             ydl_note_kernel(fam, nmp.c_str());
             igemm2p_kernel<BM, BN, NW, WP, RED><<<G, NW * 64, smem, st>>>(a);
@@ -2953,14 +2896,11 @@ static int launch_igemm2(IgemmArgs a, hipStream_t st, int fam) {
     return 0;
 }
 
-// ring instantiations: id -> (BM, BN)
-static const int kRingBM[] = {0, 256, 128, 128, 256, 128, 128, 128, 128, 64, 64, 128, 128, 128, 128, 256, 256, 128, 256, 256, 256, 256, 256, 256, 256, 128, 256, 128, 128, 128, 128};
-static const int kRingBN[] = {0, 128, 128, 64, 64, 128, 128, 128, 64, 128, 128, 64, 64, 64, 128, 128, 128, 128, 128, 128, 256, 256, 256, 128, 128, 128, 128, 128, 128, 128, 128};
-// patch-form 3x3 / stride-1 kernel (igemm2h_kernel): eligibility and launch
-static int g_halo = 1;          // ydl_debug_set key 8 (YDL_HALO=0 at start-up)
+// patch-form 3x3 / stride-1 kernels (igemm2h_kernel / igemm2hs_kernel): eligibility and launch.  (Not for a launch with the fused
+// BatchNorm-backward reduce: conv_plan asks only without it.)
+static int g_halo = 1;          // ydl_debug_set key 8
 static bool halo_ok(const IgemmArgs& a, int id) {
-    static const int env = getenv("YDL_HALO") ? atoi(getenv("YDL_HALO")) : 1;
-    if (!env || !g_halo || (id != 7 && id != 13 && id != 15 && id != 24 && id != 29) || a.br.nseg > 0) return false;
+    if (!g_halo || !kRing[id].patch) return false;
     if (a.ncls > 1 || a.ntaps != 9 || a.Ttot != 9 || a.in_mul != 1 || a.out_mul != 1 || a.out_h0 != 0 || a.out_w0 != 0) return false;
     if (a.Hi != a.Ho || a.Wi != a.Wo || a.Hg != a.Ho || a.Wg != a.Wo || (a.Ho & 7) || (a.Wo & 15) || (a.Kc & 63)) return false;
     bool seen[9] = {false, false, false, false, false, false, false, false, false};
@@ -2971,24 +2911,21 @@ static bool halo_ok(const IgemmArgs& a, int id) {
     }
     return true;
 }
-template <int BN, int S, int NW = 8>
+template <int BN, int S>
 static int launch_igemm2h(IgemmArgs a, hipStream_t st, int fam) {
-    constexpr int WP = 4;
+    constexpr int NW = 8, WP = 4;
     a.grid_n = (a.Cst + BN - 1) / BN;
     a.grid_m = a.M / 128;                                  // every tile is full (halo_ok)
     YDL_CHECK(a.bytesB < 0x08000000u, "ring kernel: weight matrix of 128 MiB or more is not supported");
     {
-        static const int forced = getenv("YDL_RING_MFAST") ? atoi(getenv("YDL_RING_MFAST")) : -1;
         const double wbytes = (double)a.Cout * a.Ttot * a.Kc * 2.0;
         const double abytes = (double)a.N * a.Hi * a.Wi * a.lda * 2.0;
         a.m_fastest = (wbytes > 2.0e6 && (double)a.grid_m * wbytes > (double)a.grid_n * abytes) ? 1 : 0;
-        if (forced >= 0) a.m_fastest = forced;
     }
-    static const std::string nm = std::string("igemm2h_kernel<128,") + std::to_string(BN) + "," + std::to_string(S) + (NW == 8 ? ">" : ",nw4>");
+    static const std::string nm = std::string("igemm2h_kernel<128,") + std::to_string(BN) + "," + std::to_string(S) + ">";
     ydl_note_kernel(fam, nm.c_str());
     if constexpr (S == 2) {
-        static const int onep_all = getenv("YDL_HALO_ONEP") ? atoi(getenv("YDL_HALO_ONEP")) : 0;     // 1: one patch buffer for any channel count
-        if (a.Kc == 64 || (onep_all && BN == 64)) {
+        if (a.Kc == 64) {            // one channel block needs one patch buffer
             const size_t smem = (size_t)HS_PROWS * GROWB + 2 * (size_t)BN * GROWB + 128;
             YDL_SET_MAX_LDS((igemm2hs_kernel<BN, NW, WP, true>), smem);
             igemm2hs_kernel<BN, NW, WP, true><<<dim3(a.grid_m * a.grid_n), NW * 64, smem, st>>>(a);
@@ -3005,23 +2942,31 @@ static int launch_igemm2h(IgemmArgs a, hipStream_t st, int fam) {
     YDL_LAUNCH_CHECK();
     return 0;
 }
+// the patch form of a layer whose ring choice was ``id``
+static int launch_patch(int id, const IgemmArgs& a, hipStream_t st, int fam) {
+    if (kRing[id].BN == 128) return launch_igemm2h<128, 2>(a, st, fam);
+    // 64-wide tiles, one channel block: the two-stage form with ONE patch buffer is 40 KB — four CTAs per CU (64->64 k3 @160^2: forward
+    // 66.8 -> 58.5 us, dgrad 54.2 -> 51.2); more channel blocks: three weight stages of 8 KB, two patches = 72 KB, two CTAs per CU
+    if (a.Kc == 64) return launch_igemm2h<64, 2>(a, st, fam);
+    return launch_igemm2h<64, 3>(a, st, fam);
+}
 
 // fused-parity stride-2 dgrad (igemm2s_kernel): eligibility and launch.  ``a`` is the dgrad's base argument block (A = dy, C = dx).
-static int g_s2fused = 1;       // ydl_debug_set key 9 (YDL_S2FUSED=0 at start-up)
+static int g_s2fused = 1;       // ydl_debug_set key 9
 static bool s2fused_ok(const ydl_conv_geom* g, int dtype) {
-    static const int env = getenv("YDL_S2FUSED") ? atoi(getenv("YDL_S2FUSED")) : 1;
-    if (!env || !g_s2fused || !g_ring_enabled || dtype != YDL_BF16) return false;
+    if (!g_s2fused || !g_ring_enabled || dtype != YDL_BF16) return false;
     if (g->k != 3 || g->s != 2 || g->p != 1 || g->Hi != 2 * g->Ho || g->Wi != 2 * g->Wo) return false;
     if ((g->Ho & 7) || (g->Wo & 15) || (round_up(g->Cout, 8) & 63) || (g->Cin & 7) || g->Cin < 64) return false;
     return true;
 }
-template <int S, bool ACC>
+template <bool ACC>
 static int launch_igemm2s_cfg(const IgemmArgs& a, hipStream_t st, int fam) {
-    constexpr int NW = 8, WP = 4;
+    // two weight stages (round 5): a three-stage form spilled 9 VGPRs at the 128-register budget of four waves per SIMD and measured
+    // 2..5 % slower on both layers that run it (64->128 @160^2: 118.8 vs 112.8 us, 128->256 @80^2: 96.9 vs 94.9 us)
+    constexpr int NW = 8, WP = 4, S = 2;
     const size_t smem = 2 * (size_t)S2_PROWS * GROWB + (size_t)S * 64 * GROWB;
     YDL_SET_MAX_LDS((igemm2s_kernel<NW, WP, S, ACC>), smem);
-    static const std::string nm = std::string("igemm2s_kernel<128,64,") + std::to_string(S) + (ACC ? ",acc>" : ">");
-    ydl_note_kernel(fam, nm.c_str());
+    ydl_note_kernel(fam, ACC ? "igemm2s_kernel<128,64,2,acc>" : "igemm2s_kernel<128,64,2>");
     igemm2s_kernel<NW, WP, S, ACC><<<dim3(a.grid_m * a.grid_n), NW * 64, smem, st>>>(a);
     YDL_LAUNCH_CHECK();
     return 0;
@@ -3030,125 +2975,71 @@ static int launch_igemm2s(IgemmArgs a, hipStream_t st, int fam) {
     a.grid_n = (a.Cst + 63) / 64;
     a.grid_m = a.N * (a.Hi >> 3) * (a.Wi >> 4);
     YDL_CHECK(a.bytesB < 0x08000000u, "ring kernel: weight matrix of 128 MiB or more is not supported");
-    // two weight stages everywhere (round 5): the three-stage form spills 9 VGPRs at the 128-register budget of four waves per SIMD and
-    // measured 2..5 % slower on both layers that run it (64->128 @160^2: 118.8 vs 112.8 us, 128->256 @80^2: 96.9 vs 94.9 us)
-    static const int stages = getenv("YDL_S2_STAGES") ? atoi(getenv("YDL_S2_STAGES")) : 2;       // tuning
-    // (accumulate: the two-stage form — the three-stage one spills inside its block loop: 64->128 @160^2 143 against 153 us)
-    if (a.accumulate) return stages == 33 ? launch_igemm2s_cfg<3, true>(a, st, fam) : launch_igemm2s_cfg<2, true>(a, st, fam);
-    return stages == 2 ? launch_igemm2s_cfg<2, false>(a, st, fam) : launch_igemm2s_cfg<3, false>(a, st, fam);
+    return a.accumulate ? launch_igemm2s_cfg<true>(a, st, fam) : launch_igemm2s_cfg<false>(a, st, fam);
 }
 
-static bool ring_has_bnred(int id) { return id == 7 || id == 9 || id == 13; }
-// statistics rows of a forward launch: grid_m partial rows of block_m pixels (the last one may be shorter)
-struct FwdRows { int grid_m, block_m; };
-// rows != nullptr: no launch, *rows = the partial-row geometry of the kernel this id runs on (the patch form or the ring tile)
-static int launch_ring(int id, const IgemmArgs& a, hipStream_t st, int fam, FwdRows* rows = nullptr) {
-    if (rows) {
-        const int bm = (a.br.nseg == 0 && halo_ok(a, id)) ? 128 : kRingBM[id];       // (igemm2h / igemm2hs: one 8 x 16 patch per tile)
-        *rows = FwdRows{(a.M + bm - 1) / bm, bm};
-        return 0;
-    }
-    if (a.br.nseg > 0) {          // epilogue with the fused BatchNorm-backward reduce: the instantiations the dgrads of the models use
+static int launch_ring(int id, const IgemmArgs& a, hipStream_t st, int fam) {
+    if (a.br.nseg > 0) {          // epilogue with the fused BatchNorm-backward reduce: the rows with kRing[id].bnred
         switch (id) {
-            case 7: return launch_igemm2<128, 128, 8, 4, 2, true>(a, st, fam);
-            case 9: return launch_igemm2<64, 128, 4, 2, 3, true>(a, st, fam);
-            case 13: return launch_igemm2<128, 64, 8, 4, 2, true>(a, st, fam);
+            case RING_128x128: return launch_igemm2<128, 128, 8, 4, 2, true>(a, st, fam);
+            case RING_64x128: return launch_igemm2<64, 128, 4, 2, 3, true>(a, st, fam);
+            case RING_128x64: return launch_igemm2<128, 64, 8, 4, 2, true>(a, st, fam);
         }
         ydl_set_error("fused BatchNorm reduce: no instantiation for this ring configuration (query ydl_conv_dgrad_bnred_supported)");
         return 1;
     }
-    if (halo_ok(a, id)) {
-        // weight ring depth: 6 stages x 16 KB + two patches = 144 KB, one CTA per CU with five weight steps in flight; 64-wide tiles
-        // 3 stages x 8 KB = 72 KB, two CTAs per CU (YDL_HALO_S: tuning)
-        static const int hs = getenv("YDL_HALO_S") ? atoi(getenv("YDL_HALO_S")) : 0;
-        if (id == 7 || id == 15 || id == 24 || id == 29) {
-            if (hs == 3) return launch_igemm2h<128, 3>(a, st, fam);
-            if (hs == 6) return launch_igemm2h<128, 6>(a, st, fam);
-            return launch_igemm2h<128, 2>(a, st, fam);
-        }
-        if (hs == 6) return launch_igemm2h<64, 6>(a, st, fam);
-        if (hs == 43) return launch_igemm2h<64, 3, 4>(a, st, fam);       // four waves of 32 x 64: 16 MFMAs per wave and barrier (slower)
-        // one channel block: the two-stage form with ONE patch buffer is 40 KB — four CTAs per CU (64->64 k3 @160^2: forward
-        // 66.8 -> 58.5 us, dgrad 54.2 -> 51.2); more channel blocks: three weight stages, two patches, two CTAs per CU
-        if (hs == 2 || (hs == 0 && a.Kc == 64)) return launch_igemm2h<64, 2>(a, st, fam);
-        return launch_igemm2h<64, 3>(a, st, fam);
-    }
     switch (id) {
-        case 1: return launch_igemm2<256, 128, 8, 4, 3>(a, st, fam);
-        case 2: return launch_igemm2<128, 128, 4, 2, 4>(a, st, fam);
-        case 3: return launch_igemm2<128, 64, 4, 4, 3>(a, st, fam);
-        case 4: return launch_igemm2<256, 64, 8, 8, 3>(a, st, fam);
-        case 5: return launch_igemm2<128, 128, 8, 4, 4>(a, st, fam);
-        case 6: return launch_igemm2<128, 128, 4, 2, 2>(a, st, fam);      // 64 KB: two CTAs per CU
-        case 7: return launch_igemm2<128, 128, 8, 4, 2>(a, st, fam);
-        case 8: return launch_igemm2<128, 64, 4, 2, 3>(a, st, fam);       // 72 KB: two CTAs per CU, 64x32 wave tiles
-        case 9: return launch_igemm2<64, 128, 4, 2, 3>(a, st, fam);       // 72 KB: two CTAs per CU, 32x64 wave tiles (small M)
-        case 10: return launch_igemm2<64, 128, 4, 2, 4>(a, st, fam);      // 96 KB: one CTA per CU, deeper ring
-        case 11: return launch_igemm2<128, 64, 4, 2, 2>(a, st, fam);      // 48 KB: three CTAs per CU (64-channel outputs)
-        case 12: return launch_igemm2<128, 64, 4, 4, 2>(a, st, fam);      // 48 KB, 32x64 wave tiles
-        case 13: return launch_igemm2<128, 64, 8, 4, 2>(a, st, fam);      // 48 KB, 8 waves of 32x32
-        case 14: return launch_igemm2<128, 128, 8, 4, 2, false, 1>(a, st, fam);   // staggered halves (round 5)
-        case 15: return launch_igemm2<256, 128, 8, 4, 3, false, 1>(a, st, fam);   // 256x128, 64x64 wave tiles, 144 KB: one CTA per CU
-        case 16: return launch_igemm2<256, 128, 8, 4, 2, false, 1>(a, st, fam);   // the same with two stages (96 KB)
-        case 17: return launch_igemm2<128, 128, 8, 4, 2, false, 2>(a, st, fam);   // staggered + s_setprio 1 for the younger half
-        case 18: return launch_igemm2<256, 128, 8, 4, 3, false, 2>(a, st, fam);
-        case 19: return launch_igemm2<256, 128, 8, 4, 3, false, 3>(a, st, fam);   // timing experiment: 32x32x16 MFMAs (garbage results)
-        // (ids 20-22: 256 x 256 tiles — 8 waves of 64 x 128 spill ~600 VGPRs at the 256-register budget of two waves per SIMD, 4 waves of
-        //  128 x 128 spill 521 even with 256 AGPRs: not kept)
-        case 24: return launch_igemm2l<256, 128, 8, 4, 3, 4>(a, st, fam);         // loader waves: 8 multipliers of 64x64 + 4 loaders, 144 KB
-        case 25: return launch_igemm2l<128, 128, 8, 4, 3, 4>(a, st, fam);         // 8 multipliers of 32x64 + 4 loaders, 96 KB
-        case 29: return launch_igemm2l<128, 128, 4, 2, 2, 4>(a, st, fam);         // 4 multipliers of 64x64 + 4 loaders, two stages: two CTAs (16 waves) per CU
-        // (ids 26-28, measured and dropped — profiles/r5_ab_ring_loader_waves.log: 256 x 128 with two loaders 3..8 % behind four; 128 x 128 with two
-        //  stages and two CTAs per CU: four loaders = 24 waves = 80 registers, two loaders = 16 DMAs per loader and step — both 10..60 % slower)
-        case 23: return launch_igemm2<256, 128, 4, 2, 3>(a, st, fam);             // 256x128, FOUR waves of 128x64 (one per SIMD), 144 KB: measured 15..40 % slower than id 15
+        case RING_128x128: return launch_igemm2<128, 128, 8, 4, 2>(a, st, fam);
+        case RING_64x128: return launch_igemm2<64, 128, 4, 2, 3>(a, st, fam);
+        case RING_128x64: return launch_igemm2<128, 64, 8, 4, 2>(a, st, fam);
+        case RING_256x128_STG: return launch_igemm2<256, 128, 8, 4, 3, false, 1>(a, st, fam);
+        case RING_256x128_LOADERS: return launch_igemm2l<256, 128, 8, 4, 3, 4>(a, st, fam);
+        case RING_128x128_LOADERS: return launch_igemm2l<128, 128, 8, 4, 3, 4>(a, st, fam);
+        case RING_128x128_LOADERS_S2: return launch_igemm2l<128, 128, 4, 2, 2, 4>(a, st, fam);
     }
     ydl_set_error("internal: unknown ring kernel id");
     return 1;
 }
 
-// Tile choice: a pure function of (M, Cst, K chunks, dtype) — the stats-workspace queries call it too.
-static TileCfg pick_cfg(int M, int Cst, int nchunks = 0, bool bf16 = false, int Kc = 0, int taps = 0, bool one_class = true, bool loaders_ok = true) {
+// Tile choice: a pure function of (M, Cst, K chunks, dtype) and the debug knobs.
+static TileCfg pick_cfg(int M, int Cst, int nchunks, bool bf16, int Kc, int taps, bool one_class, bool loaders_ok) {
     TileCfg c;
-    c.ring = 0;
-    // 64..127 stored output channels: 128x64 tile, 8 waves, 2 stages = 48 KB (three CTAs per CU).  Measured against the register-staged
-    // kernel: 64->128 k3s2 dgrad @320^2 231 -> 199 us, 64->64 k3 @160^2 78/72 -> 77/60 us, 128->64 k3 @160^2 fwd 120 -> 106 us
-    // (YDL_RING64=0 switches it off, another id selects that instantiation)
-    static const int ring64 = getenv("YDL_RING64") ? atoi(getenv("YDL_RING64")) : 13;
-    if (bf16 && g_ring_enabled && Cst >= (ring64 ? 64 : 128) && Cst % 8 == 0 && nchunks >= 16 && Kc > 0 && Kc % 64 == 0 && taps <= 29) {
-        // bf16 MFMA-bound layers (>= 2 K-steps of 64, >= 128 output channels): LDS-DMA ring kernel.  Measured on MI355X over the
+    c.ring = RING_NONE;
+    if (bf16 && g_ring_enabled && Cst >= 64 && Cst % 8 == 0 && nchunks >= 16 && Kc > 0 && Kc % 64 == 0 && taps <= 29) {
+        // bf16 MFMA-bound layers (>= 2 K-steps of 64, >= 64 output channels): LDS-DMA ring kernel.  Measured on MI355X over the
         // 3x3 and wide 1x1 layers of BASELINE config 2 (tools/conv_bench.py, forward and dgrad): the 128x128 tile with a 2-stage
         // ring (64 KB of LDS, two CTAs per CU: one CTA's epilogue and load latency hide behind the other's MFMAs) beats the
         // deeper one-CTA-per-CU rings on every layer but the smallest grids, which prefer 64-pixel tiles (more CTAs).
-        static const int forced = getenv("YDL_RING") ? atoi(getenv("YDL_RING")) : -1;      // tuning: force an instantiation id
         const long b128 = (long)((M + 127) / 128) * ((Cst + 127) / 128);
-        int id = b128 < 256 ? 9 : 7;
+        int id = b128 < 256 ? RING_64x128 : RING_128x128;
         // Round 5: 256 x 128 tile, 64 x 64 wave tiles, three stages (144 KB: ONE CTA per CU) with the two wave halves staggered by half a
-        // K-step (igemm2_kernel<..., STG>) — 25 % fewer staged bytes per MAC than 128 x 128.  Measured against id 7 / 9 on config 2
-        // (tools/conv_bench.py, YDL_RING=15): wins 3..8 % where one round of CTAs covers the layer and the K loop is long enough to
+        // K-step (igemm2_kernel<..., STG>) — 25 % fewer staged bytes per MAC than 128 x 128.  Measured against the two plain tiles on
+        // config 2 (tools/conv_bench.py): wins 3..8 % where one round of CTAs covers the layer and the K loop is long enough to
         // carry the un-overlapped prologue / epilogue (256->512 k3s2 @40^2 82 -> 79 us, 512->1024 k3s2 @20^2 73 -> 69, 256->256 k3
         // @40^2 42 -> 39, 2048->1024 @20^2 37 -> 34.5, 768->128 @80^2 54 -> 51); loses on the 9-step 160^2 layer (the persistent
         // 128 x 128 form keeps those), with 100 tiles (512->512 k3 @20^2: 59 vs 51 us) and on the multi-class strided dgrads.
-        static const int big = getenv("YDL_RING256") ? atoi(getenv("YDL_RING256")) : 1;
         const long b256 = (long)((M + 255) / 256) * ((Cst + 127) / 128);
-        if (big && one_class && Cst >= 128 && b256 >= 180 && b256 <= 512 && nchunks >= 96) id = 15;
+        if (one_class && Cst >= 128 && b256 >= 180 && b256 <= 512 && nchunks >= 96) id = RING_256x128_STG;
         // Round 5, loader waves (igemm2l_kernel: 8 multiplier + 4 loader waves, one CTA per CU, three stages): where the choice was a
         // one-CTA-per-CU tile anyway it wins 3..12 % over the staggered 256 x 128 (256->512 k3s2 @40^2 85.7 -> 75.1 us, 256->256 k3 @40^2
         // 41.0 -> 38.5, 2048->1024 @20^2 35.1 -> 32.4, 512->1024 k3s2 @20^2 65.4 -> 62.0), and as 128 x 128 it replaces the 64 x 128 tile of
         // the small grids (512->512 k3 @20^2 forward 44.9 -> 37.8 us, dgrad 42.4 -> 35.6; 1024->512 @20^2 15.8 -> 14.1).  The two-CTA
         // 128 x 128 ring keeps everything else: with 24 waves per CU the split form has 80 registers and loses 10-40 %.
-        // (ydl_debug_set key 19 / YDL_RING_LOADERS=0: off)
-        if (ring_loaders() && loaders_ok) {     // (not for a launch with the fused BatchNorm-backward reduce, nor for its support query)
-            if (id == 15 && nchunks >= 128) id = 24;      // (12 K-steps, 768 -> 128 @80^2: 42.8 against 41.2 us — the staggered form keeps it)
-            if (id == 9 && b128 >= 64) id = 25;
+        // (ydl_debug_set key 19 = 0: off)
+        if (g_ring_loaders && loaders_ok) {     // (not for a launch with the fused BatchNorm-backward reduce, nor for its support query)
+            if (id == RING_256x128_STG && nchunks >= 128) id = RING_256x128_LOADERS;      // (12 K-steps, 768 -> 128 @80^2: 42.8 against 41.2 us — the staggered form keeps it)
+            if (id == RING_64x128 && b128 >= 64) id = RING_128x128_LOADERS;
             // the two-CTA 128 x 128 ring where it is NOT walked persistently (fewer than 2.5 tiles per resident CTA): 4 multiplier waves of
             // 64 x 64 + 4 loader waves, two stages, two CTAs per CU (128 registers) — 3..8 % faster than the 8-wave form (512->512 @40^2
             // forward 31.4 -> 29.6 us, dgrad 28.6 -> 26.2; 768->128 @80^2 42.3 -> 40.2); the persistent walk keeps the many-tile layers
             // (64->128 k3s2 @160^2: 112 against 123 us)
-            if (id == 7 && b128 < 1280) id = 29;
+            if (id == RING_128x128 && b128 < 1280) id = RING_128x128_LOADERS_S2;
         }
-        if (Cst < 128) id = ring64;
-        if (forced >= 0) id = forced;
-        if (id > 0) { c.ring = id; c.BM = kRingBM[id]; c.BN = kRingBN[id]; return c; }
+        // 64..127 stored output channels: 128x64 tile, 8 waves, 2 stages = 48 KB (three CTAs per CU).  Measured against the register-staged
+        // kernel: 64->128 k3s2 dgrad @320^2 231 -> 199 us, 64->64 k3 @160^2 78/72 -> 77/60 us, 128->64 k3 @160^2 fwd 120 -> 106 us
+        if (Cst < 128) id = RING_128x64;
+        c.ring = id; c.BM = kRing[id].BM; c.BN = kRing[id].BN;
+        return c;
     }
     c.BN = Cst <= 16 ? 16 : (Cst <= 64 ? 64 : 128);
     c.BM = 128;
@@ -3168,80 +3059,83 @@ static TileCfg pick_cfg(int M, int Cst, int nchunks = 0, bool bf16 = false, int 
     return c;
 }
 
-// path_out != nullptr: no launch, *path_out = the kernel family this geometry runs on (0 register-staged tiles, 1 point-wise
-// streaming kernel, 2 LDS-DMA ring, 3 stem kernel)
-// rows_out != nullptr: no launch, *rows_out = the (grid_m, block_m) of the statistics partial rows this launch would write (the
-// ydl_conv_fwd_* queries: host only, no device state — the device-dependent conditions of wreg_ok come after its partial-row refusal)
-template <typename T>
-static int dispatch_igemm(const IgemmArgs& a, hipStream_t st, int fam, FwdRows* rows_out = nullptr, int force_bm = 0, int* path_out = nullptr) {
-    if constexpr (sizeof(T) == 2) {
-        if (fam == 0 && !force_bm && args_stem(a)) {
-            const StemPlan sp = stem_plan(a.M, a.Wo);
-            if (sp.ok && path_out) { *path_out = 3; return 0; }
-            if (sp.ok && rows_out) { *rows_out = FwdRows{sp.grid_m, sp.block_m}; return 0; }
-            if (sp.ok) {
-                StemArgs q{};
-                q.X = (const bf16_t*)a.A; q.W = (const bf16_t*)a.B; q.Y = (bf16_t*)a.C; q.stats = a.stats;
-                q.H = a.Hi; q.Wd = a.Wi; q.ldc = a.ldc; q.M = a.M; q.block_m = sp.block_m; q.stats_ld = a.stats_ld;
-                q.stats_atomic = a.stats_atomic; q.bytesX = a.bytesA;
-                ydl_note_kernel(fam, "stem_kernel<bf16,16,64>");
-                stem_kernel<<<sp.grid_m, 256, 0, st>>>(q);
-                YDL_LAUNCH_CHECK();
-                return 0;
-            }
-        }
+// The launch plan of one forward / dgrad argument block: which kernel runs it and the statistics partial rows it writes.  A pure host
+// function: the ydl_conv_fwd_* queries, the accumulate check of conv_fwd_impl, ydl_conv_dgrad_bnred_supported and dispatch_igemm all
+// read this one result, so a query cannot describe another kernel than the launch runs.
+//   es: element size; fam: 0 forward, 1 dgrad; with_reduce: the launch carries the fused BatchNorm-backward reduce (a.br of a launch,
+//   or the question ydl_conv_dgrad_bnred_supported asks)
+// Order of refusals: the weights-in-registers kernel refuses partial rows BEFORE its device-dependent conditions (wreg_ok), so the
+// forward queries, which always describe a launch with partial rows, need no device.
+enum ConvFamily { CONV_STEM, CONV_PW, CONV_WREG, CONV_PATCH, CONV_RING, CONV_TILE };
+struct ConvPlan {
+    ConvFamily family;      // stem_kernel, pw_kernel, igemm2w_kernel, igemm2h / igemm2hs_kernel, igemm2 / igemm2p / igemm2l_kernel, igemm_kernel
+    TileCfg tile;           // the instantiation: CONV_PATCH / CONV_RING tile.ring = the kRing row, CONV_TILE the (BM, BN) of igemm_kernel
+    PwPlan pw;              //                    CONV_PW (pw_plan)
+    int grid_m, block_m;    // grid_m partial rows of block_m pixels, the last one may be shorter (CONV_WREG writes none: 0, 0)
+    bool has_bnred;         // that instantiation has a form with the fused reduce
+};
+static ConvPlan conv_plan(const IgemmArgs& a, int es, int fam, bool with_reduce) {
+    ConvPlan pl{};
+    if (es == 2 && fam == 0 && args_stem(a)) {
+        const StemPlan sp = stem_plan(a.M, a.Wo);
+        if (sp.ok) { pl.family = CONV_STEM; pl.grid_m = sp.grid_m; pl.block_m = sp.block_m; return pl; }
     }
-    {
-        const PwPlan pl = pw_plan(a.M, a.Kc, a.Cout, a.Cst, (int)sizeof(T), args_pointwise(a));
-        if (pl.ok && !force_bm && path_out) { *path_out = 1; return 0; }
-        if (pl.ok && !force_bm && rows_out) { *rows_out = FwdRows{pl.grid_m, pl.block_m}; return 0; }
-        if (pl.ok && !force_bm) {
+    pl.pw = pw_plan(a.M, a.Kc, a.Cout, a.Cst, es, args_pointwise(a));
+    if (pl.pw.ok) { pl.family = CONV_PW; pl.grid_m = pl.pw.grid_m; pl.block_m = pl.pw.block_m; return pl; }
+    // weights-in-registers kernel: 3x3 / s1 over one 64-channel block (a launch WITH the fused reduce runs on the ring instead)
+    if (es == 2 && !with_reduce && wreg_ok(a)) { pl.family = CONV_WREG; return pl; }
+    // K chunks of the shortest class (multi-class dgrad): the ring kernel wants >= 2 K-steps everywhere
+    int nch = a.ntaps * (a.Kc / (16 / es));
+    if (a.ncls > 1) {
+        nch = 1 << 30;
+        for (int i = 0; i < a.ncls; ++i) nch = min(nch, a.cls_ntaps[i] * (a.Kc / (16 / es)));
+    }
+    pl.tile = pick_cfg(a.M, a.Cst, nch, es == 2, a.Kc, a.Ttot, a.ncls <= 1, !with_reduce);
+    pl.block_m = pl.tile.BM;
+    pl.family = CONV_TILE;
+    if (pl.tile.ring) {
+        const bool patch = !with_reduce && halo_ok(a, pl.tile.ring);
+        pl.family = patch ? CONV_PATCH : CONV_RING;
+        if (patch) pl.block_m = 128;                     // (igemm2h / igemm2hs: one 8 x 16 patch per tile)
+        pl.has_bnred = !patch && ring_has_bnred(pl.tile.ring);
+    }
+    pl.grid_m = (a.M + pl.block_m - 1) / pl.block_m;
+    return pl;
+}
+
+template <typename T>
+static int dispatch_igemm(const IgemmArgs& a, hipStream_t st, int fam) {
+    const ConvPlan pl = conv_plan(a, (int)sizeof(T), fam, a.br.nseg > 0);
+    switch (pl.family) {
+        case CONV_STEM: {
+            StemArgs q{};
+            q.X = (const bf16_t*)a.A; q.W = (const bf16_t*)a.B; q.Y = (bf16_t*)a.C; q.stats = a.stats;
+            q.H = a.Hi; q.Wd = a.Wi; q.ldc = a.ldc; q.M = a.M; q.block_m = pl.block_m; q.stats_ld = a.stats_ld;
+            q.stats_atomic = a.stats_atomic; q.bytesX = a.bytesA;
+            ydl_note_kernel(fam, "stem_kernel<bf16,16,64>");
+            stem_kernel<<<pl.grid_m, 256, 0, st>>>(q);
+            YDL_LAUNCH_CHECK();
+            return 0;
+        }
+        case CONV_PW: {
             YDL_CHECK(a.br.nseg == 0, "fused BatchNorm reduce: this geometry runs on the point-wise kernel (query ydl_conv_dgrad_bnred_supported)");
             PwArgs q{};
             q.X = a.A; q.W = a.B; q.Y = a.C; q.stats = a.stats;
-            q.M = a.M; q.lda = a.lda; q.ldc = a.ldc; q.Cout = a.Cout; q.WN = pl.WN; q.accumulate = a.accumulate;
-            q.block_m = pl.block_m; q.stats_ld = a.stats_ld; q.stats_atomic = a.stats_atomic; q.bytesX = a.bytesA; q.ldw_bytes = a.ldb_bytes;
-            return launch_pw<T>(q, pl, st, fam);
+            q.M = a.M; q.lda = a.lda; q.ldc = a.ldc; q.Cout = a.Cout; q.WN = pl.pw.WN; q.accumulate = a.accumulate;
+            q.block_m = pl.pw.block_m; q.stats_ld = a.stats_ld; q.stats_atomic = a.stats_atomic; q.bytesX = a.bytesA; q.ldw_bytes = a.ldb_bytes;
+            return launch_pw<T>(q, pl.pw, st, fam);
         }
+        case CONV_WREG: return launch_igemm2w(a, st, fam);
+        case CONV_PATCH: return launch_patch(pl.tile.ring, a, st, fam);
+        case CONV_RING: return launch_ring(pl.tile.ring, a, st, fam);
+        case CONV_TILE: break;
     }
-    if constexpr (sizeof(T) == 2) {
-        // weights-in-registers kernel: 3x3 / s1 over one 64-channel block (igemm2w_kernel).  (Not for the path query of
-        // ydl_conv_dgrad_bnred_supported: a launch WITH the fused BatchNorm reduce skips this kernel and runs on the ring.)
-        if (!force_bm && !path_out && wreg_ok(a)) {
-            YDL_CHECK(rows_out == nullptr, "internal: the weights-in-registers kernel writes no statistics partial rows");
-            return launch_igemm2w(a, st, fam);
-        }
-    }
-    // K chunks of the shortest class (multi-class dgrad): the ring kernel wants >= 2 K-steps everywhere
-    int nch = a.ntaps * (a.Kc / (16 / (int)sizeof(T)));
-    if (a.ncls > 1) {
-        nch = 1 << 30;
-        for (int i = 0; i < a.ncls; ++i) nch = min(nch, a.cls_ntaps[i] * (a.Kc / (16 / (int)sizeof(T))));
-    }
-    TileCfg c = pick_cfg(a.M, a.Cst, nch, sizeof(T) == 2, a.Kc, a.Ttot, a.ncls <= 1, a.br.nseg == 0 && path_out == nullptr);
-    if constexpr (sizeof(T) == 2) {
-        if (c.ring && !force_bm) {
-            if (path_out) { *path_out = ring_has_bnred(c.ring) ? 2 : 4; return 0; }
-            return launch_ring(c.ring, a, st, fam, rows_out);
-        }
-    }
-    if (path_out) { *path_out = 0; return 0; }
     YDL_CHECK(a.br.nseg == 0, "fused BatchNorm reduce: this geometry runs on the register-staged kernel (query ydl_conv_dgrad_bnred_supported)");
-    if (c.ring) c = pick_cfg(a.M, a.Cst);
-    if (force_bm) c.BM = force_bm;
-    static const int env_bm = getenv("YDL_FORCE_BM") ? atoi(getenv("YDL_FORCE_BM")) : 0;     // tuning runs only
-    static const int env_bn = getenv("YDL_FORCE_BN") ? atoi(getenv("YDL_FORCE_BN")) : 0;
-    if (env_bm && a.stats == nullptr) c.BM = env_bm;        // (the stats workspace is sized from pick_cfg: keep it for those)
-    if (env_bn && c.BN != 16 && a.Cst >= env_bn) c.BN = env_bn;
-    if (rows_out) { *rows_out = FwdRows{(a.M + c.BM - 1) / c.BM, c.BM}; return 0; }
-    static const int nw8 = getenv("YDL_NW8") ? atoi(getenv("YDL_NW8")) : 1;
-    if (c.BM == 128 && c.BN == 128) {
-        if (nw8 == 2) return launch_igemm<T, 128, 128, 4, 2>(a, st, fam);      // 2x2 waves, 64x64 wave tiles (experiment)
-        return nw8 ? launch_igemm<T, 128, 128, 8>(a, st, fam) : launch_igemm<T, 128, 128, 4>(a, st, fam);
-    }
+    const TileCfg& c = pl.tile;
+    if (c.BM == 128 && c.BN == 128) return launch_igemm<T, 128, 128, 8>(a, st, fam);
     if (c.BM == 128 && c.BN == 64) return launch_igemm<T, 128, 64>(a, st, fam);
     if (c.BM == 128 && c.BN == 16) return launch_igemm<T, 128, 16>(a, st, fam);
-    if (c.BM == 64 && c.BN == 128) return nw8 ? launch_igemm<T, 64, 128, 8>(a, st, fam) : launch_igemm<T, 64, 128, 4>(a, st, fam);
+    if (c.BM == 64 && c.BN == 128) return launch_igemm<T, 64, 128, 8>(a, st, fam);
     if (c.BM == 64 && c.BN == 64) return launch_igemm<T, 64, 64>(a, st, fam);
     return launch_igemm<T, 64, 16>(a, st, fam);
 }
@@ -3298,24 +3192,18 @@ static int fwd_args(const ydl_conv_geom* g, int dtype, const void* x, const void
     return set_extents(a, dtype);
 }
 
-// statistics partial rows of a forward launch: the dispatcher's own selection, run in its query form (no launch)
-static int fwd_rows(const IgemmArgs& a, int dtype, FwdRows& r) {
-    return dtype == YDL_F32 ? dispatch_igemm<float>(a, nullptr, 0, &r) : dispatch_igemm<bf16_t>(a, nullptr, 0, &r);
-}
-
 // (grid_m, block_m) of ydl_conv_fwd with partial rows: the rows a launch with accumulate = 0 writes (a launch that accumulates checks
-// that it writes the same ones).  {0, 0} on a bad geometry.
-static FwdRows fwd_blocks(const ydl_conv_geom* g, int dtype) {
+// that it writes the same ones).  (0, 0) on a bad geometry.
+static ConvPlan fwd_blocks(const ydl_conv_geom* g, int dtype) {
     static float stats_tag;                // any non-null pointer: the queries describe a launch WITH partial rows
     IgemmArgs a;
-    FwdRows r{0, 0};
-    if (fwd_args(g, dtype, nullptr, nullptr, nullptr, &stats_tag, 0, 0, a) || fwd_rows(a, dtype, r)) return FwdRows{0, 0};
-    return r;
+    if (fwd_args(g, dtype, nullptr, nullptr, nullptr, &stats_tag, 0, 0, a)) return ConvPlan{};
+    return conv_plan(a, esize(dtype), 0, false);
 }
 
 extern "C" int64_t ydl_conv_fwd_stats_ws_bytes(const ydl_conv_geom* g, int dtype) {
     // [gridM][2][round_up(Cout,8)] floats + room for ydl_bn_finalize's level-1 chunk partials (gridM/64 + 1 rows)
-    const FwdRows r = fwd_blocks(g, dtype);
+    const ConvPlan r = fwd_blocks(g, dtype);
     if (r.grid_m <= 0) return 0;
     return ((int64_t)r.grid_m + r.grid_m / 64 + 2) * 2 * round_up(g->Cout, 8) * (int64_t)sizeof(float);
 }
@@ -3330,11 +3218,9 @@ static int conv_fwd_impl(const ydl_conv_geom* g, int dtype, const void* x, const
     if (stats_ws != nullptr && !stats_atomic && accumulate) {
         // the queries describe the launch without accumulation: this one must write the same rows (the thin-input stem kernel,
         // for one, runs only without it)
-        FwdRows r0{0, 0}, r1{0, 0};
         IgemmArgs a0 = a;
         a0.accumulate = 0;
-        if (int e = fwd_rows(a0, dtype, r0)) return e;
-        if (int e = fwd_rows(a, dtype, r1)) return e;
+        const ConvPlan r0 = conv_plan(a0, esize(dtype), 0, false), r1 = conv_plan(a, esize(dtype), 0, false);
         YDL_CHECK(r0.grid_m == r1.grid_m && r0.block_m == r1.block_m,
                   "partial-row statistics with accumulate != 0: this geometry runs on another kernel than ydl_conv_fwd_grid_m / _block_m describe");
     }
@@ -3353,9 +3239,9 @@ extern "C" int ydl_conv_fwd_sums(const ydl_conv_geom* g, int dtype, const void* 
 }
 
 static int conv_dgrad_impl(const ydl_conv_geom* g, int dtype, const void* dy, const void* wt, void* dx,
-                           int accumulate, const ydl_bnred* red, int* path_out, void* stream) {
+                           int accumulate, const ydl_bnred* red, ConvPlan* plan_out, void* stream) {
     if (int e = check_geom(g, dtype)) return e;
-    YDL_CHECK(path_out || (aligned16(dy) && aligned16(wt) && aligned16(dx)), "pointers must be 16-byte aligned");
+    YDL_CHECK(plan_out || (aligned16(dy) && aligned16(wt) && aligned16(dx)), "pointers must be 16-byte aligned");
     YDL_CHECK(g->ldy >= round_up(g->Cout, 8), "dy pixel stride must cover Cout rounded up to 8");
     hipStream_t st = (hipStream_t)stream;
     const int s = g->s, k = g->k, pd = g->p;
@@ -3400,7 +3286,12 @@ static int conv_dgrad_impl(const ydl_conv_geom* g, int dtype, const void* dy, co
         if (red) a.br = *red;
         return a;
     };
-    if (red == nullptr && path_out == nullptr && ncls == 4 && s2fused_ok(g, dtype)) {
+    // plan_out != nullptr (ydl_conv_dgrad_bnred_supported): no launch, *plan_out = the plan of this gradient as ONE launch WITH the fused reduce
+    auto run = [&](const IgemmArgs& a) -> int {
+        if (plan_out) { *plan_out = conv_plan(a, esize(dtype), 1, true); return 0; }
+        return dtype == YDL_F32 ? dispatch_igemm<float>(a, st, 1) : dispatch_igemm<bf16_t>(a, st, 1);
+    };
+    if (red == nullptr && plan_out == nullptr && ncls == 4 && s2fused_ok(g, dtype)) {
         // k3 s2 p1: all four parity classes in one CTA (igemm2s_kernel)
         IgemmArgs a = base_args();
         a.M = g->N * g->Ho * g->Wo; a.Hg = g->Ho; a.Wg = g->Wo; a.ntaps = 9;
@@ -3419,25 +3310,23 @@ static int conv_dgrad_impl(const ydl_conv_geom* g, int dtype, const void* dy, co
                 if (cls[order[j]].nt > cls[order[i]].nt) { int t = order[i]; order[i] = order[j]; order[j] = t; }
         IgemmArgs a = base_args();
         a.ncls = ncls;
-        int tp = 0, maxM = 0;
+        int tp = 0;
         for (int i = 0; i < ncls; ++i) {
             const Cls& c = cls[order[i]];
             a.cls_ntaps[i] = c.nt; a.cls_tap0[i] = tp; a.cls_Hg[i] = c.Hg; a.cls_Wg[i] = c.Wg;
             a.cls_M[i] = g->N * c.Hg * c.Wg; a.cls_h0[i] = c.ph; a.cls_w0[i] = c.pw;
             for (int t = 0; t < c.nt; ++t) { a.dh[tp + t] = c.dh[t]; a.dw[tp + t] = c.dw[t]; a.wt[tp + t] = c.wt[t]; }
             tp += c.nt;
-            if (a.cls_M[i] > maxM) maxM = a.cls_M[i];
         }
-        // single-class fields: used for the tile choice (M of the largest class) and as defaults
+        // single-class fields: defaults
         a.Hg = a.cls_Hg[0]; a.Wg = a.cls_Wg[0]; a.out_h0 = a.cls_h0[0]; a.out_w0 = a.cls_w0[0];
         a.ntaps = a.cls_ntaps[0];
         a.M = 0;
         for (int i = 0; i < ncls; ++i) a.M += a.cls_M[i];       // tile choice sees the whole launch
-        (void)maxM;
         if (int e2 = set_extents(a, dtype)) return e2;
-        return dtype == YDL_F32 ? dispatch_igemm<float>(a, st, 1, nullptr, 0, path_out) : dispatch_igemm<bf16_t>(a, st, 1, nullptr, 0, path_out);
+        return run(a);
     }
-    if (path_out && ncls > 1) { *path_out = 0; return 0; }       // one launch per class (debug knob): no fused form
+    if (plan_out && ncls > 1) { *plan_out = ConvPlan{}; plan_out->family = CONV_TILE; return 0; }       // one launch per class (debug knob): no fused form
     YDL_CHECK(red == nullptr || ncls == 1, "fused BatchNorm reduce needs the single-launch dgrad");
     for (int ci = 0; ci < ncls; ++ci) {
         const Cls& c = cls[ci];
@@ -3447,8 +3336,7 @@ static int conv_dgrad_impl(const ydl_conv_geom* g, int dtype, const void* dy, co
         a.ntaps = c.nt;
         for (int t = 0; t < c.nt; ++t) { a.dh[t] = c.dh[t]; a.dw[t] = c.dw[t]; a.wt[t] = c.wt[t]; }
         if (int e2 = set_extents(a, dtype)) return e2;
-        int e = dtype == YDL_F32 ? dispatch_igemm<float>(a, st, 1, nullptr, 0, path_out) : dispatch_igemm<bf16_t>(a, st, 1, nullptr, 0, path_out);
-        if (e) return e;
+        if (int e = run(a)) return e;
     }
     return 0;
 }
@@ -3460,9 +3348,9 @@ extern "C" int ydl_conv_dgrad(const ydl_conv_geom* g, int dtype, const void* dy,
 
 extern "C" int ydl_conv_dgrad_bnred_supported(const ydl_conv_geom* g, int dtype) {
     if (g == nullptr || dtype != YDL_BF16) return 0;
-    int path = -1;
-    if (conv_dgrad_impl(g, dtype, nullptr, nullptr, nullptr, 0, nullptr, &path, nullptr) != 0) return 0;
-    return path == 2 ? 1 : 0;
+    ConvPlan pl{};
+    if (conv_dgrad_impl(g, dtype, nullptr, nullptr, nullptr, 0, nullptr, &pl, nullptr) != 0) return 0;
+    return pl.family == CONV_RING && pl.has_bnred ? 1 : 0;
 }
 
 extern "C" int ydl_conv_dgrad_bnred(const ydl_conv_geom* g, int dtype, const void* dy, const void* wt, void* dx,
@@ -3727,7 +3615,6 @@ struct Wgrad2Args {
     int njt, nct;
     int ldw;                              // dW row stride (floats)
     float* slab;                          // deterministic mode: [splits][Cout][ntaps*Kc] partial sums, else NULL
-    int dbg;                              // timing experiments only (YDL_WG3_DBG): 1 no DMA, 2 no epilogue, 3 no MFMA/LDS reads
 };
 
 template <int TCO>
@@ -3980,7 +3867,6 @@ __global__ __launch_bounds__(256, 2) void wgrad3_kernel(const Wgrad2Args p) {
     const unsigned adv_wrap_h = (unsigned)(((p.Hi - p.Ho * p.s) * p.Wi) * p.ldx) * 2u;             // into the next image
     auto issue = [&](int p0, int buf) {
         const unsigned base = (unsigned)buf * (unsigned)STAGE;
-        if (p.dbg == 1) return;
 #pragma unroll
         for (int i = 0; i < YR; ++i) {
             const int m = p0 + yr + YRP * i;
@@ -4002,7 +3888,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3_kernel(const Wgrad2Args p) {
             }
             const int ih = __mul24(xho[i], p.s) + dh, iw = __mul24(xwo[i], p.s) + dw;      // (full-rate 24-bit multiplies: map sides < 2^21, conv_wgrad_impl)
             const bool ok = qv && m < pend && (unsigned)ih < (unsigned)p.Hi && (unsigned)iw < (unsigned)p.Wi;
-            lds_dma16(rsX, wave_x + base + (unsigned)i * 4096u, p.dbg == 5 ? (unsigned)(m * 256 + xq * 16) : (ok ? xoff[i] : 0xFFFFFFFFu));
+            lds_dma16(rsX, wave_x + base + (unsigned)i * 4096u, ok ? xoff[i] : 0xFFFFFFFFu);
             xwo[i] += adv_w; xho[i] += adv_h; xoff[i] += adv_step;
             if (xwo[i] >= p.Wo) { xwo[i] -= p.Wo; xho[i] += 1; xoff[i] += adv_wrap_w; }
             if (xho[i] >= p.Ho) { xho[i] -= p.Ho; xoff[i] += adv_wrap_h; }
@@ -4052,20 +3938,11 @@ __global__ __launch_bounds__(256, 2) void wgrad3_kernel(const Wgrad2Args p) {
     for (int p0 = pbeg; p0 < pend; p0 += SP) {
         wait_vm_barrier<L * (S - 2)>();
         issue(p0 + (S - 1) * SP, nxt);
-        if (p.dbg < 3) compute(buf);
+        compute(buf);
         buf = buf + 1 == S ? 0 : buf + 1;
         nxt = nxt + 1 == S ? 0 : nxt + 1;
     }
     wait_vm_barrier<0>();                          // the trailing DMAs land before the CTA (and its LDS allocation) goes away
-    if (p.dbg == 2 || p.dbg >= 4) {
-        float sink = 0.f;
-#pragma unroll
-        for (int a = 0; a < NA; ++a)
-#pragma unroll
-            for (int b = 0; b < NB; ++b) sink += acc[a][b][0] + acc[a][b][1] + acc[a][b][2] + acc[a][b][3];
-        if (sink == 123.456f) p.dW[0] = sink;
-        return;
-    }
     const size_t wrow = (size_t)p.ntaps * p.Kc;
 #pragma unroll
     for (int a = 0; a < NA; ++a)
@@ -4086,7 +3963,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3_kernel(const Wgrad2Args p) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-// wgrad3s: wgrad3 with the two jobs of a wave SPLIT over different waves (round 5).  Measured on wgrad3 (YDL_WG3_DBG): the DMA + barrier
+// wgrad3s: wgrad3 with the two jobs of a wave SPLIT over different waves (round 5).  Measured on wgrad3 (no-DMA / no-MFMA ablations): the DMA + barrier
 // loop alone takes 45-65 % of the kernel, the MFMA + fragment-read loop alone 40-55 %, and the whole is their SUM — a wave that is
 // held at its LDS-DMA instructions by a full memory pipeline cannot issue its MFMAs, and with one or two waves per SIMD nobody else can.
 // Here waves 0-3 only multiply (fragment reads + MFMAs, no vector-memory instruction in their loop) and NL extra LOADER waves only
@@ -4322,7 +4199,6 @@ struct PwbwArgs {
     const bf16_t* X; const bf16_t* dY; const bf16_t* Wt; bf16_t* dX; float* dW;
     int M, ldx, ldy, lddx, ldw, chunk;
     unsigned bytesX, bytesY, bytesDX, bytesWt;
-    int dbg;
 };
 #define PWBW_SP 32
 template <int S, bool ACC>
@@ -4458,7 +4334,6 @@ __global__ __launch_bounds__(512, 2) void pwbw_kernel(const PwbwArgs p) {
     int buf = 0, nxt = S - 1, k = 0;
     for (int p0 = pbeg; p0 < pend; p0 += SP, ++k) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // own staging writes / fragment reads of the previous stage are done
-        if (p.dbg == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         wait_vm_barrier<NWAIT>();
         // the previous stage's rows come out of LDS BEFORE the DMAs below overwrite the buffer its old-dx tile sits in (nxt)
         uint4 v, o = make_uint4(0u, 0u, 0u, 0u);
@@ -4525,7 +4400,6 @@ extern "C" int ydl_conv_bwd_pw(const ydl_conv_geom* g, int dtype, const void* x,
     a.bytesY = (unsigned)((unsigned long long)(M - 1) * g->ldy * 2ull + 256ull);
     a.bytesDX = (unsigned)((unsigned long long)(M - 1) * lddx * 2ull + 256ull);
     a.bytesWt = 128u * 256u;
-    a.dbg = getenv("YDL_PWBW_DBG") ? atoi(getenv("YDL_PWBW_DBG")) : 0;
     hipStream_t st = (hipStream_t)stream;
     ydl_note_kernel(1, accumulate ? "pwbw_kernel<128,128,acc>" : "pwbw_kernel<128,128>");
     ydl_note_kernel(2, "pwbw_kernel<128,128>");
@@ -4700,8 +4574,7 @@ __global__ __launch_bounds__(256, 2) void stemw_kernel(const StemwArgs p) {
 }
 static int g_stemw = 1;
 static bool stemw_ok(const ydl_conv_geom* g, int dtype) {
-    static const int env = getenv("YDL_STEMW") ? atoi(getenv("YDL_STEMW")) : 1;
-    return g_stemw && env && dtype == YDL_BF16 && g->k == 3 && g->s == 1 && g->p == 1 && g->Cin <= 16 && g->Cin > 8 && g->ldx == 16 &&
+    return g_stemw && dtype == YDL_BF16 && g->k == 3 && g->s == 1 && g->p == 1 && g->Cin <= 16 && g->Cin > 8 && g->ldx == 16 &&
            g->Cout == 64 && g->Hi == g->Ho && g->Wi == g->Wo && g->Wo % 64 == 0 && (long)g->N * g->Ho * g->Wo >= 65536;
 }
 static int launch_stemw(const ydl_conv_geom* g, const void* x, const void* dy, float* dw, int ldw, unsigned bx, unsigned by, hipStream_t st) {
@@ -4710,7 +4583,7 @@ static int launch_stemw(const ydl_conv_geom* g, const void* x, const void* dy, f
     a.X = (const bf16_t*)x; a.dY = (const bf16_t*)dy; a.dW = dw;
     a.H = g->Ho; a.W = g->Wo; a.segs = g->Wo / 64; a.ldy = g->ldy; a.ldw = ldw;
     a.nstages = g->N * g->Ho * a.segs;
-    static const int ctas = getenv("YDL_STEMW_CTAS") ? atoi(getenv("YDL_STEMW_CTAS")) : 512;
+    constexpr int ctas = 512;
     a.chunk = (a.nstages + ctas - 1) / ctas;
     const int grid = (a.nstages + a.chunk - 1) / a.chunk;
     a.bytesX = bx; a.bytesY = by;
@@ -4728,10 +4601,9 @@ struct WgradPlan { int kind;     // 0: wgrad_kernel<float>, 1: wgrad_kernel<bf16
                    int jtiles, ctiles, splits, chunk; };
 
 static int g_wgrad_tr = 1;
-static int g_wg3_loaders = -1;   // ydl_debug_set key 18: loader waves of the LDS-DMA weight-gradient kernel (-1: YDL_WG3_LOADERS or 4; 0 off)
+static int g_wg3_loaders = -1;   // ydl_debug_set key 18: loader waves of the LDS-DMA weight-gradient kernel (-1: the default, 4; 0 off)
 static int wg3_loaders() {
-    static const int env = getenv("YDL_WG3_LOADERS") ? atoi(getenv("YDL_WG3_LOADERS")) : 4;
-    const int v = g_wg3_loaders >= 0 ? g_wg3_loaders : env;
+    const int v = g_wg3_loaders >= 0 ? g_wg3_loaders : 4;
     return (v == 1 || v == 2 || v == 4) ? v : 0;
 }
 static int g_wgrad_dma = 1;      // 128-wide weight-gradient kernel: 1 = LDS-DMA feed (wgrad3_kernel), 0 = register-staged (wgrad2_kernel)
@@ -4742,21 +4614,18 @@ static WgradPlan wgrad_plan(const ydl_conv_geom* g, int dtype) {
     const int M = g->N * g->Ho * g->Wo;
     // measured on MI355X: the 128-wide pipelined kernel wins on the large-M layers (>= 160x160 at bs 16), the small
     // 64x64-tile kernel (8 CTAs/CU) wins where M is small and the grid of big tiles would be latency-bound
-    static const int wg2_min_m = getenv("YDL_WG2_MINM") ? atoi(getenv("YDL_WG2_MINM")) : 200000;
+    constexpr int wg2_min_m = 200000;
     // mid-size layers (M below the threshold): the 128-wide kernel sized to exactly ONE wave of CTAs (2 per CU x 256 CUs): its
     // time is very sensitive to the CTA count (atomic volume grows with it, and a second partial wave costs a full tile time) —
     // 128->256 k3s2 @80^2: 270 CTAs 154 us, 396 CTAs 117 us, 522 CTAs 154 us; the 64x64-tile kernel 148 us
-    // (3x3 layers only: 256->512 k3s2 @40^2 124 -> 93 us, 256->256 k3 @40^2 67 -> 63 us; the 1x1 layers lose 5-18 us with it.
-    //  YDL_WG2_ONEWAVE=0 off, 2 = every layer)
-    static const int onewave = getenv("YDL_WG2_ONEWAVE") ? atoi(getenv("YDL_WG2_ONEWAVE")) : 1;
+    // (3x3 layers only: 256->512 k3s2 @40^2 124 -> 93 us, 256->256 k3 @40^2 67 -> 63 us; the 1x1 layers lose 5-18 us with it)
+    constexpr long mid_slots = 512, mid_minfill = 410;
     bool mid = false;
-    if (dtype == YDL_BF16 && g_wgrad_tr == 1 && M < wg2_min_m && onewave && Kc % 8 == 0) {
+    if (dtype == YDL_BF16 && g_wgrad_tr == 1 && M < wg2_min_m && Kc % 8 == 0) {
         const int TCO = g->Cout > 64 ? 128 : 64;
         const long tiles = (long)((ntaps * Kc + 127) / 128) * ((g->Cout + TCO - 1) / TCO);
-        static const long slots = getenv("YDL_WG2_MIDSLOTS") ? atol(getenv("YDL_WG2_MIDSLOTS")) : 512;      // tuning
-        static const long minfill = getenv("YDL_WG2_MIDMIN") ? atol(getenv("YDL_WG2_MIDMIN")) : 410;
-        const long sp = slots / tiles;
-        mid = sp >= 1 && tiles * sp >= minfill && (M + 63) / 64 >= 4 * sp && (ntaps > 1 || onewave == 2);
+        const long sp = mid_slots / tiles;
+        mid = sp >= 1 && tiles * sp >= mid_minfill && (M + 63) / 64 >= 4 * sp && ntaps > 1;
     }
     // Round 5: with loader waves the 128-wide kernel also wins on the small-map layers that carry enough work (measured against the
     // 64 x 64-tile kernel, same box: 512->1024 k3s2 @20^2 134 -> 108 us, 2048->1024 @20^2 71 -> 52, 768->128 @80^2 59 -> 53, 512->512 @40^2
@@ -4770,8 +4639,7 @@ static WgradPlan wgrad_plan(const ydl_conv_geom* g, int dtype) {
         const long tiles = (long)pl.jtiles * pl.ctiles;
         const int stages = (M + 63) / 64;
         if (mid) {
-            static const long slots = getenv("YDL_WG2_MIDSLOTS") ? atol(getenv("YDL_WG2_MIDSLOTS")) : 512;
-            int splits = (int)(slots / tiles);
+            int splits = (int)(mid_slots / tiles);
             const int per = (stages + splits - 1) / splits;
             pl.chunk = per * 64;
             pl.splits = (M + pl.chunk - 1) / pl.chunk;
@@ -4781,9 +4649,8 @@ static WgradPlan wgrad_plan(const ydl_conv_geom* g, int dtype) {
         // sustain only ~1.3 TB/s chip-wide (measured), so the atomic volume T * tile_bytes is budgeted at ~20-30 % of the
         // layer's streaming/MFMA time: short 1x1 layers get 256 CTAs, long 3x3 layers up to 2048 (measured optimum per layer
         // on MI355X: 128->128 k1 @160: 256 CTAs 55 us vs 1024 CTAs 92 us; 128->64 k3 @160: 1024-1536 CTAs).
-        static const long forced = getenv("YDL_WG2_CTAS") ? atol(getenv("YDL_WG2_CTAS")) : 0;
-        long target2 = forced;
-        if (!target2) {
+        long target2;
+        {
             const double bytes_in = ((double)g->N * g->Hi * g->Wi * g->Cin + (double)M * g->Cout) * 2.0;
             const double flops = 2.0 * M * g->Cout * ntaps * Kc;
             const double d0 = bytes_in / 4.5e12 > flops / 450e12 ? bytes_in / 4.5e12 : flops / 450e12;
@@ -4807,16 +4674,12 @@ static WgradPlan wgrad_plan(const ydl_conv_geom* g, int dtype) {
     pl.jtiles = (ntaps * Kc + TE - 1) / TE;
     pl.ctiles = (g->Cout + TE - 1) / TE;
     // split-K over pixels.  Every split adds one f32 atomic pass over the dW tile (chip-wide atomic rate ~1.3 TB/s),
-    // so splits are bounded by an atomic-byte budget as well as by the CTA target (env knobs for tuning runs)
+    // so splits are bounded by the CTA target
     const long tiles = (long)pl.jtiles * pl.ctiles;
     const int stages = (M + WG_BKP - 1) / WG_BKP;
     // (measured: the short 1x1 layers are atomic-bound earlier: 1024 CTAs beat 2048 there, 3x3 layers are flat 2048-4096)
-    static const long forced_ctas = getenv("YDL_WG_CTAS") ? atol(getenv("YDL_WG_CTAS")) : 0;
-    const long target_ctas = forced_ctas ? forced_ctas : (ntaps == 1 ? 1024 : 2048);
-    static const long atomic_budget = getenv("YDL_WG_ATOMIC_MB") ? atol(getenv("YDL_WG_ATOMIC_MB")) * (1l << 20) : (1l << 40);
+    const long target_ctas = ntaps == 1 ? 1024 : 2048;
     int splits = (int)((target_ctas + tiles - 1) / tiles);
-    const long dw_bytes = (long)g->Cout * ntaps * Kc * 4;
-    if ((long)splits * dw_bytes > atomic_budget) splits = (int)(atomic_budget / dw_bytes);
     if (splits > stages / 4) splits = stages / 4;
     if (splits < 1) splits = 1;
     if (splits > 1024) splits = 1024;
@@ -4920,27 +4783,21 @@ static int conv_wgrad_impl(const ydl_conv_geom* g, int dtype, const void* x, con
         a.ldw = ldw; a.M = M; a.chunk = pl.chunk;
         a.bytesX = (unsigned)bx; a.bytesY = (unsigned)by; a.magicW = magicW; a.magicHW = magicHW;
         a.njt = pl.jtiles; a.nct = pl.ctiles; a.slab = slab;
-        static const int w3dbg = getenv("YDL_WG3_DBG") ? atoi(getenv("YDL_WG3_DBG")) : 0;
-        a.dbg = w3dbg;
-        static const int dma_env = getenv("YDL_WG3") ? atoi(getenv("YDL_WG3")) : 1;
-        if (g_wgrad_dma && dma_env) {
-            // ring shape (YDL_WG3_CFG, tuning): 0 = 64-pixel stages x 2, 1 = 32-pixel stages x 4 (same LDS, three stages in flight),
-            // 2 = 64-pixel stages x 3 (one CTA per CU for TCO = 128)
-            static const int cfg = getenv("YDL_WG3_CFG") ? atoi(getenv("YDL_WG3_CFG")) : 1;
-            ydl_note_kernel(2, pl.kind == 4 ? "wgrad3_kernel<128>" : "wgrad3_kernel<64>");
-            int e = 0;
-            // loader-wave form (wgrad3s_kernel): four loader waves per CTA by default (ydl_debug_set key 18 / YDL_WG3_LOADERS = 0: every
-            // wave loads and multiplies, wgrad3_kernel; 1, 2: fewer loader waves — measured slower than no split, 4: -12..-20 % on every layer)
-            const int loaders = wg3_loaders();
-            if (loaders) ydl_note_kernel(2, pl.kind == 4 ? "wgrad3s_kernel<128>" : "wgrad3s_kernel<64>");
-            // (stage shape, measured with four loaders: 32 pixels x 4 stages; 64 x 2 is equal within 3 % either way, 64 x 3 — one CTA per
+        if (g_wgrad_dma) {
+            // loader-wave form (wgrad3s_kernel): four loader waves per CTA by default (ydl_debug_set key 18 = 0: every wave loads and
+            // multiplies, wgrad3_kernel; 1, 2: fewer loader waves — measured slower than no split, 4: -12..-20 % on every layer)
+            // (ring shape, measured with four loaders: 32-pixel stages x 4; 64 x 2 is equal within 3 % either way, 64 x 3 — one CTA per
             //  CU — loses 10-20 % on the 3x3 layers)
-            if (loaders == 1 || loaders == 2 || loaders == 4) {
+            const int loaders = wg3_loaders();
+            int e = 0;
+            if (loaders) {
+                ydl_note_kernel(2, pl.kind == 4 ? "wgrad3s_kernel<128>" : "wgrad3s_kernel<64>");
                 if (pl.kind == 4) e = loaders == 1 ? launch_wgrad3s<128, 32, 4, 1>(a, grid, st) : (loaders == 2 ? launch_wgrad3s<128, 32, 4, 2>(a, grid, st) : launch_wgrad3s<128, 32, 4, 4>(a, grid, st));
                 else e = loaders == 1 ? launch_wgrad3s<64, 32, 4, 1>(a, grid, st) : (loaders == 2 ? launch_wgrad3s<64, 32, 4, 2>(a, grid, st) : launch_wgrad3s<64, 32, 4, 4>(a, grid, st));
-            } else
-            if (pl.kind == 4) e = cfg == 0 ? launch_wgrad3<128, 64, 2>(a, grid, st) : (cfg == 2 ? launch_wgrad3<128, 64, 3>(a, grid, st) : launch_wgrad3<128, 32, 4>(a, grid, st));
-            else e = cfg == 0 ? launch_wgrad3<64, 64, 2>(a, grid, st) : (cfg == 2 ? launch_wgrad3<64, 64, 3>(a, grid, st) : launch_wgrad3<64, 32, 4>(a, grid, st));
+            } else {
+                ydl_note_kernel(2, pl.kind == 4 ? "wgrad3_kernel<128>" : "wgrad3_kernel<64>");
+                e = pl.kind == 4 ? launch_wgrad3<128, 32, 4>(a, grid, st) : launch_wgrad3<64, 32, 4>(a, grid, st);
+            }
             if (e) return e;
         } else {
             const size_t smem = 4 * 64 * W2_ROWB;
