@@ -429,6 +429,23 @@ int ydl_attn_stem_table_fwd(const float* emb_mix, const float* emb_a, const floa
 int ydl_attn_stem_table_bwd(const float* emb_mix, const float* emb_a, const float* emb_b, const float* emb, const float* demb,
                             float* d_emb_mix, float* d_emb_a, float* d_emb_b, int m, int Cg, int ks, void* stream);
 
+/* ---- dense multi-head self-attention: the core of TransformerLayer / C3TR (models/common.py:79-112) ----------------------------
+ * NHWC rows of ld* elements in the compute dtype, f32 arithmetic on MFMA.  The tokens of sample n are its S consecutive rows
+ * [n*S, (n+1)*S); head h is the channel block [h*d, (h+1)*d) of a row.  q, k, v have their own row strides (channel blocks of one
+ * buffer are fine).  Per (sample, head):  P = softmax_j(scale * q_i . k_j),  out_i = sum_j P_ij v_j;  no mask, no dropout.
+ * lse: f32 [N][heads][S], max + log(sum) of each softmax row, kept for the backward (may be NULL in inference).
+ * S >= 1 is free; d must be a multiple of 8 with 8 <= d <= 128 (anything else is an error).  Nothing outside rows [0, N*S) and
+ * channels [0, heads*d) is read or written; rows that are not 16-byte aligned move element by element. */
+int ydl_mha_fwd(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse,
+                int N, int S, int heads, int d, float scale, void* stream);
+/* Backward in gather form (P recomputed from lse; one kernel per query tile writes dq, one per key tile writes dk and dv): no
+ * atomics, bitwise reproducible.  dq, dk, dv (rows of ldd elements) are written, or added into with accumulate != 0.
+ * ws: ydl_mha_bwd_ws_bytes(N, S, heads) bytes, receives delta = rowsum(dout * out) in f32. */
+int64_t ydl_mha_bwd_ws_bytes(int N, int S, int heads);
+int ydl_mha_bwd(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldo,
+                const float* lse, const void* dout, int lddo, void* dq, void* dk, void* dv, int ldd, int accumulate, float* ws,
+                int N, int S, int heads, int d, float scale, void* stream);
+
 /* ---- pieces of the DCNv3 module around the sampling op (models/ops_dcnv3/build/.../modules/dcnv3.py:50-136) ------------
  * depth-wise k x k convolution, stride 1, 'same' padding (the `dw_conv = Conv(c, c, k, g=c)` branch, :89);
  * w is the f32 master weight [C][k*k] (= nn.Conv2d(C, C, k, groups=C).weight, shape [C,1,k,k]); k in {1,3,5,7}. */

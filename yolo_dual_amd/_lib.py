@@ -119,6 +119,9 @@ SIGNATURES = {
                                 _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ydl_attn_stem_table_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ydl_attn_stem_table_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ydl_mha_fwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp]),
+    "ydl_mha_bwd_ws_bytes": (_i64, [_i, _i, _i]),
+    "ydl_mha_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _f, _vp]),
     "ydl_dwconv_fwd": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_dwconv_dgrad": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_dwconv_wgrad_ws_bytes": (_i64, [_i, _i]),

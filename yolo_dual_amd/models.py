@@ -25,7 +25,7 @@ import yaml
 
 from . import _lib as L
 from .modules import (GAM, AttentionConv, AttentionStem, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C2f_DCN, C3, C3_DCN, C3_DCNCommon, C3_DCNV3,
-                      C3Common, C3Ghost, C3k2, Concat, DWConv, GhostBottleneck, GhostConv,
+                      C3Common, C3Ghost, C3k2, C3TR, Concat, DWConv, GhostBottleneck, GhostConv, TransformerBlock,
                       Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region)
 from .tape import Tape, Var
 
@@ -526,12 +526,12 @@ def make_divisible(x, divisor):
 _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": SPPF, "Concat": Concat,
                 "nn.Upsample": Upsample, "Upsample": Upsample, "C3_DCNV3": C3_DCNV3, "Bottleneck_DCNV3": Bottleneck_DCNV3,
                 "AttentionConv": AttentionConv, "AttentionStem": AttentionStem, "DWConv": DWConv, "GhostConv": GhostConv,
-                "GhostBottleneck": GhostBottleneck, "C3Ghost": C3Ghost}
+                "GhostBottleneck": GhostBottleneck, "C3Ghost": C3Ghost, "C3TR": C3TR, "TransformerBlock": TransformerBlock}
 
 
 def parse_model(d: dict, ch: List[int], deformable: bool = False):
     """models/yolo.py:299-382 for the block set of this path: resolves module names, applies depth/width gains
-    (``n = max(round(n*gd), 1)``, ``c2 = make_divisible(c2*gw, 8)``), inserts ``n`` for C3 (AttentionConv / AttentionStem get none:
+    (``n = max(round(n*gd), 1)``, ``c2 = make_divisible(c2*gw, 8)``), inserts ``n`` for C3 and C3TR (AttentionConv / AttentionStem get none:
     n > 1 is a Sequential of identical constructions, models/yolo.py:318-329,369), and tags every layer
     with ``.i .f .type .np``.  Returns (nn.Sequential, sorted save-list).  ``deformable``: resolve ``C3_DCN`` to models/common.py's
     DCNv2 block (C3_DCNCommon, n inserted like C3: models/yolo.py:321,327)."""
@@ -546,16 +546,18 @@ def parse_model(d: dict, ch: List[int], deformable: bool = False):
         args = [None if a == "None" else a for a in args]
         n = n_ = max(round(n * gd), 1) if n > 1 else n
         if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3, C3_DCNCommon, AttentionConv, AttentionStem,
-                   DWConv, GhostConv, GhostBottleneck, C3Ghost):
+                   DWConv, GhostConv, GhostBottleneck, C3Ghost, C3TR):
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)
             args = [c1, c2, *args[1:]]
-            if cls in (C3Common, C3_DCNV3, C3_DCNCommon, C3Ghost):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
+            if cls in (C3Common, C3_DCNV3, C3_DCNCommon, C3Ghost, C3TR):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
                 args.insert(2, n)
                 n = 1
         elif cls is Concat:
             c2 = sum(ch[x] for x in f)
+        elif cls is TransformerBlock:                    # not in the reference's channel-scaling set: args as written, c2 = ch[f]
+            c2 = ch[f]
         elif cls is Upsample:
             c2 = ch[f]
             args = [args[0], args[1], args[2] if len(args) > 2 else "nearest"]

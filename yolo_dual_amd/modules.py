@@ -1266,23 +1266,19 @@ class SegmentHead(YdlModule):
 # ----------------------------------------------------------------------------------------------------------
 # DCNv3 module and its YOLO wiring (models/ops_dcnv3/build/.../modules/dcnv3.py:50-136, "common and yolo.py":2-38)
 # ----------------------------------------------------------------------------------------------------------
-class Linear(YdlModule):
-    """``nn.Linear`` over the channel dimension of an NHWC tensor (state_dict: weight [out, in], bias [out]) = a 1x1
-    convolution with bias on the implicit-GEMM kernels; the bias gradient is a deterministic per-channel sum."""
-
-    def __init__(self, in_features: int, out_features: int, bias: bool = True):
-        super().__init__()
-        self.in_features, self.out_features = in_features, out_features
-        self.weight = nn.Parameter(torch.empty(out_features, in_features))
-        self.bias = nn.Parameter(torch.empty(out_features)) if bias else None
-        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        if bias:
-            bound = 1 / math.sqrt(in_features)
-            nn.init.uniform_(self.bias, -bound, bound)
-        self._wcache = {}
+class _LinearOps:
+    """what Tape.linear needs from a weight holder, written against ``self.weight`` [rows, in], ``self.bias`` [rows] or None and
+    ``self._rows``: None (the whole parameters: Linear) or the slice of rows this holder stands for (one Q / K / V block of
+    ``in_proj_weight`` / ``in_proj_bias``).  ``final``: this holder's backward is the last launch that writes the parameters'
+    gradients, so only it reports them to ``config.mark_touched`` (the data-parallel hook may start the all-reduce from there)."""
+    _rows = None
+    final = True
 
     def _wkey(self, tape: Tape):
         return (tape.dname, self.weight.data_ptr(), self.weight._version, config.weight_epoch())
+
+    def _sel(self, t: torch.Tensor) -> torch.Tensor:
+        return t if self._rows is None else t[self._rows]
 
     def compute_weights(self, tape: Tape):
         key = self._wkey(tape)
@@ -1295,7 +1291,7 @@ class Linear(YdlModule):
             master = self.weight.detach()
             if not master.is_contiguous():
                 master = master.contiguous()
-            L.call("ydl_weight_prep", tape.dt, _p(master), _p(c["w"]), _p(c["wt"]), self.out_features, 1, self.in_features,
+            L.call("ydl_weight_prep", tape.dt, _p(self._sel(master)), _p(c["w"]), _p(c["wt"]), self.out_features, 1, self.in_features,
                    _stream())
             c["key"] = key
         return c["w"], c["wt"]
@@ -1310,15 +1306,16 @@ class Linear(YdlModule):
             c["bpad"] = torch.zeros(cp, dtype=torch.float32, device=device)
             c["bkey"] = None
         if c.get("bkey") != key:
-            L.call("ydl_copy2d", L.YDL_F32, _p(self.bias.detach()), self.out_features, _p(c["bpad"]), cp, 1, self.out_features, 0,
-                   _stream())
+            L.call("ydl_copy2d", L.YDL_F32, _p(self._sel(self.bias.detach())), self.out_features, _p(c["bpad"]), cp, 1, self.out_features,
+                   0, _stream())
             c["bkey"] = key
         return c["ones"], c["bpad"]
 
     def _grad_of(self, p: nn.Parameter) -> torch.Tensor:
+        """(this holder's rows of) the parameter's gradient"""
         if p.grad is None:
             p.grad = torch.zeros_like(p)
-        return p.grad
+        return self._sel(p.grad)
 
     def wgrad(self, tape: Tape, gp, x: Var, dy: Var, st) -> None:
         if not self.weight.requires_grad:          # frozen: no gradient kernel, never marked touched
@@ -1331,7 +1328,24 @@ class Linear(YdlModule):
             tmp = zero_(torch.empty((self.out_features, 1, cin_p), dtype=torch.float32, device=g.device), st)
             _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(tmp), st)
             L.call("ydl_wgrad_unpad", _p(tmp), _p(g), self.out_features, 1, self.in_features, 1, st)
-        config.mark_touched(self.weight)
+        if self.final:
+            config.mark_touched(self.weight)
+
+
+class Linear(_LinearOps, YdlModule):
+    """``nn.Linear`` over the channel dimension of an NHWC tensor (state_dict: weight [out, in], bias [out]) = a 1x1
+    convolution with bias on the implicit-GEMM kernels; the bias gradient is a deterministic per-channel sum."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True):
+        super().__init__()
+        self.in_features, self.out_features = in_features, out_features
+        self.weight = nn.Parameter(torch.empty(out_features, in_features))
+        self.bias = nn.Parameter(torch.empty(out_features)) if bias else None
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if bias:
+            bound = 1 / math.sqrt(in_features)
+            nn.init.uniform_(self.bias, -bound, bound)
+        self._wcache = {}
 
     def _fwd(self, tape: Tape, x: Var) -> Var:
         return tape.linear(x, self)
@@ -1590,3 +1604,128 @@ class AttentionStem(_LocalAttention):
         for p in (mix, ea, eb):
             if p.requires_grad:
                 config.mark_touched(p)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# C3TR / TransformerBlock / TransformerLayer (models/common.py:79-112, :183-188): dense multi-head self-attention over the H*W
+# positions of a sample (csrc/mha.hip) between Linear layers on the implicit-GEMM kernels
+# ----------------------------------------------------------------------------------------------------------
+MHA_HEAD_DIM_STEP, MHA_HEAD_DIM_MAX = 8, 128          # ydl_mha_fwd: d a multiple of 8, 8 <= d <= 128
+
+
+class _InProj(_LinearOps):
+    """rows [i*c, (i+1)*c) of ``ma.in_proj_weight`` / ``ma.in_proj_bias`` seen as one Linear by Tape.linear: the compute-layout
+    copy is derived from the row block, and the weight and bias gradients are written into the matching contiguous slices of the
+    two parameters' gradients.  TransformerLayer runs the blocks in the order Q, K, V, so the backward reaches block 0 last: it
+    alone is ``final``."""
+
+    def __init__(self, ma: "_MultiheadAttention", i: int):
+        self.ma, self.i = ma, i
+        self.in_features = self.out_features = ma.embed_dim
+        self._rows = slice(i * ma.embed_dim, (i + 1) * ma.embed_dim)
+        self.final = i == 0
+        self._wcache = {}
+
+    @property
+    def weight(self) -> nn.Parameter:
+        return self.ma.in_proj_weight
+
+    @property
+    def bias(self) -> nn.Parameter:
+        return self.ma.in_proj_bias
+
+
+class _MultiheadAttention(nn.Module):
+    """parameter holder with ``nn.MultiheadAttention``'s names, shapes and initialisation: ``in_proj_weight`` [3c, c] (xavier
+    uniform), ``in_proj_bias`` [3c] (zero), ``out_proj`` = Linear(c, c) with a zero bias.  The arithmetic is Tape.mha."""
+
+    def __init__(self, embed_dim: int, num_heads: int):
+        super().__init__()
+        self.embed_dim, self.num_heads = embed_dim, num_heads
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
+        self.out_proj = Linear(embed_dim, embed_dim)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        nn.init.constant_(self.out_proj.bias, 0.0)
+        self.__dict__["_blocks"] = [_InProj(self, i) for i in range(3)]
+
+    def blocks(self):
+        return self.__dict__["_blocks"]
+
+    def forward(self, *a, **kw):  # pragma: no cover - run through TransformerLayer
+        raise RuntimeError("_MultiheadAttention holds parameters only; call the TransformerLayer")
+
+
+class TransformerLayer(YdlModule):
+    """models/common.py:79-93: x1 = out_proj(MHA(in_q(q x), in_k(k x), in_v(v x))) + x;  out = fc2(fc1(x1)) + x1 (no LayerNorm).
+    The tokens of a sample are its H*W positions."""
+
+    def __init__(self, c, num_heads):
+        super().__init__()
+        if c % num_heads:
+            raise AssertionError("embed_dim must be divisible by num_heads")
+        d = c // num_heads
+        if d % MHA_HEAD_DIM_STEP or not MHA_HEAD_DIM_STEP <= d <= MHA_HEAD_DIM_MAX:
+            raise NotImplementedError(f"TransformerLayer: head dimension {d} (c={c}, num_heads={num_heads}) is not implemented: the "
+                                      f"HIP attention kernels serve multiples of {MHA_HEAD_DIM_STEP} between {MHA_HEAD_DIM_STEP} and "
+                                      f"{MHA_HEAD_DIM_MAX}")
+        self.c, self.num_heads = c, num_heads
+        self.q = Linear(c, c, bias=False)
+        self.k = Linear(c, c, bias=False)
+        self.v = Linear(c, c, bias=False)
+        self.ma = _MultiheadAttention(c, num_heads)
+        self.fc1 = Linear(c, c, bias=False)
+        self.fc2 = Linear(c, c, bias=False)
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        if x.C != self.c:
+            raise RuntimeError(f"TransformerLayer input channel mismatch: got {x.C}, weights expect {self.c}")
+        x = tape._flat(x)
+        c = self.c
+        t = tape.new(x.N, 3 * c, x.H, x.W)           # [pix][q x | k x | v x]
+        qkv = tape.new(x.N, 3 * c, x.H, x.W)         # [pix][Q | K | V]
+        for i, (lin, blk) in enumerate(zip((self.q, self.k, self.v), self.ma.blocks())):
+            a = tape.linear(x, lin, out=t.slice(i * c, (i + 1) * c))
+            tape.linear(a, blk, out=qkv.slice(i * c, (i + 1) * c))
+        att = tape.mha(qkv, self.num_heads)
+        x1 = tape.add(tape.linear(att, self.ma.out_proj), x)
+        return tape.add(tape.linear(tape.linear(x1, self.fc1), self.fc2), x1, out=out)
+
+
+class TransformerBlock(YdlModule):
+    """models/common.py:96-112: optional Conv(c1, c2), the learnable position embedding p + linear(p), then ``num_layers``
+    TransformerLayers."""
+
+    def __init__(self, c1, c2, num_heads, num_layers):
+        super().__init__()
+        self.conv = None
+        if c1 != c2:
+            self.conv = Conv(c1, c2)
+        self.linear = Linear(c2, c2)
+        self.tr = nn.Sequential(*(TransformerLayer(c2, num_heads) for _ in range(num_layers)))
+        self.c2 = c2
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        if self.conv is not None:
+            x = self.conv._fwd(tape, x)
+        n = len(self.tr)
+        x = tape.add(x, tape.linear(x, self.linear), out=out if n == 0 else None)
+        for i, layer in enumerate(self.tr):
+            x = layer._fwd(tape, x, out=out if i == n - 1 else None)
+        return x
+
+
+class C3TR(C3Common):
+    """models/common.py:183-188: C3 whose ``m`` is one TransformerBlock(c_, c_, 4, n)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = TransformerBlock(self.c_, self.c_, 4, n)
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        c_ = self.c_
+        cat = tape.new(x.N, 2 * c_, x.H, x.W)
+        left, right = cat.slice(0, c_), cat.slice(c_, 2 * c_)
+        self.m._fwd(tape, self.cv1._fwd(tape, x), out=left)
+        self.cv2._fwd(tape, x, out=right)
+        return self.cv3._fwd(tape, cat)

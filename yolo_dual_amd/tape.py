@@ -1129,15 +1129,19 @@ class Tape:
             x = self.copy(x, self.new(x.N, x.C, x.H, x.W, need=x.need, f32=(x.dt == L.YDL_F32)))
         return x
 
-    def linear(self, x: Var, lin) -> Var:
+    def linear(self, x: Var, lin, out: Optional[Var] = None) -> Var:
         """nn.Linear on the channel dimension of an NHWC tensor (modules/dcnv3.py:92-100) = 1x1 convolution + bias.
-        ``lin`` holds weight [out, in] (KRSC of a 1x1 conv is the same memory) and bias [out]."""
+        ``lin`` holds weight [out, in] (KRSC of a 1x1 conv is the same memory) and bias [out].  ``out`` may be an 8-aligned channel
+        slice of a wider buffer (the Q | K | V blocks of Tape.mha)."""
         x = self._flat(x)
         Cin, Cout = lin.in_features, lin.out_features
         if x.C != Cin:
             raise RuntimeError(f"Linear input channel mismatch: got {x.C}, weight expects {Cin}")
         w, wt = lin.compute_weights(self)
-        out = self.new(x.N, Cout, x.H, x.W)
+        if out is None:
+            out = self.new(x.N, Cout, x.H, x.W)
+        elif (out.N, out.C, out.H, out.W) != (x.N, Cout, x.H, x.W) or not out.aligned():
+            raise RuntimeError("linear: the output slice has the wrong shape or is not 16-byte aligned")
         geom = L.ConvGeom(x.N, x.H, x.W, Cin, x.H, x.W, Cout, 1, 1, 0, x.ld, out.ld, 0)
         gp = ctypes.byref(geom)
         st = _stream()
@@ -1158,8 +1162,9 @@ class Tape:
                     gb = lin._grad_of(lin.bias)
                     ws = torch.empty(L.lib().ydl_channel_sum_ws_bytes(Cout) // 4, dtype=torch.float32, device=self.device)
                     L.call("ydl_channel_sum", self.dt, _p(dout), out.ld, _p(gb), _p(ws), x.npix, Cout, 1, st2)
-                    from . import config as _cfg
-                    _cfg.mark_touched(lin.bias)
+                    if lin.final:            # a row block of a shared parameter reports it once, after its last writer
+                        from . import config as _cfg
+                        _cfg.mark_touched(lin.bias)
                 lin.wgrad(self, gp, x, dov, st2)
                 if x.need:
                     gx, acc = self.grad_target(x)
@@ -1531,6 +1536,41 @@ class Tape:
                         gx, acc = self.grad_target(x)
                         L.call("ydl_conv_dgrad", gp, self.dt, dblk[i], _p(wts[i]), _p(gx), acc, st2)
                 self._keep.extend((geom, qkv, dqkv, ws, demb))
+            self.bw.append(bw)
+        return out
+
+    def mha(self, qkv: Var, heads: int) -> Var:
+        """dense multi-head self-attention over the H*W positions of each sample (nn.MultiheadAttention's core, no mask, no
+        dropout): ``qkv`` is ONE buffer of rows [pix][Q | K | V] whose three channel blocks were written by Tape.linear; head h is
+        channels [h*d, (h+1)*d) of a block, scale = d^-0.5.  ydl_mha_fwd keeps the f32 log-sum of every softmax row; the backward
+        (ydl_mha_bwd, gather form, bitwise reproducible) writes dQ | dK | dV into the gradient of ``qkv`` in the same layout."""
+        if qkv.parent is not None or qkv.lazy or qkv.virtual or qkv.C % 3:
+            raise RuntimeError("mha: qkv must be a whole [pix][Q | K | V] buffer")
+        C = qkv.C // 3
+        d = C // heads
+        if C % heads or d % 8 or not 8 <= d <= 128:
+            raise NotImplementedError(f"mha: head dimension {C}/{heads} is not implemented (multiples of 8 between 8 and 128)")
+        N, S = qkv.N, qkv.H * qkv.W
+        es = 4 if self.dt == L.YDL_F32 else 2
+        scale = float(d) ** -0.5
+        base = qkv.t.data_ptr()
+        blk = [ctypes.c_void_p(base + i * C * es) for i in range(3)]
+        out = self.new(N, C, qkv.H, qkv.W)
+        lse = torch.empty(N * heads * S, dtype=torch.float32, device=self.device) if self.record else None
+        L.call("ydl_mha_fwd", self.dt, blk[0], qkv.ld, blk[1], qkv.ld, blk[2], qkv.ld, _p(out.t), out.ld, _p(lse),
+               N, S, heads, d, scale, _stream())
+        if self.record and qkv.need:
+            def bw():
+                if not out.is_set():
+                    return
+                st2 = _stream()
+                ws = torch.empty(L.lib().ydl_mha_bwd_ws_bytes(N, S, heads) // 4, dtype=torch.float32, device=self.device)
+                g, acc = self.grad_target(qkv)
+                gbase = g.data_ptr()
+                dblk = [ctypes.c_void_p(gbase + i * C * es) for i in range(3)]
+                L.call("ydl_mha_bwd", self.dt, blk[0], qkv.ld, blk[1], qkv.ld, blk[2], qkv.ld, _p(out.t), out.ld, _p(lse),
+                       _p(self._gbuf(out)), out.ld, dblk[0], dblk[1], dblk[2], qkv.ld, acc, _p(ws), N, S, heads, d, scale, st2)
+                self._keep.extend((ws, lse))
             self.bw.append(bw)
         return out
 
