@@ -180,6 +180,146 @@ def _launch_wgrad(tape: Tape, gp, x_ptr, dy_ptr, dw_ptr, st, fuse=None) -> bool:
     return False
 
 
+class _GemmWeights:
+    """What the tape needs from the holder of an implicit-GEMM weight, once: the compute-layout copies of the f32 master, the padded
+    bias row, the gradient storage and the weight-gradient launch.  The master is seen as a contiguous [rows][taps][cin] f32 array
+    (KRSC: an OIHW parameter in channels_last storage, or a [rows, cin] matrix).  A holder supplies
+
+      ``_wparam``       the weight parameter (default ``self.weight``; ``self.bias`` is the bias parameter or None)
+      ``_gemm_dims()``  (rows, taps, cin)
+      ``_rows``         None, or the slice of the parameters' rows this holder stands for (one Q / K / V block of ``in_proj_weight``)
+      ``final``         this holder's backward is the last launch writing its parameters' gradients, so only it reports them to
+                        ``config.mark_touched`` (the data-parallel hook may start the all-reduce from there)
+      ``_place_grad``   None, or a method that adds a padded gradient into a gradient torch laid out some other way (cold path)
+
+    Holders with a BatchNorm ``self.bn`` behind the GEMM (Conv, _FusedPair, _DeformGemm) also get its coefficient and gradient rows."""
+    _rows = None
+    final = True
+    _place_grad = None
+    _wname = "Conv2d"
+    k, s, p = 1, 1, 0
+
+    @property
+    def _wparam(self) -> nn.Parameter:
+        return self.weight
+
+    def _krsc(self, t: torch.Tensor) -> torch.Tensor:
+        """[rows][taps][cin] view of the weight or of its gradient (no copy)"""
+        if t.dim() == 4:
+            return t.permute(0, 2, 3, 1)
+        return t if self._rows is None else t[self._rows]
+
+    def _master_krsc(self) -> torch.Tensor:
+        p = self._wparam
+        w = self._krsc(p.detach())
+        if not w.is_contiguous():
+            if p.dim() == 4:                           # someone re-assigned .data in OIHW order: re-home it
+                p.data = p.data.contiguous(memory_format=torch.channels_last)
+                w = self._krsc(p.detach())
+            if not w.is_contiguous():
+                w = w.contiguous()
+        return w
+
+    def _wkey(self, tape: Tape):
+        wp = self._wparam
+        return (tape.dname, wp.data_ptr(), wp._version, config.weight_epoch())
+
+    def _wbuffers(self, tape: Tape, master: torch.Tensor):
+        rows, taps, cin = self._gemm_dims()
+        dev = master.device
+        w = self._wcache.get("w")
+        if w is None or self._wcache.get("dname") != tape.dname or w.device != dev:
+            w = torch.empty((rows, taps, round_up(cin, 8)), dtype=tape.tdt, device=dev)
+            wt = torch.empty((cin, taps, round_up(rows, 8)), dtype=tape.tdt, device=dev)
+            self._wcache.update(w=w, wt=wt, dname=tape.dname, key=None)
+        return self._wcache["w"], self._wcache["wt"]
+
+    def compute_weights(self, tape: Tape):
+        """compute-dtype copies w [rows][taps][cin_p] / wt [cin][taps][rows_p] of the f32 master weight, refreshed when the
+        parameter changed (torch version counter, or the epoch the fused optimizer bumps)"""
+        key = self._wkey(tape)
+        if self._wcache.get("key") == key:
+            return self._wcache["w"], self._wcache["wt"]
+        master = self._master_krsc()
+        w, wt = self._wbuffers(tape, master)
+        L.call("ydl_weight_prep", tape.dt, _p(master), _p(w), _p(wt), *self._gemm_dims(), _stream())
+        self._wcache["key"] = key
+        return w, wt
+
+    def bias_coeffs(self, device):
+        """(ones, bias) padded to a multiple of 8 channels for ydl_bn_act_fwd (scale = 1, shift = bias)"""
+        rows = self._gemm_dims()[0]
+        cp = round_up(rows, 8)
+        key = (self.bias.data_ptr(), self.bias._version, config.weight_epoch())
+        c = self._wcache
+        if c.get("ones") is None or c["ones"].device != device:       # created once (a refresh below only rewrites bpad's contents)
+            c["ones"] = torch.ones(cp, dtype=torch.float32, device=device)
+            c["bpad"] = torch.zeros(cp, dtype=torch.float32, device=device)
+            c["bkey"] = None
+        if c.get("bkey") != key:
+            L.call("ydl_copy2d", L.YDL_F32, _p(self._krsc(self.bias.detach())), rows, _p(c["bpad"]), cp, 1, rows, 0, _stream())
+            c["bkey"] = key
+        return c["ones"], c["bpad"]
+
+    def _grad_of(self, p: nn.Parameter) -> torch.Tensor:
+        """(this holder's rows of) the parameter's gradient"""
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)       # preserves the KRSC (channels_last) strides of a convolution weight
+        return p.grad if self._rows is None else p.grad[self._rows]
+
+    def wgrad(self, tape: Tape, gp, x: Var, dy: Var, st, col0: int = 0, final: bool = True, fuse=None) -> bool:
+        """``col0``: first input channel of the block this call covers (gp.ldw = total padded Cin then); ``final``: the
+        last launch writing this parameter's gradient (only then may the data-parallel hook see it); ``fuse``: see
+        ``_launch_wgrad`` — returns True when the input gradient was produced by the same launch"""
+        p = self._wparam
+        if not p.requires_grad:                    # frozen: no gradient kernel, never marked touched
+            return False
+        rows, taps, cin = self._gemm_dims()
+        self._grad_of(p)                           # allocates on first use
+        gk = self._krsc(p.grad)
+        if not gk.is_contiguous() and self._place_grad is None:
+            raise RuntimeError(f"{self._wname} weight gradient must be KRSC-contiguous")
+        cin_p = round_up(cin, 8)
+        done = False
+        if cin_p == cin and gk.is_contiguous():
+            done = _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), ctypes.c_void_p(gk.data_ptr() + 4 * col0), st, fuse)
+        else:
+            assert col0 == 0 and final
+            tmp = zero_(torch.empty((rows, taps, cin_p), dtype=torch.float32, device=gk.device), st)
+            _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(tmp), st)
+            if gk.is_contiguous():
+                L.call("ydl_wgrad_unpad", _p(tmp), _p(gk), rows, taps, cin, 1, st)
+            else:
+                self._place_grad(p.grad, tmp)
+        if final and self.final:
+            config.mark_touched(p)
+        return done
+
+    # -- the BatchNorm behind the GEMM ---------------------------------------------------------------------
+    def mark_step(self, tape: Tape) -> None:
+        if tape.train:
+            self.bn._nbt_pending += 1
+
+    def coeffs(self, device):
+        cp = round_up(self._gemm_dims()[0], 8)
+        buf = torch.empty((4, cp), dtype=torch.float32, device=device)
+        if cp != self._gemm_dims()[0]:
+            zero_(buf)
+        return {"mean": buf[0], "invstd": buf[1], "scale": buf[2], "shift": buf[3]}
+
+    def grad_slot(self, tape: Tape, which: str):
+        """gradient storage of gamma / beta; ``touch_bn`` must be called AFTER the kernel writing it is enqueued (the
+        data-parallel hook may launch the bucket's all-reduce from inside mark_touched)"""
+        p = self.bn.weight if which == "gamma" else self.bn.bias
+        return self._grad_of(p), 1
+
+    def touch_bn(self) -> None:
+        if self.bn.weight.requires_grad:
+            config.mark_touched(self.bn.weight)
+        if self.bn.bias.requires_grad:
+            config.mark_touched(self.bn.bias)
+
+
 class _BNHolder(nn.BatchNorm2d):
     """Parameter/buffer holder with nn.BatchNorm2d's state_dict layout.  ``num_batches_tracked`` is advanced on the
     host and flushed into the buffer whenever the state is read, so the hot loop launches no extra kernel."""
@@ -212,7 +352,7 @@ def _act_code(act) -> int:
     raise NotImplementedError(f"activation {act!r} is not supported by the HIP path (SiLU/ReLU/Identity)")
 
 
-class Conv(YdlModule):
+class Conv(_GemmWeights, YdlModule):
     """``Conv(c1, c2, k=1, s=1, p=None, g=1, act=True)`` (seg scripts) and
     ``Conv(c1, c2, k=1, s=1, p=None, g=1, d=1, act=True)`` (models/common.py): the 7th positional argument is taken
     as ``act`` when it is a bool/Module and as the dilation when it is an int > 0 that is not a bool."""
@@ -243,73 +383,14 @@ class Conv(YdlModule):
         self.act = nn.SiLU() if act is True else (act if isinstance(act, nn.Module) else nn.Identity())
         self.act_code = _act_code(self.act)
         self._wcache = {}
-        # depth-wise layers: the DCNv3 dw_conv branch keeps Tape.dwconv_bn_act (stride 1, separate statistics pass); the Ghost
-        # blocks (DWConv, GhostConv.cv2) and every stride-2 layer run Tape.dw_bn_act (statistics from the convolution launch)
-        self.dw_fused_stats = self.depthwise and s != 1
 
-    # -- parameters in compute layout -------------------------------------------------------------------
-    def _master_krsc(self) -> torch.Tensor:
-        w = self.conv.weight.detach().permute(0, 2, 3, 1)
-        if not w.is_contiguous():                      # someone re-assigned .data in OIHW order: re-home it
-            self.conv.weight.data = self.conv.weight.data.contiguous(memory_format=torch.channels_last)
-            w = self.conv.weight.detach().permute(0, 2, 3, 1)
-            if not w.is_contiguous():
-                w = w.contiguous()
-        return w
+    # -- parameters in compute layout: _GemmWeights over the KRSC master ``conv.weight`` ---------------------
+    @property
+    def _wparam(self) -> nn.Parameter:
+        return self.conv.weight
 
-    def _wkey(self, tape: Tape):
-        wp = self.conv.weight
-        return (tape.dname, wp.data_ptr(), wp._version, config.weight_epoch())
-
-    def mark_step(self, tape: Tape) -> None:
-        if tape.train:
-            self.bn._nbt_pending += 1
-
-    def _wbuffers(self, tape: Tape, master: torch.Tensor):
-        kk = self.k * self.k
-        dev = master.device
-        w = self._wcache.get("w")
-        if w is None or self._wcache.get("dname") != tape.dname or w.device != dev:
-            w = torch.empty((self.c2, kk, round_up(self.c1, 8)), dtype=tape.tdt, device=dev)
-            wt = torch.empty((self.c1, kk, round_up(self.c2, 8)), dtype=tape.tdt, device=dev)
-            self._wcache.update(w=w, wt=wt, dname=tape.dname, key=None)
-        return self._wcache["w"], self._wcache["wt"]
-
-    def compute_weights(self, tape: Tape):
-        """compute-dtype copies w [Cout][taps][Cin_p] / wt [Cin][taps][Cout_p] of the f32 KRSC master weight, refreshed
-        when the parameter changed (torch version counter, or the epoch the fused optimizer bumps)"""
-        key = self._wkey(tape)
-        if self._wcache.get("key") == key:
-            return self._wcache["w"], self._wcache["wt"]
-        master = self._master_krsc()
-        w, wt = self._wbuffers(tape, master)
-        L.call("ydl_weight_prep", tape.dt, _p(master), _p(w), _p(wt), self.c2, self.k * self.k, self.c1, _stream())
-        self._wcache["key"] = key
-        return w, wt
-
-    def coeffs(self, device):
-        cp = round_up(self.c2, 8)
-        buf = torch.empty((4, cp), dtype=torch.float32, device=device)
-        if cp != self.c2:
-            zero_(buf)
-        return {"mean": buf[0], "invstd": buf[1], "scale": buf[2], "shift": buf[3]}
-
-    def _grad_of(self, p: nn.Parameter) -> torch.Tensor:
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)       # preserves the KRSC (channels_last) strides of the weight
-        return p.grad
-
-    def grad_slot(self, tape: Tape, which: str):
-        """gradient storage of gamma / beta; ``touch_bn`` must be called AFTER the kernel writing it is enqueued (the
-        data-parallel hook may launch the bucket's all-reduce from inside mark_touched)"""
-        p = self.bn.weight if which == "gamma" else self.bn.bias
-        return self._grad_of(p), 1
-
-    def touch_bn(self) -> None:
-        if self.bn.weight.requires_grad:
-            config.mark_touched(self.bn.weight)
-        if self.bn.bias.requires_grad:
-            config.mark_touched(self.bn.bias)
+    def _gemm_dims(self):
+        return self.c2, self.k * self.k, self.c1
 
     def trainable(self):
         """(weight, BN weight, BN bias) ``requires_grad`` flags: a frozen parameter (``--freeze``, seg_diceloss_yolov5.py:955-959)
@@ -321,31 +402,10 @@ class Conv(YdlModule):
         """the weight gradient can be written per input-channel block (``wgrad(col0=...)``): dense KRSC storage"""
         return self.c1 % 8 == 0 and self.conv.weight.detach().permute(0, 2, 3, 1).is_contiguous()
 
-    def wgrad(self, tape: Tape, gp, x: Var, dy: Var, st, col0: int = 0, final: bool = True, fuse=None) -> bool:
-        """``col0``: first input channel of the block this call covers (gp.ldw = total padded Cin then); ``final``: the
-        last launch writing this parameter's gradient (only then may the data-parallel hook see it); ``fuse``: see
-        ``_launch_wgrad`` — returns True when the input gradient was produced by the same launch"""
-        p = self.conv.weight
-        g = self._grad_of(p)
-        gk = g.permute(0, 2, 3, 1)
-        kk = self.k * self.k
-        cin_p = round_up(self.c1, 8)
-        if cin_p == self.c1 and gk.is_contiguous():
-            done = _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), ctypes.c_void_p(gk.data_ptr() + 4 * col0), st, fuse)
-            if final:
-                config.mark_touched(p)
-            return done
-        assert col0 == 0 and final
-        tmp = zero_(torch.empty((self.c2, kk, cin_p), dtype=torch.float32, device=g.device), st)
-        _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(tmp), st)
-        if gk.is_contiguous():
-            L.call("ydl_wgrad_unpad", _p(tmp), _p(gk), self.c2, kk, self.c1, 1, st)
-        else:                                           # exotic grad layout: let torch place it (cold path)
-            g.add_(tmp[:, :, :self.c1].view(self.c2, self.k, self.k, self.c1).permute(0, 3, 1, 2))
-        config.mark_touched(p)
-        return False
+    def _place_grad(self, g: torch.Tensor, tmp: torch.Tensor) -> None:
+        """exotic gradient layout: let torch place the padded [c2][k*k][cin_p] gradient (cold path)"""
+        g.add_(tmp[:, :, :self.c1].view(self.c2, self.k, self.k, self.c1).permute(0, 3, 1, 2))
 
-    # -- forward ----------------------------------------------------------------------------------------
     # -- depth-wise variant (weight [C,1,k,k]: the KRSC physical layout is [C][k*k]) -------------------------
     def master_dw(self) -> torch.Tensor:
         w = self.conv.weight.detach().permute(0, 2, 3, 1)
@@ -357,17 +417,13 @@ class Conv(YdlModule):
             raise RuntimeError("depth-wise weight gradient must be KRSC-contiguous")
         return g
 
+    # -- forward ----------------------------------------------------------------------------------------
     def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None, res: Optional[Var] = None,
              res_mode: int = L.RES_NONE, act_code: Optional[int] = None) -> Var:
         self.mark_step(tape)
         act = self.act_code if act_code is None else act_code
-        if self.depthwise and self.dw_fused_stats:
-            return tape.dw_bn_act(x, self, self.s, act, out=out, res=res, res_mode=res_mode)
         if self.depthwise:
-            if res is not None:
-                raise NotImplementedError("depth-wise Conv with a fused residual")
-            y = tape.dwconv_bn_act(x, self, act)
-            return y if out is None else tape.copy(y, out)
+            return tape.dw_bn_act(x, self, self.s, act, out=out, res=res, res_mode=res_mode)
         if getattr(self, "_fused", None) is not None and not tape.train:
             y = tape.conv_bias_act(x, self, act, res=res, res_mode=res_mode)
             return y if out is None else tape.copy(y, out)
@@ -468,7 +524,7 @@ class _S2DStem:
         config.mark_touched(p)
 
 
-class _FusedPair:
+class _FusedPair(_GemmWeights):
     """Two 1x1 Convs that read the SAME input (cv1/cv2 of a CSP block) run as ONE convolution with concatenated output
     channels: the input is read once in forward and wgrad, and dgrad writes the input gradient once instead of
     write + read-modify-write.  Possible without any copy when the two modules' parameters, gradients and BN buffers
@@ -533,9 +589,8 @@ class _FusedPair:
         wa, wb = self.a.conv.weight, self.b.conv.weight
         return (tape.dname, wa.data_ptr(), wa._version, wb._version, config.weight_epoch())
 
-    _wbuffers = None        # bound below (shared implementation with Conv)
-    compute_weights = None
-    coeffs = None
+    def _gemm_dims(self):
+        return self.c2, self.k * self.k, self.c1
 
     def mark_step(self, tape: Tape) -> None:
         self.a.mark_step(tape)
@@ -586,11 +641,6 @@ class _FusedPair:
 
 class _FusedBN:
     pass
-
-
-_FusedPair._wbuffers = Conv._wbuffers
-_FusedPair.compute_weights = Conv.compute_weights
-_FusedPair.coeffs = Conv.coeffs
 
 
 def _csp_forward(blk, tape: Tape, x: Var, add: bool) -> Var:
@@ -722,7 +772,6 @@ class DWConv(Conv):
         if d != 1:
             raise NotImplementedError(f"DWConv: dilation d={d} is not implemented on the HIP path")
         super().__init__(c1, c2, k, s, None, g, d, act)
-        self.dw_fused_stats = self.depthwise
 
 
 class GhostConv(YdlModule):
@@ -737,7 +786,6 @@ class GhostConv(YdlModule):
         c_ = c2 // 2
         self.cv1 = Conv(c1, c_, k, s, None, g, act=act)
         self.cv2 = Conv(c_, c_, 5, 1, None, c_, act=act)
-        self.cv2.dw_fused_stats = self.cv2.depthwise
         self.c_ = c_
 
     def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
@@ -818,11 +866,12 @@ class DeformConv2d(YdlModule):
                 f"padding={self.padding}, dilation={self.dilation}, bias={self.bias is not None}")
 
 
-class _DeformGemm:
+class _DeformGemm(_GemmWeights):
     """parameter holder of the 1x1 GEMM over a deformable column buffer, with Conv's interface for Tape.conv_bn_act: weight
     [Cout][kh*kw*Cin (+1)] = the KRSC weight (+ the bias column), followed by the BatchNorm ``bn``.  Not a module: it only
-    points at the DeformConv2d's parameters and the block's BatchNorm."""
-    k, s, p = 1, 1, 0
+    points at the DeformConv2d's parameters and the block's BatchNorm.  Its own: the [weight | bias] master and the scatter of
+    the padded gradient back into the two parameters; everything else is _GemmWeights."""
+    _wname = "DeformConv2d"
 
     def __init__(self, dc: DeformConv2d, bn: nn.BatchNorm2d):
         self.dc, self.bn = dc, bn
@@ -832,52 +881,29 @@ class _DeformGemm:
         self.c2 = dc.out_channels
         self._wcache = {}
 
-    def mark_step(self, tape: Tape) -> None:
-        if tape.train:
-            self.bn._nbt_pending += 1
+    @property
+    def _wparam(self) -> nn.Parameter:
+        return self.dc.weight
+
+    def _gemm_dims(self):
+        return self.c2, 1, self.c1
 
     def _wkey(self, tape: Tape):
         w, b = self.dc.weight, self.dc.bias
         return (tape.dname, w.data_ptr(), w._version, b._version if b is not None else -1, config.weight_epoch())
 
-    def compute_weights(self, tape: Tape):
-        key = self._wkey(tape)
-        c = self._wcache
-        if c.get("key") == key:
-            return c["w"], c["wt"]
-        dev = self.dc.weight.device
-        if c.get("w") is None or c["w"].dtype != tape.tdt or c["w"].device != dev:
-            c["w"] = torch.empty((self.c2, 1, round_up(self.c1, 8)), dtype=tape.tdt, device=dev)
-            c["wt"] = torch.empty((self.c1, 1, round_up(self.c2, 8)), dtype=tape.tdt, device=dev)
-        st = _stream()
-        wk = self.dc.weight.detach().permute(0, 2, 3, 1)
-        if not wk.is_contiguous():
-            self.dc.weight.data = self.dc.weight.data.contiguous(memory_format=torch.channels_last)
-            wk = self.dc.weight.detach().permute(0, 2, 3, 1)
+    def _master_krsc(self) -> torch.Tensor:
+        wk = super()._master_krsc()
         if self.dc.bias is None:
-            master = wk
-        else:                      # [Cout][kk | bias]: two strided copies into a cached f32 buffer
-            master = c.get("master")
-            if master is None or master.device != dev:
-                master = c["master"] = torch.empty((self.c2, self.c1), dtype=torch.float32, device=dev)
-            L.call("ydl_copy2d", L.YDL_F32, _p(wk), self.kk, _p(master), self.c1, self.c2, self.kk, 0, st)
-            L.call("ydl_copy2d", L.YDL_F32, _p(self.dc.bias.detach()), 1, ctypes.c_void_p(master.data_ptr() + 4 * self.kk), self.c1,
-                   self.c2, 1, 0, st)
-        L.call("ydl_weight_prep", tape.dt, _p(master), _p(c["w"]), _p(c["wt"]), self.c2, 1, self.c1, st)
-        c["key"] = key
-        return c["w"], c["wt"]
-
-    coeffs = Conv.coeffs
-    touch_bn = Conv.touch_bn
-
-    def _grad_of(self, p: nn.Parameter) -> torch.Tensor:
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
-
-    def grad_slot(self, tape: Tape, which: str):
-        p = self.bn.weight if which == "gamma" else self.bn.bias
-        return self._grad_of(p), 1
+            return wk
+        c, st = self._wcache, _stream()         # [Cout][kk | bias]: two strided copies into a cached f32 buffer
+        master = c.get("master")
+        if master is None or master.device != wk.device:
+            master = c["master"] = torch.empty((self.c2, self.c1), dtype=torch.float32, device=wk.device)
+        L.call("ydl_copy2d", L.YDL_F32, _p(wk), self.kk, _p(master), self.c1, self.c2, self.kk, 0, st)
+        L.call("ydl_copy2d", L.YDL_F32, _p(self.dc.bias.detach()), 1, ctypes.c_void_p(master.data_ptr() + 4 * self.kk), self.c1,
+               self.c2, 1, 0, st)
+        return master
 
     def trainable(self):
         b = self.dc.bias
@@ -889,11 +915,9 @@ class _DeformGemm:
 
     def wgrad(self, tape: Tape, gp, x: Var, dy: Var, st, col0: int = 0, final: bool = True, fuse=None) -> bool:
         w, b = self.dc.weight, self.dc.bias
+        if b is None and self.kk % 8 == 0 and w.requires_grad:
+            return super().wgrad(tape, gp, x, dy, st, col0, final, fuse)       # the column buffer IS the dense KRSC gradient
         gk = self._grad_of(w).permute(0, 2, 3, 1) if w.requires_grad else None
-        if b is None and self.kk % 8 == 0 and gk is not None and gk.is_contiguous():
-            done = _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(gk), st, fuse)
-            config.mark_touched(w)
-            return done
         if gk is not None and not gk.is_contiguous():
             raise RuntimeError("DeformConv2d weight gradient must be KRSC-contiguous")
         ld = round_up(self.c1, 8)
@@ -950,68 +974,20 @@ class C2f_DCN(C2f):
         self.m = nn.ModuleList(_DCNSeq(self.c, g) for _ in range(n))
 
 
-class _BiasConv2d(nn.Conv2d):
+class _BiasConv2d(_GemmWeights, nn.Conv2d):
     """``nn.Conv2d(c1, c2, k, s, p, bias=True)`` run by Tape.conv_bias (no BatchNorm, no activation); weight kept channels_last
     (the KRSC master).  ``_keep_init``: the yaml models' kaiming pass leaves its (zero) initialisation alone."""
     _keep_init = True
+    _wname = "conv_offset_mask"
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
+        self.k, self.s, self.p = self.kernel_size[0], self.stride[0], self.padding[0]
         self._wcache = {}
 
-    def compute_weights(self, tape: Tape):
-        key = (tape.dname, self.weight.data_ptr(), self.weight._version, config.weight_epoch())
-        c = self._wcache
-        kk = self.kernel_size[0] * self.kernel_size[1]
-        dev = self.weight.device
-        if c.get("w") is None or c["w"].dtype != tape.tdt or c["w"].device != dev:
-            c["w"] = torch.empty((self.out_channels, kk, round_up(self.in_channels, 8)), dtype=tape.tdt, device=dev)
-            c["wt"] = torch.empty((self.in_channels, kk, round_up(self.out_channels, 8)), dtype=tape.tdt, device=dev)
-            c["key"] = None
-        if c.get("key") != key:
-            wk = self.weight.detach().permute(0, 2, 3, 1)
-            if not wk.is_contiguous():
-                self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
-                wk = self.weight.detach().permute(0, 2, 3, 1)
-            L.call("ydl_weight_prep", tape.dt, _p(wk), _p(c["w"]), _p(c["wt"]), self.out_channels, kk, self.in_channels, _stream())
-            c["key"] = key
-        return c["w"], c["wt"]
-
-    def bias_coeffs(self, device):
-        cp = round_up(self.out_channels, 8)
-        key = (self.bias.data_ptr(), self.bias._version, config.weight_epoch())
-        c = self._wcache
-        if c.get("ones") is None or c["ones"].device != device:
-            c["ones"] = torch.ones(cp, dtype=torch.float32, device=device)
-            c["bpad"] = torch.zeros(cp, dtype=torch.float32, device=device)
-            c["bkey"] = None
-        if c.get("bkey") != key:
-            L.call("ydl_copy2d", L.YDL_F32, _p(self.bias.detach()), self.out_channels, _p(c["bpad"]), cp, 1, self.out_channels, 0,
-                   _stream())
-            c["bkey"] = key
-        return c["ones"], c["bpad"]
-
-    def _grad_of(self, p: nn.Parameter) -> torch.Tensor:
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
-
-    def wgrad(self, tape: Tape, gp, x: Var, dy: Var, st) -> None:
-        if not self.weight.requires_grad:
-            return
-        gk = self._grad_of(self.weight).permute(0, 2, 3, 1)
-        kk = self.kernel_size[0] * self.kernel_size[1]
-        cin_p = round_up(self.in_channels, 8)
-        if cin_p == self.in_channels and gk.is_contiguous():
-            _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(gk), st)
-        else:
-            if not gk.is_contiguous():
-                raise RuntimeError("conv_offset_mask weight gradient must be KRSC-contiguous")
-            tmp = zero_(torch.empty((self.out_channels, kk, cin_p), dtype=torch.float32, device=gk.device), st)
-            _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(tmp), st)
-            L.call("ydl_wgrad_unpad", _p(tmp), _p(gk), self.out_channels, kk, self.in_channels, 1, st)
-        config.mark_touched(self.weight)
+    def _gemm_dims(self):
+        return self.out_channels, self.k * self.k, self.in_channels
 
 
 class DCNv2(YdlModule):
@@ -1266,70 +1242,13 @@ class SegmentHead(YdlModule):
 # ----------------------------------------------------------------------------------------------------------
 # DCNv3 module and its YOLO wiring (models/ops_dcnv3/build/.../modules/dcnv3.py:50-136, "common and yolo.py":2-38)
 # ----------------------------------------------------------------------------------------------------------
-class _LinearOps:
-    """what Tape.linear needs from a weight holder, written against ``self.weight`` [rows, in], ``self.bias`` [rows] or None and
-    ``self._rows``: None (the whole parameters: Linear) or the slice of rows this holder stands for (one Q / K / V block of
-    ``in_proj_weight`` / ``in_proj_bias``).  ``final``: this holder's backward is the last launch that writes the parameters'
-    gradients, so only it reports them to ``config.mark_touched`` (the data-parallel hook may start the all-reduce from there)."""
-    _rows = None
-    final = True
+class _LinearOps(_GemmWeights):
+    """a Linear as Tape.conv_bias sees it: the 1x1 case of _GemmWeights over ``self.weight`` [rows, in] and ``self.bias`` [rows] or
+    None (the whole parameters: Linear) or over one row block of them (``_rows``: _InProj)"""
+    _wname = "Linear"
 
-    def _wkey(self, tape: Tape):
-        return (tape.dname, self.weight.data_ptr(), self.weight._version, config.weight_epoch())
-
-    def _sel(self, t: torch.Tensor) -> torch.Tensor:
-        return t if self._rows is None else t[self._rows]
-
-    def compute_weights(self, tape: Tape):
-        key = self._wkey(tape)
-        c = self._wcache
-        if c.get("key") != key or c.get("w") is None or c["w"].dtype != tape.tdt:
-            dev = self.weight.device
-            if c.get("w") is None or c["w"].dtype != tape.tdt or c["w"].device != dev:
-                c["w"] = torch.empty((self.out_features, 1, round_up(self.in_features, 8)), dtype=tape.tdt, device=dev)
-                c["wt"] = torch.empty((self.in_features, 1, round_up(self.out_features, 8)), dtype=tape.tdt, device=dev)
-            master = self.weight.detach()
-            if not master.is_contiguous():
-                master = master.contiguous()
-            L.call("ydl_weight_prep", tape.dt, _p(self._sel(master)), _p(c["w"]), _p(c["wt"]), self.out_features, 1, self.in_features,
-                   _stream())
-            c["key"] = key
-        return c["w"], c["wt"]
-
-    def bias_coeffs(self, device):
-        """(ones, bias) padded to a multiple of 8 channels for ydl_bn_act_fwd (scale = 1, shift = bias)"""
-        cp = round_up(self.out_features, 8)
-        key = (self.bias.data_ptr(), self.bias._version, config.weight_epoch())
-        c = self._wcache
-        if c.get("ones") is None or c["ones"].device != device:       # created once (a refresh below only rewrites bpad's contents)
-            c["ones"] = torch.ones(cp, dtype=torch.float32, device=device)
-            c["bpad"] = torch.zeros(cp, dtype=torch.float32, device=device)
-            c["bkey"] = None
-        if c.get("bkey") != key:
-            L.call("ydl_copy2d", L.YDL_F32, _p(self._sel(self.bias.detach())), self.out_features, _p(c["bpad"]), cp, 1, self.out_features,
-                   0, _stream())
-            c["bkey"] = key
-        return c["ones"], c["bpad"]
-
-    def _grad_of(self, p: nn.Parameter) -> torch.Tensor:
-        """(this holder's rows of) the parameter's gradient"""
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return self._sel(p.grad)
-
-    def wgrad(self, tape: Tape, gp, x: Var, dy: Var, st) -> None:
-        if not self.weight.requires_grad:          # frozen: no gradient kernel, never marked touched
-            return
-        g = self._grad_of(self.weight)
-        cin_p = round_up(self.in_features, 8)
-        if cin_p == self.in_features and g.is_contiguous():
-            _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(g), st)
-        else:
-            tmp = zero_(torch.empty((self.out_features, 1, cin_p), dtype=torch.float32, device=g.device), st)
-            _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), _p(tmp), st)
-            L.call("ydl_wgrad_unpad", _p(tmp), _p(g), self.out_features, 1, self.in_features, 1, st)
-        if self.final:
-            config.mark_touched(self.weight)
+    def _gemm_dims(self):
+        return self.out_features, 1, self.in_features
 
 
 class Linear(_LinearOps, YdlModule):
@@ -1348,7 +1267,7 @@ class Linear(_LinearOps, YdlModule):
         self._wcache = {}
 
     def _fwd(self, tape: Tape, x: Var) -> Var:
-        return tape.linear(x, self)
+        return tape.conv_bias(x, self)
 
 
 def _lanes_per_group_channel_block(gc: int) -> int:
@@ -1614,7 +1533,7 @@ MHA_HEAD_DIM_STEP, MHA_HEAD_DIM_MAX = 8, 128          # ydl_mha_fwd: d a multipl
 
 
 class _InProj(_LinearOps):
-    """rows [i*c, (i+1)*c) of ``ma.in_proj_weight`` / ``ma.in_proj_bias`` seen as one Linear by Tape.linear: the compute-layout
+    """rows [i*c, (i+1)*c) of ``ma.in_proj_weight`` / ``ma.in_proj_bias`` seen as one Linear by Tape.conv_bias: the compute-layout
     copy is derived from the row block, and the weight and bias gradients are written into the matching contiguous slices of the
     two parameters' gradients.  TransformerLayer runs the blocks in the order Q, K, V, so the backward reaches block 0 last: it
     alone is ``final``."""
@@ -1685,11 +1604,11 @@ class TransformerLayer(YdlModule):
         t = tape.new(x.N, 3 * c, x.H, x.W)           # [pix][q x | k x | v x]
         qkv = tape.new(x.N, 3 * c, x.H, x.W)         # [pix][Q | K | V]
         for i, (lin, blk) in enumerate(zip((self.q, self.k, self.v), self.ma.blocks())):
-            a = tape.linear(x, lin, out=t.slice(i * c, (i + 1) * c))
-            tape.linear(a, blk, out=qkv.slice(i * c, (i + 1) * c))
+            a = tape.conv_bias(x, lin, out=t.slice(i * c, (i + 1) * c))
+            tape.conv_bias(a, blk, out=qkv.slice(i * c, (i + 1) * c))
         att = tape.mha(qkv, self.num_heads)
-        x1 = tape.add(tape.linear(att, self.ma.out_proj), x)
-        return tape.add(tape.linear(tape.linear(x1, self.fc1), self.fc2), x1, out=out)
+        x1 = tape.add(tape.conv_bias(att, self.ma.out_proj), x)
+        return tape.add(tape.conv_bias(tape.conv_bias(x1, self.fc1), self.fc2), x1, out=out)
 
 
 class TransformerBlock(YdlModule):
@@ -1709,7 +1628,7 @@ class TransformerBlock(YdlModule):
         if self.conv is not None:
             x = self.conv._fwd(tape, x)
         n = len(self.tr)
-        x = tape.add(x, tape.linear(x, self.linear), out=out if n == 0 else None)
+        x = tape.add(x, tape.conv_bias(x, self.linear), out=out if n == 0 else None)
         for i, layer in enumerate(self.tr):
             x = layer._fwd(tape, x, out=out if i == n - 1 else None)
         return x

@@ -493,6 +493,42 @@ class Tape:
             self._side_used = False
         self._keep.clear()
 
+    # ------------------------------------------------------------------ BatchNorm pieces shared by conv_bn_act and dw_bn_act
+    def _bn_coeffs(self, m, cf, C: int, st, part=None) -> None:
+        """scale / shift (and in train mode mean / invstd, the running statistics) of ``m.bn`` into ``cf``: from the partial rows
+        ``part`` = (ws, rows, block_m, npix, rep) a convolution launch wrote (ydl_bn_finalize), or in eval mode (``part`` None)
+        from the running statistics (ydl_bn_eval_coeffs)"""
+        bn = m.bn
+        if part is None:
+            L.call("ydl_bn_eval_coeffs", C, _p(bn.weight), _p(bn.bias), _p(bn.running_mean), _p(bn.running_var), bn.eps,
+                   _p(cf["scale"]), _p(cf["shift"]), st)
+            return
+        ws, rows, block_m, npix, rep = part
+        L.call("ydl_bn_finalize", _p(ws), rows, block_m, npix, C, _p(bn.weight), _p(bn.bias), bn.eps, bn.momentum,
+               _p(bn.running_mean), _p(bn.running_var), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rep, st)
+
+    def _bn_grad_rows(self, m, cp: int):
+        """(dgamma row, dbeta row, accumulate flag) of ``m.bn``.  A frozen parameter (requires_grad False) gets a scratch row: the
+        sums still exist (dy needs them).  One accumulate flag serves both rows, so a scratch row beside a real one is zeroed."""
+        _w, train_g, train_b = m.trainable()
+        gw, accw = m.grad_slot(self, "gamma") if train_g else (torch.empty(cp, dtype=torch.float32, device=self.device), 0)
+        gb, accb = m.grad_slot(self, "beta") if train_b else (torch.empty(cp, dtype=torch.float32, device=self.device), 0)
+        if accb != accw:
+            zero_(gw if not train_g else gb)
+            accw = 1
+        return gw, gb, accw
+
+    def _res_grad(self, res: Optional[Var], res_mode: int, o: Var, dout: torch.Tensor):
+        """(buffer, row stride, residual mode) for the BatchNorm-backward pass that also writes (or adds) the gradient of the
+        residual operand: dz for a residual joined before the activation, dout itself for one joined after it.  (None, 0, mode)
+        when there is nothing to write: no residual, none wanted, or d/dres IS dout and res took dout's buffer (no copy pass)."""
+        if res is None or not res.need or res_mode not in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
+            return None, 0, res_mode
+        if res_mode == L.RES_AFTER_ACT and self._alias_grad(res, o, dout):
+            return None, 0, res_mode
+        gbuf, racc = self.grad_target(res)
+        return gbuf, res.ld, (res_mode | L.RES_GRAD_ACCUMULATE) if racc else res_mode
+
     # ------------------------------------------------------------------ conv + BN + act (+ residual)
     def conv_bn_act(self, x: Var, m, s: int, p: int, act: int, out=None,
                     res: Optional[Var] = None, res_mode: int = L.RES_NONE) -> Var:
@@ -642,14 +678,10 @@ class Tape:
                 grid_m, block_m = L.lib().ydl_conv_fwd_grid_m(gp, self.dt), L.lib().ydl_conv_fwd_block_m(gp, self.dt)
             ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
             conv_fwd(_p(ws))
-            L.call("ydl_bn_finalize", _p(ws), grid_m, block_m,
-                   npix, Cout, _p(m.bn.weight), _p(m.bn.bias), m.bn.eps, m.bn.momentum,
-                   _p(m.bn.running_mean), _p(m.bn.running_var), _p(cf["mean"]), _p(cf["invstd"]),
-                   _p(cf["scale"]), _p(cf["shift"]), rep, st)
+            self._bn_coeffs(m, cf, Cout, st, (ws, grid_m, block_m, npix, rep))
         else:
             conv_fwd(None)
-            L.call("ydl_bn_eval_coeffs", Cout, _p(m.bn.weight), _p(m.bn.bias), _p(m.bn.running_mean),
-                   _p(m.bn.running_var), m.bn.eps, _p(cf["scale"]), _p(cf["shift"]), st)
+            self._bn_coeffs(m, cf, Cout, st)
         single = len(parts) == 1
         for (co, cw, o) in parts:
             cp = round_up(cw, 8)
@@ -692,12 +724,7 @@ class Tape:
                                                          # (a residual operand that does is served by the BN-backward pass below)
             st2 = _stream()
             dy = self.new(x.N, Cout, Ho, Wo)
-            # frozen BN parameters (requires_grad False): the sums still exist (dy needs them) but land in a scratch row
-            gw, accw = m.grad_slot(self, "gamma") if train_g else (torch.empty(Cout_p, dtype=torch.float32, device=self.device), 0)
-            gb, accb = m.grad_slot(self, "beta") if train_b else (torch.empty(Cout_p, dtype=torch.float32, device=self.device), 0)
-            if accb != accw:                              # one accumulate flag serves both rows: give the scratch row defined contents
-                zero_(gw if not train_g else gb)
-                accw = 1
+            gw, gb, accw = self._bn_grad_rows(m, Cout_p)
             for (co, cw, o) in parts:
                 cp = round_up(cw, 8)
                 dyv = dy.t if single else dy.t[:, co:co + cw]
@@ -705,16 +732,7 @@ class Tape:
                     zero_(dyv)
                     continue
                 dout = self._gbuf(o)
-                # gradient of the residual branch, written (or added) by the same kernel pass: dz for a residual joined before the
-                # activation, dout itself for one joined after it
-                dres_t, dres_ld, rmode = None, 0, res_mode
-                if res is not None and res.need and res_mode == L.RES_AFTER_ACT and self._alias_grad(res, o, dout):
-                    pass          # d/dres IS dout and nothing else has written it yet: res takes dout's buffer, no copy pass
-                elif res is not None and res.need and res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
-                    gbuf, racc = self.grad_target(res)
-                    dres_t, dres_ld = gbuf, res.ld
-                    if racc:
-                        rmode = res_mode | L.RES_GRAD_ACCUMULATE
+                dres_t, dres_ld, rmode = self._res_grad(res, res_mode, o, dout)
                 if sums_mode:
                     red = o.bnred
                     o.bnred = None
@@ -746,7 +764,7 @@ class Tape:
                 # HBM-bound 1x1 layer: input and weight gradient in ONE pass over dy, on the main stream (ydl_conv_bwd_pw)
                 gx, acc = self.grad_target(x)
                 if m.wgrad(self, gp, x, dy, st2, fuse=(_p(wt), _p(gx), x.ld, acc)):
-                    _keep = (geom,)
+                    self._keep.append(geom)
                     return
                 L.call("ydl_conv_dgrad", gp, self.dt, _p(dy.t), _p(wt), _p(gx), acc, st2)     # (the weight gradient ran alone)
                 return
@@ -763,7 +781,7 @@ class Tape:
                 gx, acc = self.grad_target(x)
                 if not self._try_bnred(x, gp, dy, wt, gx, acc, st2):
                     L.call("ydl_conv_dgrad", gp, self.dt, _p(dy.t), _p(wt), _p(gx), acc, st2)
-            _keep = (geom,)   # keep the ctypes struct alive for the closure
+            self._keep.append(geom)     # the ctypes struct outlives the enqueue
 
         self.bw.append(bw)
         return ret
@@ -781,11 +799,8 @@ class Tape:
         out = self.new(x.N, m.c2, Ho, Wo)
         w, _wt = m._fused_weights(self)
         geom = L.ConvGeom(x.N, x.H, x.W, m.c1, Ho, Wo, m.c2, k, s, p, x.ld, out.ld, 0)
-        st = _stream()
-        L.call("ydl_conv_fwd", ctypes.byref(geom), self.dt, _p(x.t), _p(w), _p(out.t), None, 0, st)
         f = m._fused
-        L.call("ydl_bn_act_fwd", self.dt, _p(out.t), out.ld, _p(f["ones"]), _p(f["bias"]), _p(res.t) if res is not None else None,
-               res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, x.N * Ho * Wo, round_up(m.c2, 8), st)
+        self._conv_shift_fwd(ctypes.byref(geom), x, w, out, lambda _dev: (f["ones"], f["bias"]), _stream(), act, res, res_mode)
         return out
 
     def _bw_split(self, m, subs, dy: Var, wt: torch.Tensor, Cout_p: int, Ho: int, Wo: int, st2) -> None:
@@ -1129,111 +1144,12 @@ class Tape:
             x = self.copy(x, self.new(x.N, x.C, x.H, x.W, need=x.need, f32=(x.dt == L.YDL_F32)))
         return x
 
-    def linear(self, x: Var, lin, out: Optional[Var] = None) -> Var:
-        """nn.Linear on the channel dimension of an NHWC tensor (modules/dcnv3.py:92-100) = 1x1 convolution + bias.
-        ``lin`` holds weight [out, in] (KRSC of a 1x1 conv is the same memory) and bias [out].  ``out`` may be an 8-aligned channel
-        slice of a wider buffer (the Q | K | V blocks of Tape.mha)."""
-        x = self._flat(x)
-        Cin, Cout = lin.in_features, lin.out_features
-        if x.C != Cin:
-            raise RuntimeError(f"Linear input channel mismatch: got {x.C}, weight expects {Cin}")
-        w, wt = lin.compute_weights(self)
-        if out is None:
-            out = self.new(x.N, Cout, x.H, x.W)
-        elif (out.N, out.C, out.H, out.W) != (x.N, Cout, x.H, x.W) or not out.aligned():
-            raise RuntimeError("linear: the output slice has the wrong shape or is not 16-byte aligned")
-        geom = L.ConvGeom(x.N, x.H, x.W, Cin, x.H, x.W, Cout, 1, 1, 0, x.ld, out.ld, 0)
-        gp = ctypes.byref(geom)
-        st = _stream()
-        L.call("ydl_conv_fwd", gp, self.dt, _p(x.t), _p(w), _p(out.t), None, 0, st)
-        if lin.bias is not None:
-            cp = round_up(Cout, 8)
-            ones, bias = lin.bias_coeffs(self.device)
-            L.call("ydl_bn_act_fwd", self.dt, _p(out.t), out.ld, _p(ones), _p(bias), None, 0, L.RES_NONE, L.ACT_NONE,
-                   _p(out.t), out.ld, x.npix, cp, st)
-        if self.record:
-            def bw():
-                if not out.is_set():
-                    return
-                st2 = _stream()
-                dout = self._gbuf(out)
-                dov = Var(self, dout, out.ld, False)
-                if lin.bias is not None and lin.bias.requires_grad:
-                    gb = lin._grad_of(lin.bias)
-                    ws = torch.empty(L.lib().ydl_channel_sum_ws_bytes(Cout) // 4, dtype=torch.float32, device=self.device)
-                    L.call("ydl_channel_sum", self.dt, _p(dout), out.ld, _p(gb), _p(ws), x.npix, Cout, 1, st2)
-                    if lin.final:            # a row block of a shared parameter reports it once, after its last writer
-                        from . import config as _cfg
-                        _cfg.mark_touched(lin.bias)
-                lin.wgrad(self, gp, x, dov, st2)
-                if x.need:
-                    gx, acc = self.grad_target(x)
-                    L.call("ydl_conv_dgrad", gp, self.dt, _p(dout), _p(wt), _p(gx), acc, st2)
-                self._keep.append(geom)
-            self.bw.append(bw)
-        return out
-
-    def dwconv_bn_act(self, x: Var, m, act: int) -> Var:
-        """depth-wise ``Conv(c, c, k, g=c)`` = conv -> train-mode BN -> SiLU (modules/dcnv3.py:89, :35-39)"""
-        x = self._flat(x)
-        C, k, p = m.c1, m.k, m.p
-        y = self.new(x.N, C, x.H, x.W)
-        out = self.new(x.N, C, x.H, x.W)
-        st = _stream()
-        wm = m.master_dw()                                   # f32 [C][k*k]
-        L.call("ydl_dwconv_fwd", self.dt, _p(x.t), x.ld, _p(wm), _p(y.t), y.ld, x.N, x.H, x.W, C, k, p, st)
-        cf = m.coeffs(self.device)
-        npix = x.npix
-        cp = round_up(C, 8)
-        if self.train:
-            ws = torch.empty(L.lib().ydl_bn_stats_ws_bytes(npix, C) // 4, dtype=torch.float32, device=self.device)
-            bm = L.lib().ydl_bn_stats_block_m()
-            L.call("ydl_bn_stats", self.dt, _p(y.t), y.ld, _p(ws), npix, C, st)
-            L.call("ydl_bn_finalize", _p(ws), (npix + bm - 1) // bm, bm, npix, C, _p(m.bn.weight), _p(m.bn.bias), m.bn.eps,
-                   m.bn.momentum, _p(m.bn.running_mean), _p(m.bn.running_var), _p(cf["mean"]), _p(cf["invstd"]),
-                   _p(cf["scale"]), _p(cf["shift"]), 1, st)
-        else:
-            L.call("ydl_bn_eval_coeffs", C, _p(m.bn.weight), _p(m.bn.bias), _p(m.bn.running_mean), _p(m.bn.running_var),
-                   m.bn.eps, _p(cf["scale"]), _p(cf["shift"]), st)
-        L.call("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), None, 0, L.RES_NONE, act,
-               _p(out.t), out.ld, npix, cp, st)
-        if self.record:
-            if not self.train:
-                raise RuntimeError("backward through eval-mode BatchNorm is not supported")
-
-            def bw():
-                if not out.is_set():
-                    return
-                st2 = _stream()
-                dy = self.new(x.N, C, x.H, x.W)
-                train_w, train_g, train_b = m.trainable()
-                gw, accw = m.grad_slot(self, "gamma") if train_g else (torch.empty(cp, dtype=torch.float32, device=self.device), 0)
-                gb, accb = m.grad_slot(self, "beta") if train_b else (torch.empty(cp, dtype=torch.float32, device=self.device), 0)
-                if accb != accw:
-                    zero_(gw if not train_g else gb)
-                    accw = 1
-                ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
-                L.call("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(self._gbuf(out)), out.ld, _p(out.t), out.ld,
-                       _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), L.RES_NONE, act,
-                       _p(dy.t), dy.ld, None, 0, _p(gw), _p(gb), accw, _p(ws2), npix, C, cp, st2)
-                m.touch_bn()
-                if train_w:
-                    gk = m.grad_dw()
-                    ws3 = torch.empty(L.lib().ydl_dwconv_wgrad_ws_bytes(C, k) // 4, dtype=torch.float32, device=self.device)
-                    L.call("ydl_dwconv_wgrad", self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws3), x.N, x.H, x.W, C, k, p, st2)
-                    from . import config as _cfg
-                    _cfg.mark_touched(m.conv.weight)
-                if x.need:
-                    gx, acc = self.grad_target(x)
-                    L.call("ydl_dwconv_dgrad", self.dt, _p(dy.t), dy.ld, _p(wm), _p(gx), x.ld, acc, x.N, x.H, x.W, C, k, p, st2)
-            self.bw.append(bw)
-        return out
-
     def dw_bn_act(self, x: Var, m, s: int, act: int, out: Optional[Var] = None, res: Optional[Var] = None,
                   res_mode: int = L.RES_NONE) -> Var:
-        """strided depth-wise Conv+BN+act of the Ghost blocks (models/common.py:67-70, 253-279): out = act(bn(dwconv(x))) [+ res],
-        stride 1 or 2.  The convolution launch writes the BatchNorm partial rows of its own output (ydl_dwconv2_fwd), so train mode
-        goes conv -> ydl_bn_finalize -> ydl_bn_act_fwd with no statistics pass over y.  ``out`` may be a concat slice."""
+        """depth-wise Conv+BN+act: out = act(bn(dwconv(x))) [+ res], stride 1 or 2 — the Ghost blocks (models/common.py:67-70,
+        253-279) and the ``dw_conv`` branch of DCNv3 (modules/dcnv3.py:89, :35-39).  The convolution launch writes the BatchNorm
+        partial rows of its own output (ydl_dwconv2_fwd), so train mode goes conv -> ydl_bn_finalize -> ydl_bn_act_fwd with no
+        statistics pass over y.  ``out`` may be a concat slice."""
         x = self._flat(x)
         if res is not None:
             res = self._flat(res)
@@ -1258,13 +1174,10 @@ class Tape:
             ws = torch.empty(L.lib().ydl_bn_stats_ws_bytes(npix, C) // 4, dtype=torch.float32, device=self.device)
             bm = L.lib().ydl_bn_stats_block_m()
             L.call("ydl_dwconv2_fwd", self.dt, _p(x.t), x.ld, _p(wm), _p(y.t), y.ld, _p(ws), x.N, x.H, x.W, C, k, s, st)
-            L.call("ydl_bn_finalize", _p(ws), (npix + bm - 1) // bm, bm, npix, C, _p(m.bn.weight), _p(m.bn.bias), m.bn.eps,
-                   m.bn.momentum, _p(m.bn.running_mean), _p(m.bn.running_var), _p(cf["mean"]), _p(cf["invstd"]),
-                   _p(cf["scale"]), _p(cf["shift"]), 1, st)
+            self._bn_coeffs(m, cf, C, st, (ws, (npix + bm - 1) // bm, bm, npix, 1))
         else:
             L.call("ydl_dwconv2_fwd", self.dt, _p(x.t), x.ld, _p(wm), _p(y.t), y.ld, None, x.N, x.H, x.W, C, k, s, st)
-            L.call("ydl_bn_eval_coeffs", C, _p(m.bn.weight), _p(m.bn.bias), _p(m.bn.running_mean), _p(m.bn.running_var),
-                   m.bn.eps, _p(cf["scale"]), _p(cf["shift"]), st)
+            self._bn_coeffs(m, cf, C, st)
         L.call("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
                res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
         if not self.record:
@@ -1282,29 +1195,20 @@ class Tape:
             st2 = _stream()
             dy = self.new(x.N, C, Ho, Wo)
             dout = self._gbuf(out)
-            train_w, train_g, train_b = m.trainable()
-            gw, accw = m.grad_slot(self, "gamma") if train_g else (torch.empty(cp, dtype=torch.float32, device=self.device), 0)
-            gb, accb = m.grad_slot(self, "beta") if train_b else (torch.empty(cp, dtype=torch.float32, device=self.device), 0)
-            if accb != accw:
-                zero_(gw if not train_g else gb)
-                accw = 1
-            dres_t, dres_ld, rmode = None, 0, res_mode
-            if res is not None and res.need and res_mode == L.RES_AFTER_ACT and self._alias_grad(res, out, dout):
-                pass
-            elif res is not None and res.need and res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
-                dres_t, racc = self.grad_target(res)
-                dres_ld = res.ld
-                if racc:
-                    rmode = res_mode | L.RES_GRAD_ACCUMULATE
+            gw, gb, accw = self._bn_grad_rows(m, cp)
+            dres_t, dres_ld, rmode = self._res_grad(res, res_mode, out, dout)
             ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
             L.call("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
                    _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rmode, act,
                    _p(dy.t), dy.ld, _p(dres_t), dres_ld, _p(gw), _p(gb), accw, _p(ws2), npix, C, cp, st2)
             m.touch_bn()
-            if train_w:
+            if m.trainable()[0]:
                 gk = m.grad_dw()
-                ws3 = torch.empty(L.lib().ydl_dwconv2_wgrad_ws_bytes(C, k) // 4, dtype=torch.float32, device=self.device)
-                L.call("ydl_dwconv2_wgrad", self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws3), x.N, x.H, x.W, C, k, s, st2)
+                # k = 3 at stride 1 (DCNv3's dw_conv) stays on the stride-1 entry point and its vectorised kernel until
+                # ydl_dwconv2_wgrad has been measured against it at those shapes; its last argument is the padding, 1 like s
+                wg = "ydl_dwconv_wgrad" if (k == 3 and s == 1) else "ydl_dwconv2_wgrad"
+                ws3 = torch.empty(getattr(L.lib(), wg + "_ws_bytes")(C, k) // 4, dtype=torch.float32, device=self.device)
+                L.call(wg, self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws3), x.N, x.H, x.W, C, k, s, st2)
                 from . import config as _cfg
                 _cfg.mark_touched(m.conv.weight)
             if x.need:
@@ -1364,47 +1268,60 @@ class Tape:
             self.bw.append(bw)
         return out
 
-    def conv_bias(self, x: Var, m) -> Var:
-        """plain ``nn.Conv2d(..., bias=True)`` with no BatchNorm and no activation (DCNv2's conv_offset_mask, models/common.py:1652-1659):
-        implicit-GEMM convolution, the bias added by ydl_bn_act_fwd (scale 1); backward: bias gradient by ydl_channel_sum, weight
-        gradient and input gradient by the conv kernels.  ``m`` is a yolo_dual_amd.modules._BiasConv2d."""
+    def _conv_shift_fwd(self, gp, x: Var, w: torch.Tensor, out: Var, shift, st, act: int = L.ACT_NONE, res: Optional[Var] = None,
+                        res_mode: int = L.RES_NONE) -> None:
+        """out = act(conv(x, w) + b) [+ res]: the implicit-GEMM launch, then — unless ``shift`` is None — ydl_bn_act_fwd in place
+        with scale 1; ``shift(device)`` = (ones, b), asked for after the convolution is enqueued (it may launch a copy)"""
+        L.call("ydl_conv_fwd", gp, self.dt, _p(x.t), _p(w), _p(out.t), None, 0, st)
+        if shift is not None:
+            ones, bias = shift(self.device)
+            L.call("ydl_bn_act_fwd", self.dt, _p(out.t), out.ld, _p(ones), _p(bias), _p(res.t) if res is not None else None,
+                   res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, out.npix, round_up(out.C, 8), st)
+
+    def _conv_bias_bwd(self, m, gp, x: Var, dy: Var, wt: torch.Tensor, st) -> None:
+        """backward of out = conv(x, m.weight) + m.bias from dy = d out: the bias gradient (ydl_channel_sum), the weight gradient,
+        and the input gradient added into d x"""
+        if m.bias is not None and m.bias.requires_grad:
+            ws = torch.empty(L.lib().ydl_channel_sum_ws_bytes(dy.C) // 4, dtype=torch.float32, device=self.device)
+            L.call("ydl_channel_sum", self.dt, _p(dy.t), dy.ld, _p(m._grad_of(m.bias)), _p(ws), dy.npix, dy.C, 1, st)
+            if m.final:                  # a row block of a shared parameter reports it once, after its last writer
+                from . import config as _cfg
+                _cfg.mark_touched(m.bias)
+        m.wgrad(self, gp, x, dy, st)
+        if x.need:
+            gx, acc = self.grad_target(x)
+            L.call("ydl_conv_dgrad", gp, self.dt, _p(dy.t), _p(wt), _p(gx), acc, st)
+
+    def conv_bias(self, x: Var, m, out: Optional[Var] = None) -> Var:
+        """convolution + optional bias with no BatchNorm and no activation: ``nn.Conv2d`` (DCNv2's conv_offset_mask,
+        models/common.py:1652-1659) and ``nn.Linear`` on the channel dimension of an NHWC tensor (modules/dcnv3.py:92-100), which is
+        its 1x1 case.  ``m`` is a yolo_dual_amd.modules._GemmWeights holder: weight [out][taps][in] in KRSC order, ``bias`` [out] or
+        None.  ``out`` may be an 8-aligned channel slice of a wider buffer (the Q | K | V blocks of Tape.mha).  Backward: bias
+        gradient by ydl_channel_sum, weight and input gradient by the conv kernels."""
         x = self._flat(x)
-        k, s, p = m.kernel_size[0], m.stride[0], m.padding[0]
-        Cin, Cout = m.in_channels, m.out_channels
+        Cout, _taps, Cin = m._gemm_dims()
+        k, s, p = m.k, m.s, m.p
         if x.C != Cin:
-            raise RuntimeError(f"Conv2d input channel mismatch: got {x.C}, weight expects {Cin}")
+            raise RuntimeError(f"{m._wname} input channel mismatch: got {x.C}, weight expects {Cin}")
         Ho = (x.H + 2 * p - k) // s + 1
         Wo = (x.W + 2 * p - k) // s + 1
         w, wt = m.compute_weights(self)
-        out = self.new(x.N, Cout, Ho, Wo)
+        if out is None:
+            out = self.new(x.N, Cout, Ho, Wo)
+        elif (out.N, out.C, out.H, out.W) != (x.N, Cout, Ho, Wo) or not out.aligned():
+            raise RuntimeError("conv_bias: the output slice has the wrong shape or is not 16-byte aligned")
         geom = L.ConvGeom(x.N, x.H, x.W, Cin, Ho, Wo, Cout, k, s, p, x.ld, out.ld, 0)
         gp = ctypes.byref(geom)
-        st = _stream()
-        npix = x.N * Ho * Wo
-        L.call("ydl_conv_fwd", gp, self.dt, _p(x.t), _p(w), _p(out.t), None, 0, st)
-        ones, bias = m.bias_coeffs(self.device)
-        L.call("ydl_bn_act_fwd", self.dt, _p(out.t), out.ld, _p(ones), _p(bias), None, 0, L.RES_NONE, L.ACT_NONE,
-               _p(out.t), out.ld, npix, round_up(Cout, 8), st)
+        self._conv_shift_fwd(gp, x, w, out, m.bias_coeffs if m.bias is not None else None, _stream())
         if self.record:
             if x.need:
                 self._use(x)
 
             def bw():
-                # the consumers (DCNv2: the offset and mask slices) write channel slices of this buffer's gradient
+                # consumers may have written channel slices of this buffer's gradient only (DCNv2: the offset and mask slices)
                 if not (out.is_set() or any(c.gset for c in out.children)):
                     return
-                st2 = _stream()
-                dout = self._gbuf(out)
-                dov = Var(self, dout, out.ld, False)
-                if m.bias.requires_grad:
-                    ws = torch.empty(L.lib().ydl_channel_sum_ws_bytes(Cout) // 4, dtype=torch.float32, device=self.device)
-                    L.call("ydl_channel_sum", self.dt, _p(dout), out.ld, _p(m._grad_of(m.bias)), _p(ws), npix, Cout, 1, st2)
-                    from . import config as _cfg
-                    _cfg.mark_touched(m.bias)
-                m.wgrad(self, gp, x, dov, st2)
-                if x.need:
-                    gx, acc = self.grad_target(x)
-                    L.call("ydl_conv_dgrad", gp, self.dt, _p(dout), _p(wt), _p(gx), acc, st2)
+                self._conv_bias_bwd(m, gp, x, Var(self, self._gbuf(out), out.ld, False), wt, _stream())
                 self._keep.append(geom)
             self.bw.append(bw)
         return out
@@ -1489,10 +1406,10 @@ class Tape:
         base = qkv.t.data_ptr()
         blk = [ctypes.c_void_p(base + i * Cp * es) for i in range(len(projs))]
         wts = []
-        for pr, dst in zip(projs, blk):
+        for i, pr in enumerate(projs):
             w, wt = pr.compute_weights(self)
             wts.append(wt)
-            L.call("ydl_conv_fwd", gp, self.dt, _p(x.t), _p(w), dst, None, 0, st)
+            self._conv_shift_fwd(gp, x, w, Var(self, qkv.t[:, i * Cp:i * Cp + C], qkv.ld, False), None, st)
         rel = mod.rel()
         emb = mod.table(self)
         rh, rw = (_p(rel[0].detach()), _p(rel[1].detach())) if rel is not None else (None, None)
@@ -1530,18 +1447,14 @@ class Tape:
                 if want_tab:
                     mod.table_backward(self, emb, demb, st2)
                 for i, pr in enumerate(projs):
-                    dy = Var(self, dqkv.t[:, i * Cp:i * Cp + C], dqkv.ld, False)
-                    pr.wgrad(self, gp, x, dy, st2)
-                    if x.need:
-                        gx, acc = self.grad_target(x)
-                        L.call("ydl_conv_dgrad", gp, self.dt, dblk[i], _p(wts[i]), _p(gx), acc, st2)
+                    self._conv_bias_bwd(pr, gp, x, Var(self, dqkv.t[:, i * Cp:i * Cp + C], dqkv.ld, False), wts[i], st2)
                 self._keep.extend((geom, qkv, dqkv, ws, demb))
             self.bw.append(bw)
         return out
 
     def mha(self, qkv: Var, heads: int) -> Var:
         """dense multi-head self-attention over the H*W positions of each sample (nn.MultiheadAttention's core, no mask, no
-        dropout): ``qkv`` is ONE buffer of rows [pix][Q | K | V] whose three channel blocks were written by Tape.linear; head h is
+        dropout): ``qkv`` is ONE buffer of rows [pix][Q | K | V] whose three channel blocks were written by Tape.conv_bias; head h is
         channels [h*d, (h+1)*d) of a block, scale = d^-0.5.  ydl_mha_fwd keeps the f32 log-sum of every softmax row; the backward
         (ydl_mha_bwd, gather form, bitwise reproducible) writes dQ | dK | dV into the gradient of ``qkv`` in the same layout."""
         if qkv.parent is not None or qkv.lazy or qkv.virtual or qkv.C % 3:
