@@ -399,6 +399,21 @@ int ydl_deform_bwd(int dtype, const void* x, int ldx, const void* offset, int ld
                    const void* dcol, int ldc, float* grad_input, float* grad_offset, float* grad_mask, int N, int H, int W, int C,
                    int Ho, int Wo, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int G, void* stream);
 
+/* ---- dilated convolution in column form (stride 1, odd k, padding d*(k-1)/2: output size = input size) ---------------------------
+ * The zero-offset case of the deformable gather, as two pure gathers.  ydl_dilated_cols writes, for pix = (n*H + h)*W + w and
+ * tap = ky*k + kx, col[pix][tap*C + c] = x[n, h + (ky - k/2)*d, w + (kx - k/2)*d, c], or zero outside the image: a bit-exact copy in
+ * the layout of ydl_deform_gather, so the KRSC weight [Cout][k*k][C] is the weight of the 1x1 GEMM over col.  With ones_col the
+ * element col[pix][k*k*C] is 1; the elements from there (or from k*k*C) up to round_up(k*k*C + ones, 8) are zero; ldc must reach
+ * that far.  x: rows of ldx >= C elements (a channel slice is fine).  Any other geometry (even k, d < 1) is refused.
+ * ydl_dilated_cols_bwd: dx[n,h,w,c] (+)= sum over the taps whose output pixel (h - (ky - k/2)*d, w - (kx - k/2)*d) is inside the
+ * image of dcol[that pixel][tap*C + c]; f32 accumulation in registers in tap order, one store per element, no atomics and no
+ * workspace (bitwise reproducible); accumulate != 0 adds the sum to the previous contents of dx (rows of lddx).
+ * 16-byte accesses when C % 8 == 0 and rows are 16-byte aligned, an element path otherwise. */
+int ydl_dilated_cols(int dtype, const void* x, int ldx, void* col, int ldc, int ones_col,
+                     int N, int H, int W, int C, int k, int d, void* stream);
+int ydl_dilated_cols_bwd(int dtype, const void* dcol, int ldc, void* dx, int lddx, int accumulate,
+                         int N, int H, int W, int C, int k, int d, void* stream);
+
 /* ---- local (windowed) self-attention: AttentionConv / AttentionStem (models/common.py:1509-1627) --------------------------------
  * NHWC rows of ld* elements in the compute dtype, f32 arithmetic.  q, k: [pix][C]; v: m value tensors, V^mm at v + mm * v_stride
  * elements (m = 1 for AttentionConv).  Per sample, channel c and pixel (h, w), over the ks*ks taps t = i*ks + j that read position

@@ -113,6 +113,8 @@ SIGNATURES = {
                            _i, _i, _i, _i, _i, _vp]),
     "ydl_deform_gather": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i] + [_i] * 15 + [_vp]),
     "ydl_deform_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp] + [_i] * 15 + [_vp]),
+    "ydl_dilated_cols": (_i, [_i, _vp, _i, _vp, _i, _i] + [_i] * 6 + [_vp]),
+    "ydl_dilated_cols_bwd": (_i, [_i, _vp, _i, _vp, _i, _i] + [_i] * 6 + [_vp]),
     "ydl_local_attn_fwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "ydl_local_attn_bwd_ws_bytes": (_i64, [_i, _i, _i]),
     "ydl_local_attn_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i,

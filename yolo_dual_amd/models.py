@@ -24,7 +24,7 @@ import torch.nn as nn
 import yaml
 
 from . import _lib as L
-from .modules import (GAM, AttentionConv, AttentionStem, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C2f_DCN, C3, C3_DCN, C3_DCNCommon, C3_DCNV3,
+from .modules import (ASPP, RFB, GAM, AttentionConv, AttentionStem, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C2f_DCN, C3, C3_DCN, C3_DCNCommon, C3_DCNV3,
                       C3Common, C3Ghost, C3k2, C3TR, Concat, DWConv, GhostBottleneck, GhostConv, TransformerBlock,
                       Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region)
 from .tape import Tape, Var
@@ -526,7 +526,8 @@ def make_divisible(x, divisor):
 _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": SPPF, "Concat": Concat,
                 "nn.Upsample": Upsample, "Upsample": Upsample, "C3_DCNV3": C3_DCNV3, "Bottleneck_DCNV3": Bottleneck_DCNV3,
                 "AttentionConv": AttentionConv, "AttentionStem": AttentionStem, "DWConv": DWConv, "GhostConv": GhostConv,
-                "GhostBottleneck": GhostBottleneck, "C3Ghost": C3Ghost, "C3TR": C3TR, "TransformerBlock": TransformerBlock}
+                "GhostBottleneck": GhostBottleneck, "C3Ghost": C3Ghost, "C3TR": C3TR, "TransformerBlock": TransformerBlock,
+                "ASPP": ASPP, "RFB": RFB}
 
 
 def parse_model(d: dict, ch: List[int], deformable: bool = False):
@@ -546,7 +547,7 @@ def parse_model(d: dict, ch: List[int], deformable: bool = False):
         args = [None if a == "None" else a for a in args]
         n = n_ = max(round(n * gd), 1) if n > 1 else n
         if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3, C3_DCNCommon, AttentionConv, AttentionStem,
-                   DWConv, GhostConv, GhostBottleneck, C3Ghost, C3TR):
+                   DWConv, GhostConv, GhostBottleneck, C3Ghost, C3TR, ASPP, RFB):
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)

@@ -26,7 +26,8 @@ from .tape import Tape, Var, round_up, _p, _stream, zero_
 __all__ = ["autopad", "Conv", "C3", "C3Common", "Bottleneck", "C2f", "C3k2", "GAM", "SPPF", "Concat", "Upsample",
            "BasicBlock", "BottleneckBlock", "SegmentHead", "run_region", "Linear", "DCNv3", "DCNV3_YoLo", "Bottleneck_DCNV3",
            "C3_DCNV3", "DeformConv2d", "C3_DCN", "C2f_DCN", "DCNv2",
-           "Bottleneck_DCN", "C3_DCNCommon", "AttentionConv", "AttentionStem", "DWConv", "GhostConv", "GhostBottleneck", "C3Ghost"]
+           "Bottleneck_DCN", "C3_DCNCommon", "AttentionConv", "AttentionStem", "DWConv", "GhostConv", "GhostBottleneck", "C3Ghost",
+           "BasicConv", "RFB", "ASPP"]
 
 
 def autopad(k, p=None, d=1):
@@ -92,7 +93,7 @@ def refresh_weights(fn: nn.Module, tape: Tape) -> None:
     """one batched launch re-deriving the compute-layout weights of every stale Conv under ``fn``"""
     convs = getattr(fn, "_ydl_convs", None)
     if convs is None:
-        convs = [m for m in fn.modules() if isinstance(m, Conv) and not m.depthwise]
+        convs = [m for m in fn.modules() if isinstance(m, Conv) and not m.depthwise and m.d == 1 and m.bn is not None]     # (a dilated Conv's GEMM view is _DeformGemm)
         fn._ydl_convs = convs
         fn._ydl_csp = [m for m in fn.modules() if isinstance(getattr(m, "cv1", None), Conv) and isinstance(getattr(m, "cv2", None), Conv)]
     # sibling pairs that ran fused last time are prepared as ONE matrix (their masters are adjacent), their members not at all
@@ -371,18 +372,24 @@ class Conv(_GemmWeights, YdlModule):
         if g <= 0 or c1 % g != 0:
             raise ValueError(f"groups g={g} must be positive and divide c1={c1}")
         self.depthwise = g > 1 and g == c1 == c2
-        if d != 1 or (g != 1 and not self.depthwise):
-            raise NotImplementedError("the HIP path implements groups=1 (implicit GEMM) and groups=c1=c2 (depth-wise), dilation=1")
+        if g != 1 and not self.depthwise:
+            raise NotImplementedError("the HIP path implements groups=1 (implicit GEMM) and groups=c1=c2 (depth-wise, dilation=1)")
+        if d != 1 and not (g == 1 and d > 1 and s == 1 and k == 3 and p in (None, d)):
+            raise NotImplementedError(f"dilated Conv: the HIP path serves g=1, s=1, k=3, d>1 with p=None or p=d (column-form dilated "
+                                      f"convolution); got g={g}, s={s}, k={k}, d={d}, p={p}")
+        self.d = d
         if self.depthwise and (s not in (1, 2) or k not in (1, 3, 5, 7) or autopad(k, p) != k // 2):
             raise NotImplementedError(f"depth-wise Conv: stride s in {{1,2}}, k in {{1,3,5,7}}, 'same' padding p = k // 2 (got s={s}, k={k}, p={p})")
         self.c1, self.c2, self.k, self.s = c1, c2, k, s
-        self.p = autopad(k, p)
-        self.conv = nn.Conv2d(c1, c2, k, s, self.p, groups=g, bias=False)
+        self.p = autopad(k, p, d)
+        self.conv = nn.Conv2d(c1, c2, k, s, self.p, groups=g, dilation=d, bias=False)
         self.conv.weight.data = self.conv.weight.data.contiguous(memory_format=torch.channels_last)
         self.bn = _BNHolder(c2)
         self.act = nn.SiLU() if act is True else (act if isinstance(act, nn.Module) else nn.Identity())
         self.act_code = _act_code(self.act)
         self._wcache = {}
+        if d > 1:                     # column form (Tape.dilated_conv): the KRSC master seen as the [c2][9*c1] weight of a 1x1 GEMM
+            self.__dict__["_gemm"] = _DeformGemm(self.conv, self.bn)
 
     # -- parameters in compute layout: _GemmWeights over the KRSC master ``conv.weight`` ---------------------
     @property
@@ -420,8 +427,10 @@ class Conv(_GemmWeights, YdlModule):
     # -- forward ----------------------------------------------------------------------------------------
     def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None, res: Optional[Var] = None,
              res_mode: int = L.RES_NONE, act_code: Optional[int] = None) -> Var:
-        self.mark_step(tape)
         act = self.act_code if act_code is None else act_code
+        if self.d > 1:
+            return tape.dilated_conv(x, self.conv, self._gemm, self.d, act, out=out, res=res, res_mode=res_mode)
+        self.mark_step(tape)
         if self.depthwise:
             return tape.dw_bn_act(x, self, self.s, act, out=out, res=res, res_mode=res_mode)
         if getattr(self, "_fused", None) is not None and not tape.train:
@@ -440,6 +449,8 @@ class Conv(_GemmWeights, YdlModule):
         """fold the BatchNorm running statistics into the convolution: eval-mode forward becomes act(conv(x, w') + b')"""
         if self.depthwise:
             raise NotImplementedError("fuse() of a depth-wise Conv")
+        if self.d > 1:
+            raise NotImplementedError("fuse() of a dilated Conv (the folded eval path runs undilated convolutions only)")
         from .checkpoint import fuse_conv_and_bn
         wf, bf = fuse_conv_and_bn(self.conv, self.bn)
         cp = round_up(self.c2, 8)
@@ -1095,6 +1106,154 @@ class SPPF(YdlModule):
         s0 = self.cv1._fwd(tape, x, out=cat.slice(0, c_))
         tape.sppf_pools(s0, self.k, [cat.slice(c_, 2 * c_), cat.slice(2 * c_, 3 * c_), cat.slice(3 * c_, 4 * c_)])
         return self.cv2._fwd(tape, cat)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# dilated context blocks (models/common.py:1336-1361 ASPP, :1366-1384 BasicConv, :1386-1425 RFB)
+# ----------------------------------------------------------------------------------------------------------
+class _Conv2d(_BiasConv2d):
+    """a plain ``nn.Conv2d`` of a context block (Tape.conv_bias); unlike DCNv2's conv_offset_mask it takes the yaml models' kaiming pass"""
+    _keep_init = False
+    _wname = "Conv2d"
+
+
+class _DilatedConv2d(_Conv2d):
+    """``nn.Conv2d(c1, c2, k, 1, padding=d*(k-1)/2, dilation=d)`` as Tape.dilated_conv runs it: the 1x1 layer over the column buffer,
+    weight [c2][1][k*k*c1] = the KRSC master as it is"""
+    _wname = "dilated Conv2d"
+
+    def __init__(self, c1, c2, k, d, bias=True):
+        super().__init__(c1, c2, k, 1, d * (k - 1) // 2, dilation=d, bias=bias)
+        self.k, self.s, self.p = 1, 1, 0
+
+    def _gemm_dims(self):
+        return self.out_channels, 1, self.kernel_size[0] * self.kernel_size[1] * self.in_channels
+
+
+def _square(v, what: str) -> int:
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2 or v[0] != v[1]:
+            raise NotImplementedError(f"BasicConv: {what}={v} must be square on the HIP path")
+        v = v[0]
+    return int(v)
+
+
+class BasicConv(Conv):
+    """models/common.py:1366-1384: Conv2d(bias=False) -> BatchNorm2d(eps=1e-5, momentum=0.01) -> optional ReLU, or with ``bn=False`` a
+    biased Conv2d alone.  groups = 1; a dilation d > 1 needs kernel_size 3, stride 1, padding d (Tape.dilated_conv)."""
+
+    def __init__(self, in_planes, out_planes, kernel_size, stride=1, padding=0, dilation=1, groups=1, relu=True, bn=True):
+        k, p, d = _square(kernel_size, "kernel_size"), _square(padding, "padding"), _square(dilation, "dilation")
+        if groups != 1:
+            raise NotImplementedError(f"BasicConv: groups={groups} is not implemented on the HIP path (groups = 1 only)")
+        super().__init__(in_planes, out_planes, k, stride, p, 1, d, nn.ReLU(inplace=True) if relu else False)
+        self.out_channels = out_planes
+        self.relu = self.act if relu else None
+        self.bn.eps, self.bn.momentum = 1e-5, 0.01
+        if not bn:
+            if relu:
+                raise NotImplementedError("BasicConv(bn=False, relu=True): the bias form runs without an activation on the HIP path")
+            self.bn = None
+            self.conv = _DilatedConv2d(in_planes, out_planes, k, d) if d > 1 else _Conv2d(in_planes, out_planes, k, stride, p)
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None, res: Optional[Var] = None,
+             res_mode: int = L.RES_NONE, act_code: Optional[int] = None) -> Var:
+        if self.bn is not None:
+            return super()._fwd(tape, x, out=out, res=res, res_mode=res_mode, act_code=act_code)
+        if res is not None or act_code not in (None, L.ACT_NONE):
+            raise NotImplementedError("BasicConv(bn=False) takes no residual and no activation")
+        if self.d > 1:
+            y = tape.dilated_conv(x, self.conv, self.conv, self.d, L.ACT_NONE, out=out if out is None or out.aligned() else None)
+        else:
+            y = tape.conv_bias(x, self.conv, out=out if out is None or out.aligned() else None)
+        return y if out is None or y is out else tape.copy(y, out)
+
+    def fuse(self) -> "Conv":
+        if self.bn is None:
+            raise NotImplementedError("fuse() of a BasicConv without BatchNorm")
+        return super().fuse()
+
+
+class RFB(YdlModule):
+    """models/common.py:1386-1425: three branches ending in 3x3 convolutions of dilation vision+1, vision+2, vision+4, written into
+    one concat buffer, ``ConvLinear``, ``shortcut`` and relu(ConvLinear(cat) * scale + shortcut(x)).  ``scale`` multiplies the
+    BatchNorm output of ConvLinear as written (Tape.scale), so that layer's gradients carry the factor; the sum and the ReLU run in
+    the shortcut's BatchNorm apply.  stride = 1 and groups = 1 only."""
+
+    def __init__(self, in_planes, out_planes, stride=1, scale=0.1, map_reduce=8, vision=1, groups=1):
+        super().__init__()
+        if stride != 1:
+            raise NotImplementedError(f"RFB: stride={stride} is not implemented on the HIP path (stride 1 only)")
+        if groups != 1:
+            raise NotImplementedError(f"RFB: groups={groups} is not implemented on the HIP path (groups = 1 only)")
+        self.scale = scale
+        self.out_channels = out_planes
+        ip = in_planes // map_reduce
+        self.inter_planes = ip
+
+        def tail(d):
+            return BasicConv(2 * ip, 2 * ip, kernel_size=3, stride=1, padding=d, dilation=d, relu=False)
+        self.branch0 = nn.Sequential(BasicConv(in_planes, ip, kernel_size=1, stride=1, relu=False),
+                                     BasicConv(ip, 2 * ip, kernel_size=(3, 3), stride=stride, padding=(1, 1)), tail(vision + 1))
+        self.branch1 = nn.Sequential(BasicConv(in_planes, ip, kernel_size=1, stride=1, relu=False),
+                                     BasicConv(ip, 2 * ip, kernel_size=(3, 3), stride=stride, padding=(1, 1)), tail(vision + 2))
+        self.branch2 = nn.Sequential(BasicConv(in_planes, ip, kernel_size=1, stride=1, relu=False),
+                                     BasicConv(ip, (ip // 2) * 3, kernel_size=3, stride=1, padding=1),
+                                     BasicConv((ip // 2) * 3, 2 * ip, kernel_size=3, stride=stride, padding=1), tail(vision + 4))
+        self.ConvLinear = BasicConv(6 * ip, out_planes, kernel_size=1, stride=1, relu=False)
+        self.shortcut = BasicConv(in_planes, out_planes, kernel_size=1, stride=stride, relu=False)
+        self.relu = nn.ReLU(inplace=False)
+
+    def _gate(self, device, N: int) -> torch.Tensor:
+        """``scale`` as the constant f32 [N][C] operand of ydl_scale_channels (made once: the taped region issues no ATen kernel)"""
+        g = self.__dict__.get("_gate_t")
+        if g is None or g.device != device or g.shape[0] != N:
+            g = self.__dict__["_gate_t"] = torch.full((N, self.out_channels), float(self.scale), dtype=torch.float32, device=device)
+        return g
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        x = tape._flat(x)
+        ip = self.inter_planes
+        cat = tape.new(x.N, 6 * ip, x.H, x.W)
+        for i, br in enumerate((self.branch0, self.branch1, self.branch2)):
+            h = x
+            for j, blk in enumerate(br):
+                h = blk._fwd(tape, h, out=cat.slice(2 * ip * i, 2 * ip * (i + 1)) if j == len(br) - 1 else None)
+        lin = tape.scale(self.ConvLinear._fwd(tape, cat), self._gate(tape.device, x.N))
+        return self.shortcut._fwd(tape, x, res=lin, res_mode=L.RES_BEFORE_ACT, act_code=L.ACT_RELU)
+
+
+class ASPP(YdlModule):
+    """models/common.py:1336-1361 (the version without BatchNorm): cat(upsample(conv(avgpool x)), 1x1 conv, three 3x3 convs of
+    dilation 6 / 12 / 18) -> conv_1x1_output; every layer a biased ``nn.Conv2d``, no activation.  The bilinear up-sampling of the
+    pooled 1x1 map is a broadcast (Tape.resize); each branch writes its channel block of the one concat buffer when the block is a
+    whole number of 8-channel groups."""
+
+    def __init__(self, in_channel=512, out_channel=256):
+        super().__init__()
+        self.mean = nn.AdaptiveAvgPool2d((1, 1))
+        self.conv = _Conv2d(in_channel, out_channel, 1, 1)
+        self.atrous_block1 = _Conv2d(in_channel, out_channel, 1, 1)
+        self.atrous_block6 = _DilatedConv2d(in_channel, out_channel, 3, 6)
+        self.atrous_block12 = _DilatedConv2d(in_channel, out_channel, 3, 12)
+        self.atrous_block18 = _DilatedConv2d(in_channel, out_channel, 3, 18)
+        self.conv_1x1_output = _Conv2d(out_channel * 5, out_channel, 1, 1)
+        self.out_channel = out_channel
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        x = tape._flat(x)
+        c = self.out_channel
+        cat = tape.new(x.N, 5 * c, x.H, x.W)
+        direct = c % 8 == 0
+        pooled = tape.conv_bias(tape.global_pool(x, "avg"), self.conv)
+        tape.resize(pooled, x.H, x.W, L.RESIZE_BILINEAR, out=cat.slice(0, c))
+        for i, blk in enumerate((self.atrous_block1, self.atrous_block6, self.atrous_block12, self.atrous_block18)):
+            sl = cat.slice((i + 1) * c, (i + 2) * c)
+            out = sl if direct else None
+            y = tape.conv_bias(x, blk, out=out) if i == 0 else tape.dilated_conv(x, blk, blk, blk.dilation[0], L.ACT_NONE, out=out)
+            if not direct:
+                tape.copy(y, sl)
+        return tape.conv_bias(cat, self.conv_1x1_output)
 
 
 class Concat(YdlModule):

@@ -1383,6 +1383,60 @@ class Tape:
         gm.mark_step(self)
         return self.conv_bn_act(col, gm, 1, 0, act, out=out, res=res, res_mode=res_mode)
 
+    def dilated_conv(self, x: Var, m, gm, d: int, act: int, out: Optional[Var] = None, res: Optional[Var] = None,
+                     res_mode: int = L.RES_NONE) -> Var:
+        """k x k convolution with dilation ``d``, stride 1 and padding d*(k-1)/2, in column form like ``deform_conv``:
+        ydl_dilated_cols copies the taps into col[pix][tap*Cin + c] (a channel slice of a wider buffer is read in place), and the 1x1
+        GEMM over col is an ordinary ``conv_bn_act`` (``gm`` holds a BatchNorm: Conv + BN + act) or ``conv_bias`` (``gm.bn`` is None:
+        a plain ``nn.Conv2d``, bias or not, no activation), so the statistics, the weight gradient and d col come from the existing
+        conv path; ydl_dilated_cols_bwd gathers d col into d x (no atomics).  ``m`` is the ``nn.Conv2d`` that owns the weight
+        [Cout, Cin, k, k] (KRSC storage: the 1x1 weight as it is); ``gm`` its _GemmWeights view [Cout][1][k*k*Cin]."""
+        x = self.materialize(x)
+        k = m.kernel_size[0]
+        if x.C != m.in_channels:
+            raise RuntimeError(f"dilated Conv2d input channel mismatch: got {x.C}, weight expects {m.in_channels}")
+        kc = k * k * x.C
+        ld = round_up(kc, 8)
+        buf = torch.empty((x.N, x.H, x.W, ld), dtype=self.tdt, device=self.device)
+        col = Var(self, buf.permute(0, 3, 1, 2)[:, :kc], ld, x.need)
+        L.call("ydl_dilated_cols", self.dt, _p(x.t), x.ld, _p(col.t), ld, 0, x.N, x.H, x.W, x.C, k, d, _stream())
+        if self.record and x.need:
+            self._keep.append(buf)      # the deferred weight gradient reads col on the side stream: alive until the streams join
+            self._use(x)
+
+            def bw():
+                if not col.is_set():
+                    return
+                gx, acc = self.grad_target(x)
+                L.call("ydl_dilated_cols_bwd", self.dt, _p(self._gbuf(col)), ld, _p(gx), x.ld, acc, x.N, x.H, x.W, x.C, k, d, _stream())
+            self.bw.append(bw)
+        if getattr(gm, "bn", None) is None:
+            if act != L.ACT_NONE or res is not None:
+                raise NotImplementedError("dilated_conv: a convolution without BatchNorm takes no activation and no residual")
+            return self.conv_bias(col, gm, out=out)
+        gm.mark_step(self)
+        return self.conv_bn_act(col, gm, 1, 0, act, out=out, res=res, res_mode=res_mode)
+
+    def scale(self, x: Var, gate: torch.Tensor) -> Var:
+        """out = x * gate[n, c] with a constant ``gate`` (f32 [N][C], e.g. RFB's ``scale``); backward d x += d out * gate"""
+        x = self.materialize(x)
+        out = self.scale_channels(x, gate)
+        if self.record and x.need:
+            def bw():
+                if not out.is_set():
+                    return
+                st = _stream()
+                if x.is_set():
+                    tmp = self.new_like(x)
+                    L.call("ydl_scale_channels", x.dt, _p(self._gbuf(out)), out.ld, _p(gate), _p(tmp.t), tmp.ld, x.N, x.H * x.W, x.C, st)
+                    gx, acc = self.grad_target(x)
+                    L.call("ydl_copy2d", x.dt, _p(tmp.t), tmp.ld, _p(gx), x.ld, x.npix, x.C, 1, st)
+                else:
+                    gx, _ = self.grad_target(x)
+                    L.call("ydl_scale_channels", x.dt, _p(self._gbuf(out)), out.ld, _p(gate), _p(gx), x.ld, x.N, x.H * x.W, x.C, st)
+            self.bw.append(bw)
+        return out
+
     def local_attention(self, x: Var, mod) -> Var:
         """AttentionConv / AttentionStem (models/common.py:1509-1627): the bias-free 1x1 projections Q, K, V^0..V^{m-1} of x as
         implicit-GEMM launches into channel blocks of ONE buffer, then the windowed softmax-and-sum (ydl_local_attn_fwd).  ``mod`` is
