@@ -212,6 +212,17 @@ int ydl_sppf_pool_fwd(int dtype, const void* x, int ldx, void* y1, void* y2, voi
 int ydl_sppf_pool_bwd(int dtype, const void* dy1, const void* dy2, const void* dy3, int lddy, const uint8_t* idx1,
                       const uint8_t* idx2, const uint8_t* idx3, void* dx, int lddx, int accumulate,
                       int N, int H, int W, int C, int k, void* stream);
+/* The parallel pyramid of SPP / C3SPP / SPPCSPC (models/common.py:1282-1286, :1439-1446): yi = max-pool(x; ki, stride 1, pad ki/2),
+ * all three of the same x, in one launch per direction, the H x W plane held in LDS.  ki odd, 3..15, any order.  Same values,
+ * index planes and dx as ydl_maxpool_fwd(x -> yi, ki, 1, ki/2) three times and ydl_maxpool_bwd(dy1, idx1, accumulate), (dy2, idx2, 1),
+ * (dy3, idx3, 1), bit for bit; the backward is a gather without atomics.  ydl_spp_pool_supported: 1 when the window sizes are
+ * served and the plane fits (else use those calls); the other two return an error without launching when it is 0. */
+int ydl_spp_pool_supported(int dtype, int H, int W, int C, int k1, int k2, int k3);
+int ydl_spp_pool_fwd(int dtype, const void* x, int ldx, void* y1, void* y2, void* y3, int ldy,
+                     uint8_t* idx1, uint8_t* idx2, uint8_t* idx3, int N, int H, int W, int C, int k1, int k2, int k3, void* stream);
+int ydl_spp_pool_bwd(int dtype, const void* dy1, const void* dy2, const void* dy3, int lddy, const uint8_t* idx1,
+                     const uint8_t* idx2, const uint8_t* idx3, void* dx, int lddx, int accumulate,
+                     int N, int H, int W, int C, int k1, int k2, int k3, void* stream);
 /* resize: mode 0 nearest (src=min(floor(dst*scale),in-1)), 1 bilinear align_corners=False, 2 bilinear
  * align_corners=True.  scale_h/w <= 0 means "derive from sizes" (in/out, or (in-1)/(out-1)). */
 int ydl_resize_fwd(int dtype, int mode, const void* x, int ldx, void* y, int ldy,

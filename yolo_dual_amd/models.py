@@ -26,7 +26,8 @@ import yaml
 from . import _lib as L
 from .modules import (ASPP, RFB, GAM, AttentionConv, AttentionStem, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C2f_DCN, C3, C3_DCN, C3_DCNCommon, C3_DCNV3,
                       C3Common, C3Ghost, C3k2, C3TR, Concat, DWConv, GhostBottleneck, GhostConv, TransformerBlock,
-                      Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region)
+                      Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region,
+                      SPP, C3SPP, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF)
 from .tape import Tape, Var
 
 LOGGER = logging.getLogger("yolo_dual_amd")
@@ -527,12 +528,13 @@ _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": 
                 "nn.Upsample": Upsample, "Upsample": Upsample, "C3_DCNV3": C3_DCNV3, "Bottleneck_DCNV3": Bottleneck_DCNV3,
                 "AttentionConv": AttentionConv, "AttentionStem": AttentionStem, "DWConv": DWConv, "GhostConv": GhostConv,
                 "GhostBottleneck": GhostBottleneck, "C3Ghost": C3Ghost, "C3TR": C3TR, "TransformerBlock": TransformerBlock,
-                "ASPP": ASPP, "RFB": RFB}
+                "ASPP": ASPP, "RFB": RFB, "SPP": SPP, "C3SPP": C3SPP, "SimSPPF": SimSPPF, "SPPCSPC": SPPCSPC,
+                "SPPCSPC_group": SPPCSPC_group, "SimCSPSPPF": SimCSPSPPF}
 
 
 def parse_model(d: dict, ch: List[int], deformable: bool = False):
     """models/yolo.py:299-382 for the block set of this path: resolves module names, applies depth/width gains
-    (``n = max(round(n*gd), 1)``, ``c2 = make_divisible(c2*gw, 8)``), inserts ``n`` for C3 and C3TR (AttentionConv / AttentionStem get none:
+    (``n = max(round(n*gd), 1)``, ``c2 = make_divisible(c2*gw, 8)``), inserts ``n`` for C3 and C3TR (AttentionConv / AttentionStem and the SPP pyramid rows, C3SPP included, get none:
     n > 1 is a Sequential of identical constructions, models/yolo.py:318-329,369), and tags every layer
     with ``.i .f .type .np``.  Returns (nn.Sequential, sorted save-list).  ``deformable``: resolve ``C3_DCN`` to models/common.py's
     DCNv2 block (C3_DCNCommon, n inserted like C3: models/yolo.py:321,327)."""
@@ -547,7 +549,8 @@ def parse_model(d: dict, ch: List[int], deformable: bool = False):
         args = [None if a == "None" else a for a in args]
         n = n_ = max(round(n * gd), 1) if n > 1 else n
         if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3, C3_DCNCommon, AttentionConv, AttentionStem,
-                   DWConv, GhostConv, GhostBottleneck, C3Ghost, C3TR, ASPP, RFB):
+                   DWConv, GhostConv, GhostBottleneck, C3Ghost, C3TR, ASPP, RFB, SPP, C3SPP, SimSPPF, SPPCSPC, SPPCSPC_group,
+                   SimCSPSPPF):
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)

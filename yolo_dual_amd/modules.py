@@ -1109,6 +1109,144 @@ class SPPF(YdlModule):
 
 
 # ----------------------------------------------------------------------------------------------------------
+# SPP pyramid blocks (models/common.py:191-197 C3SPP, :1275-1286 SPP, :1292-1330 SimConv / SimSPPF, :1430-1448 SPPCSPC,
+# :1451-1468 SPPCSPC_group, :1473-1492 SimCSPSPPF)
+# ----------------------------------------------------------------------------------------------------------
+def _odd_windows(name: str, k) -> tuple:
+    ks = tuple(int(v) for v in (k if isinstance(k, (tuple, list)) else (k,)))
+    if any(v < 1 or v % 2 == 0 for v in ks):
+        raise NotImplementedError(f"{name}: max-pool window sizes {ks} are not implemented (odd sizes only: an even k with padding "
+                                  "k // 2 changes the output size, and the reference's concat then fails)")
+    return ks
+
+
+class SPP(YdlModule):
+    """models/common.py:1275-1286: cv2(cat(y, mp_k1(y), mp_k2(y), ...)) with y = cv1(x); the pools are PARALLEL, every one of y
+    (Tape.spp_pools), and write straight into the concat buffer cv1 opened."""
+
+    def __init__(self, c1, c2, k=(5, 9, 13)):
+        super().__init__()
+        self.k = _odd_windows("SPP", k)
+        c_ = c1 // 2
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c_ * (len(self.k) + 1), c2, 1, 1)
+        self.c_ = c_
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        c_, n = self.c_, len(self.k)
+        cat = tape.new(x.N, (n + 1) * c_, x.LH, x.LW)
+        s0 = self.cv1._fwd(tape, x, out=cat.slice(0, c_))
+        tape.spp_pools(s0, self.k, [cat.slice((i + 1) * c_, (i + 2) * c_) for i in range(n)])
+        return self.cv2._fwd(tape, cat, out=out)
+
+
+class C3SPP(C3Common):
+    """models/common.py:191-197: C3 whose ``m`` is one SPP(c_, c_, k).  Note the argument order: k comes before n."""
+
+    def __init__(self, c1, c2, k=(5, 9, 13), n=1, shortcut=True, g=1, e=0.5):
+        if g != 1:
+            raise NotImplementedError(f"C3SPP: groups g={g} is not implemented on the HIP path (g = 1 only)")
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = SPP(self.c_, self.c_, k)
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        c_ = self.c_
+        cat = tape.new(x.N, 2 * c_, x.LH, x.LW)
+        self.m._fwd(tape, self.cv1._fwd(tape, x), out=cat.slice(0, c_))
+        self.cv2._fwd(tape, x, out=cat.slice(c_, 2 * c_))
+        return self.cv3._fwd(tape, cat)
+
+
+class SimConv(Conv):
+    """models/common.py:1292-1313: Conv2d(bias=False, padding kernel_size // 2) -> BatchNorm2d -> ReLU."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride, groups=1, bias=False):
+        if groups != 1:
+            raise NotImplementedError(f"SimConv: groups={groups} is not implemented on the HIP path (groups = 1 only)")
+        if bias:
+            raise NotImplementedError("SimConv: bias=True is not implemented on the HIP path (the convolution in front of a BatchNorm "
+                                      "carries no bias)")
+        super().__init__(in_channels, out_channels, kernel_size, stride, kernel_size // 2, 1, act=nn.ReLU())
+
+
+class SimSPPF(YdlModule):
+    """models/common.py:1315-1330: SPPF on SimConv; the pools are SPPF's chain (Tape.sppf_pools)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=5):
+        super().__init__()
+        self.k, = _odd_windows("SimSPPF", kernel_size)
+        c_ = in_channels // 2
+        self.cv1 = SimConv(in_channels, c_, 1, 1)
+        self.cv2 = SimConv(c_ * 4, out_channels, 1, 1)
+        self.c_ = c_
+
+    _fwd = SPPF._fwd
+
+
+class _CSPPool(YdlModule):
+    """what SPPCSPC and SimCSPSPPF share (models/common.py:1430-1448, :1473-1492): x1 = cv4(cv3(cv1 x)) opens a 4-way concat buffer,
+    ``_pools`` fills its other three slices, y1 = cv6(cv5(buffer)) and y2 = cv2(x) are written into the halves of cv7's input.
+    ``n``, ``shortcut`` and ``g`` are accepted and unused, as in the reference (which never hands ``g`` to a convolution)."""
+
+    def __init__(self, c1, c2, e):
+        super().__init__()
+        c_ = int(2 * c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c1, c_, 1, 1)
+        self.cv3 = Conv(c_, c_, 3, 1)
+        self.cv4 = Conv(c_, c_, 1, 1)
+        self.cv5 = Conv(4 * c_, c_, 1, 1)
+        self.cv6 = Conv(c_, c_, 3, 1)
+        self.cv7 = Conv(2 * c_, c2, 1, 1)
+        self.c_ = c_
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        c_ = self.c_
+        cat = tape.new(x.N, 4 * c_, x.LH, x.LW)
+        x1 = self.cv4._fwd(tape, self.cv3._fwd(tape, self.cv1._fwd(tape, x)), out=cat.slice(0, c_))
+        self._pools(tape, x1, [cat.slice((i + 1) * c_, (i + 2) * c_) for i in range(3)])
+        halves = tape.new(x.N, 2 * c_, x.LH, x.LW)
+        self.cv6._fwd(tape, self.cv5._fwd(tape, cat), out=halves.slice(0, c_))
+        self.cv2._fwd(tape, x, out=halves.slice(c_, 2 * c_))
+        return self.cv7._fwd(tape, halves)
+
+
+class SPPCSPC(_CSPPool):
+    """models/common.py:1430-1448 (YOLOv7): parallel pools of x1 (Tape.spp_pools).  cv5 takes 4 * c_ channels, so ``k`` holds three
+    window sizes."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5, k=(5, 9, 13)):
+        super().__init__(c1, c2, e)
+        self.k = _odd_windows("SPPCSPC", k)
+        if len(self.k) != 3:
+            raise ValueError(f"SPPCSPC: k={k} must hold three window sizes (cv5 reads 4 * c_ channels)")
+
+    def _pools(self, tape: Tape, x1: Var, outs) -> None:
+        tape.spp_pools(x1, self.k, outs)
+
+
+class SimCSPSPPF(_CSPPool):
+    """models/common.py:1473-1492 (YOLOv6 v0.3; SiLU Convs despite the name): SPPF's chain of pools (Tape.sppf_pools)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5, k=5):
+        super().__init__(c1, c2, e)
+        self.k, = _odd_windows("SimCSPSPPF", k)
+
+    def _pools(self, tape: Tape, x1: Var, outs) -> None:
+        tape.sppf_pools(x1, self.k, outs)
+
+
+class SPPCSPC_group(YdlModule):
+    """models/common.py:1451-1468: SPPCSPC whose seven convolutions are all Conv(g=4).  Refused: grouped convolution with
+    1 < groups < channels is not implemented on the HIP path."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5, k=(5, 9, 13)):
+        super().__init__()
+        raise NotImplementedError("SPPCSPC_group: every convolution in it is Conv(g=4), and the HIP path implements groups=1 and "
+                                  "depth-wise groups only")
+
+
+# ----------------------------------------------------------------------------------------------------------
 # dilated context blocks (models/common.py:1336-1361 ASPP, :1366-1384 BasicConv, :1386-1425 RFB)
 # ----------------------------------------------------------------------------------------------------------
 class _Conv2d(_BiasConv2d):

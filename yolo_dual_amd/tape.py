@@ -925,6 +925,50 @@ class Tape:
             self.bw.append(bw)
         return o1, o2, o3
 
+    def spp_pools(self, x: Var, ks: Sequence[int], outs: Sequence[Var]) -> Sequence[Var]:
+        """The parallel pyramid of SPP / SPPCSPC (models/common.py:1282-1286, :1439-1446): outs[i] = max-pool(x; ks[i], stride 1,
+        pad ks[i] // 2), every pool of the same x, into the given destinations (concat slices).  Three pools whose plane fits run as
+        one LDS-resident launch per direction (ydl_spp_pool_fwd / _bwd, bit-identical to the separate pools); any other tuple
+        length, and planes that do not fit, take one ``maxpool`` call per k."""
+        ks = [int(k) for k in ks]
+        if len(ks) != len(outs):
+            raise ValueError(f"spp_pools: {len(ks)} window sizes for {len(outs)} destinations")
+        x = self.materialize(x)
+        fused = (len(ks) == 3 and x.aligned() and all(o.aligned() and o.ld == outs[0].ld and o.dt == x.dt for o in outs)
+                 and all((o.N, o.C, o.H, o.W) == (x.N, x.C, x.H, x.W) for o in outs)
+                 and L.lib().ydl_spp_pool_supported(x.dt, x.H, x.W, x.C, *ks))
+        if not fused:
+            x = self._flat(x)
+            return tuple(self.maxpool(x, k, 1, k // 2, out=o) for k, o in zip(ks, outs))
+        o1, o2, o3 = outs
+        Cp = round_up(x.C, 4 if x.dt == L.YDL_F32 else 8)
+        n = x.N * x.H * x.W * Cp
+        idx = [torch.empty((n,), dtype=torch.uint8, device=self.device) for _ in range(3)] if self.record else [None] * 3
+        L.call("ydl_spp_pool_fwd", x.dt, _p(x.t), x.ld, _p(o1.t), _p(o2.t), _p(o3.t), o1.ld, _p(idx[0]), _p(idx[1]), _p(idx[2]),
+               x.N, x.H, x.W, x.C, *ks, _stream())
+        if self.record:
+            self._use(x)
+
+            def bw():
+                if not x.need:
+                    return
+                st = _stream()
+                if all(o.is_set() for o in outs):
+                    g1, g2, g3 = (self._gbuf(o) for o in outs)
+                    gx, acc = self.grad_target(x)
+                    L.call("ydl_spp_pool_bwd", x.dt, _p(g1), _p(g2), _p(g3), o1.ld, _p(idx[0]), _p(idx[1]), _p(idx[2]),
+                           _p(gx), x.ld, acc, x.N, x.H, x.W, x.C, *ks, st)
+                    return
+                # a slice without a gradient (dead consumer): pool by pool, in the order the fused kernel sums them
+                for k, dst, ix in zip(ks, outs, idx):
+                    if not dst.is_set():
+                        continue
+                    gx, acc = self.grad_target(x)
+                    L.call("ydl_maxpool_bwd", x.dt, _p(self._gbuf(dst)), dst.ld, _p(ix), _p(gx), x.ld, acc,
+                           x.N, x.H, x.W, x.H, x.W, x.C, k, 1, k // 2, st)
+            self.bw.append(bw)
+        return o1, o2, o3
+
     def resize(self, x: Var, Ho: int, Wo: int, mode: int, scale_h: float = 0.0, scale_w: float = 0.0,
                out: Optional[Var] = None) -> Var:
         """mode: L.RESIZE_NEAREST / RESIZE_BILINEAR (align_corners=False) / RESIZE_BILINEAR_AC (True)."""
