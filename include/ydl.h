@@ -49,7 +49,8 @@ void ydl_debug_set(int key, int val);
 /* diagnostics: number of (kernel, device) launch-attribute initialisations done so far */
 int ydl_debug_attr_sets(void);
 /* diagnostics: name of the kernel instantiation the last call of an entry family launched (process-wide);
- * family 0 ydl_conv_fwd, 1 ydl_conv_dgrad, 2 ydl_conv_wgrad, 3 ydl_bn_finalize, 4 ydl_deform_bwd, 5 ydl_deform_gather.
+ * family 0 ydl_conv_fwd, 1 ydl_conv_dgrad, 2 ydl_conv_wgrad, 3 ydl_bn_finalize, 4 ydl_deform_bwd, 5 ydl_deform_gather,
+ * 6 ydl_conv_bwd_pw_bn (which also sets 1 and 2, as ydl_conv_bwd_pw does: the kernel is the same pwbw_kernel).
  * "" if none yet. */
 const char* ydl_debug_last_kernel(int family);
 
@@ -93,6 +94,22 @@ int ydl_conv_dgrad(const ydl_conv_geom* g, int dtype, const void* dy, const void
 int ydl_conv_bwd_pw_supported(const ydl_conv_geom* g, int dtype);
 int ydl_conv_bwd_pw(const ydl_conv_geom* g, int dtype, const void* x, const void* dy, const void* wt, void* dx, int lddx,
                     int accumulate, float* dw, void* stream);
+/* ydl_conv_bwd_pw for a layer whose dy is the result of a BatchNorm backward that nobody else reads: the kernel takes what the
+ * apply pass of ydl_bn_act_bwd_sums takes — the saved pre-activation y (pixel stride ldy), dout, the four coefficient rows, the
+ * COMPLETED replica sums (ydl_bn_act_bwd_reduce_sums has ended) — and forms dy = scale * (dz - sum dz / npix - xhat * sum dz xhat /
+ * npix) itself while the tiles arrive, bit for bit what the apply pass stores; that launch and its three tensor passes disappear
+ * (csrc/igemm.hip: pwbw_kernel<S, ACC, BN>; ydl_debug_last_kernel(6) names the instantiation).  Same geometries as ydl_conv_bwd_pw.  dout is ONE segment of 128 channels (dout1 = sums1 = NULL,
+ * sums0 = [YDL_BN_REPLICAS][2][128]) or TWO segments of 64 channels with pixel strides of their own and sums0 / sums1 =
+ * [YDL_BN_REPLICAS][2][64] each (a fused sibling pair activates its halves into two places; both segments must lie within 4 GiB of
+ * each other); mean / invstd / scale / shift / dgamma / dbeta are rows of 128.  act: YDL_ACT_NONE or YDL_ACT_SILU.  Block 0 stores
+ * (or, accumulate_param_grads != 0, adds) dgamma / dbeta as the apply pass does.  dy_out (optional, pixel stride lddy) also
+ * receives dy, for a second reader.  x, wt, dx, lddx, accumulate, dw: as ydl_conv_bwd_pw. */
+int ydl_conv_bwd_pw_bn_supported(const ydl_conv_geom* g, int dtype);
+int ydl_conv_bwd_pw_bn(const ydl_conv_geom* g, int dtype, const void* x, const void* y, int ldy, const void* dout0, int lddo0,
+                       const void* dout1, int lddo1, const float* mean, const float* invstd, const float* scale, const float* shift,
+                       const float* sums0, const float* sums1, int64_t npix, int act, float* dgamma, float* dbeta,
+                       int accumulate_param_grads, void* dy_out, int lddy, const void* wt, void* dx, int lddx, int accumulate,
+                       float* dw, void* stream);
 /* The input gradient with the BatchNorm backward's REDUCE pass of the layer(s) that produced the convolution's input fused into
  * its epilogue (throughput mode: replica sums, see ydl_bn_act_bwd_sums).  dx — the gradient this call completes, i.e. the `dout` of
  * those layers — is still in registers when it is stored: the epilogue reads the producers' saved pre-activations y once,
@@ -194,6 +211,12 @@ int ydl_bn_act_bwd_apply_sums(int dtype, const void* y, int ldy, const void* dou
                               int res_mode, int act, void* dy, int lddy, void* dres, int lddr,
                               float* dgamma, float* dbeta, int accumulate_param_grads,
                               float* sums, int64_t npix, int C, int Cp, void* stream);
+/* the reduce pass alone, for a layer whose consumer forms dy itself (ydl_conv_bwd_pw_bn): adds (sum dz, sum dz*xhat) into the zeroed
+ * sums and writes (res_mode & YDL_RES_GRAD_ACCUMULATE: adds) the gradient of the residual operand into dres, as the apply pass would
+ * have; dgamma / dbeta are left to the consumer, because the sums are complete only when this kernel has ended */
+int ydl_bn_act_bwd_reduce_sums(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                               const float* mean, const float* invstd, const float* scale, const float* shift,
+                               int res_mode, int act, void* dres, int lddr, float* sums, int64_t npix, int C, int Cp, void* stream);
 
 /* ---- spatial ops (NHWC, channel-vectorised) -------------------------------------------------------- */
 /* max pool (k,s,p), -inf padding; idx (uint8 window offset of the arg-max, first max in scan order) is

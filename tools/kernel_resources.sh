@@ -40,6 +40,8 @@ wgrad3s_kernelILi128ELi32ELi4ELi4E 4 0
 wgrad3s_kernelILi64ELi32ELi4ELi4E 4 0
 pwbw_kernelILi5ELb0E 5 0
 pwbw_kernelILi4ELb1E 5 0
+pwbw_kernelILi4ELb0E 3 0
+pwbw_kernelILi3ELb1E 3 0
 wgrad3_kernelILi128E 3 0
 '
 bad=0

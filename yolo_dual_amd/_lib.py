@@ -54,6 +54,9 @@ SIGNATURES = {
     "ydl_conv_dgrad_bnred": (_i, [_G, _i, _vp, _vp, _vp, _i, _R, _vp]),
     "ydl_conv_bwd_pw_supported": (_i, [_G, _i]),
     "ydl_conv_bwd_pw": (_i, [_G, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "ydl_conv_bwd_pw_bn_supported": (_i, [_G, _i]),
+    "ydl_conv_bwd_pw_bn": (_i, [_G, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _i,
+                                _vp, _vp, _i, _i, _vp, _vp]),
     "ydl_conv_wgrad": (_i, [_G, _i, _vp, _vp, _vp, _vp]),
     "ydl_conv_wgrad_ws_bytes": (_i64, [_G, _i]),
     "ydl_conv_wgrad_det": (_i, [_G, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -69,6 +72,7 @@ SIGNATURES = {
                                  _vp]),
     "ydl_bn_act_bwd_apply_sums": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i64, _i, _i,
                                  _vp]),
+    "ydl_bn_act_bwd_reduce_sums": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i64, _i, _i, _vp]),
     "ydl_bn_bwd_ws_bytes": (_i64, [_i64, _i]),
     "ydl_bn_act_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i,
                             _vp, _vp, _i, _vp, _i64, _i, _i, _vp]),
@@ -202,7 +206,7 @@ def debug_epoch() -> int:
 
 def last_kernel(family: int) -> str:
     """name of the kernel instantiation the last call of an entry family launched (0 fwd, 1 dgrad, 2 wgrad, 3 bn_finalize,
-    4 deform_bwd, 5 deform_gather)"""
+    4 deform_bwd, 5 deform_gather, 6 conv_bwd_pw_bn)"""
     return lib().ydl_debug_last_kernel(family).decode()
 
 
@@ -243,6 +247,8 @@ def profile_end():
             if getattr(g, "_both", False):
                 flops *= 2.0
                 nbytes += float(g.N) * g.Hi * g.Wi * g.Cin * es + wb * 4
+            if getattr(g, "_bn", False):          # dy is formed from y AND dout: one more pass over the output-side tensor
+                nbytes += float(g.N) * g.Ho * g.Wo * g.Cout * es
         elif isinstance(g, float):
             nbytes, g = g, None
         d = {"name": name, "ms": e0.elapsed_time(e1), "flops": flops, "bytes": nbytes}
@@ -295,13 +301,15 @@ def call(name: str, *args):
     e1.record()
     g = None
     if name in ("ydl_conv_fwd", "ydl_conv_fwd_sums", "ydl_conv_dgrad", "ydl_conv_dgrad_bnred", "ydl_conv_wgrad", "ydl_conv_wgrad_det",
-                "ydl_conv_bwd_pw"):
+                "ydl_conv_bwd_pw", "ydl_conv_bwd_pw_bn"):
         src = args[0]._obj
         g = ConvGeom(*[getattr(src, f) for f, _ in ConvGeom._fields_])
         g._es = 4 if args[1] == YDL_F32 else 2
-        g._both = name == "ydl_conv_bwd_pw"          # input AND weight gradient: twice the FLOPs, x + dy + dx + dw bytes
-        g._kernel = last_kernel(1 if ("dgrad" in name or "bwd_pw" in name) else 2 if "wgrad" in name else 0)
-        g._acc = int(args[5]) if "dgrad" in name else int(args[6]) if name.startswith("ydl_conv_fwd") else int(args[7]) if g._both else 0
+        g._bn = name == "ydl_conv_bwd_pw_bn"         # ... with dy formed on the way in: y + dout + x + dx + dw bytes
+        g._both = g._bn or name == "ydl_conv_bwd_pw"     # input AND weight gradient: twice the FLOPs, x + dy + dx + dw bytes
+        g._kernel = last_kernel(6 if g._bn else 1 if ("dgrad" in name or "bwd_pw" in name) else 2 if "wgrad" in name else 0)
+        g._acc = (int(args[25]) if g._bn else int(args[5]) if "dgrad" in name else int(args[6]) if name.startswith("ydl_conv_fwd")
+                  else int(args[7]) if g._both else 0)
     elif name == "ydl_bn_act_fwd":          # algorithmic bytes: y (+ residual) read once, out written once
         es = 4 if args[0] == YDL_F32 else 2
         g = float(args[11]) * args[12] * es * (2 + (1 if args[7] else 0))
@@ -314,6 +322,9 @@ def call(name: str, *args):
     elif name == "ydl_bn_act_bwd_sums":
         es = 4 if args[0] == YDL_F32 else 2
         g = float(args[21]) * args[23] * es * _bn_bwd_passes(args[11], args[12], args[15])
+    elif name == "ydl_bn_act_bwd_reduce_sums":     # y and dout read once; no dy
+        es = 4 if args[0] == YDL_F32 else 2
+        g = float(args[16]) * args[18] * es * (_bn_bwd_passes(args[11], args[12], args[13]) - 1)
     elif name in ("ydl_dcnv3_fwd", "ydl_dcnv3_bwd"):
         # algorithmic bytes: input, offsets, masks (and grad_output) read once; output / the three f32 gradients written once
         es = 4 if args[0] == YDL_F32 else 2

@@ -148,6 +148,17 @@ def set_fuse_pw_backward(on: bool) -> None:
     _STATE["fuse_pw_backward"] = bool(on)
 
 
+def fuse_bn_pw_backward() -> bool:
+    """where a layer's dy is read by ydl_conv_bwd_pw alone: only the reduce pass of the BatchNorm backward is launched
+    (ydl_bn_act_bwd_reduce_sums) and the one-pass kernel forms dy from y and dout itself (ydl_conv_bwd_pw_bn); bf16 throughput
+    mode only, on by default"""
+    return _STATE.get("fuse_bn_pw_backward", True)
+
+
+def set_fuse_bn_pw_backward(on: bool) -> None:
+    _STATE["fuse_bn_pw_backward"] = bool(on)
+
+
 def set_dcnv3_border_rule(rule: str) -> None:
     """Which of the reference's two answers a DCNv3 sampling position EXACTLY at -1 gets (include/ydl.h: ydl_dcnv3_set_border_rule):
     "core" (default) = inside, as the pure-PyTorch core `dcnv3_core_pytorch` and the oracle have it (functions/dcnv3_func.py:148-189);

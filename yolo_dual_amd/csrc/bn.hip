@@ -291,18 +291,7 @@ __device__ __forceinline__ void dz_xhat_q(const uint4& yq, const uint4& dq, cons
     unpack16<T>(dq, dv);
     if (ACT == YDL_ACT_RELU) unpack16<T>(oq, ov);
 #pragma unroll
-    for (int e = 0; e < V; ++e) {
-        float z = yv[e] * sc[e] + sf[e];
-        float d = dv[e];
-        if (ACT == YDL_ACT_SILU) {
-            float sg = sigmoid_f(z);
-            d *= sg * (1.f + z * (1.f - sg));
-        } else if (ACT == YDL_ACT_RELU) {
-            d = ov[e] > 0.f ? d : 0.f;
-        }
-        dz[e] = d;
-        xh[e] = (yv[e] - mu[e]) * is[e];
-    }
+    for (int e = 0; e < V; ++e) bn_dz_xhat_1<ACT>(yv[e], dv[e], ACT == YDL_ACT_RELU ? ov[e] : 0.f, sc[e], sf[e], mu[e], is[e], dz[e], xh[e]);
 }
 
 template <typename T, int ACT>
@@ -315,18 +304,7 @@ __device__ __forceinline__ void dz_xhat(const T* y, const T* dout, const T* out,
     unpack16<T>(*(const uint4*)(dout + pix * lddo + c), dv);
     if (ACT == YDL_ACT_RELU) unpack16<T>(*(const uint4*)(out + pix * ldo + c), ov);
 #pragma unroll
-    for (int e = 0; e < V; ++e) {
-        float z = yv[e] * sc[e] + sf[e];
-        float d = dv[e];
-        if (ACT == YDL_ACT_SILU) {
-            float sg = sigmoid_f(z);
-            d *= sg * (1.f + z * (1.f - sg));
-        } else if (ACT == YDL_ACT_RELU) {
-            d = ov[e] > 0.f ? d : 0.f;
-        }
-        dz[e] = d;
-        xh[e] = (yv[e] - mu[e]) * is[e];
-    }
+    for (int e = 0; e < V; ++e) bn_dz_xhat_1<ACT>(yv[e], dv[e], ACT == YDL_ACT_RELU ? ov[e] : 0.f, sc[e], sf[e], mu[e], is[e], dz[e], xh[e]);
 }
 
 template <typename T, int ACT>
@@ -460,7 +438,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
         float dz[V], xh[V], o[V], dv[V];
         dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dv);
 #pragma unroll
-        for (int e = 0; e < V; ++e) o[e] = sc[e] * (dz[e] - kb[e] - xh[e] * kg[e]);
+        for (int e = 0; e < V; ++e) o[e] = bn_bwd_dy_1(sc[e], dz[e], xh[e], kb[e], kg[e]);
         *(uint4*)(dy + pix * lddy + L.c) = pack16<T>(o);
         if (RESM != 0) {                                  // the residual branch's gradient in the same pass (no separate copy kernel)
             T* rp = dres + pix * lddr + L.c;
@@ -678,12 +656,30 @@ extern "C" int ydl_bn_act_fwd_sums(int dtype, const void* y, int ldy, const floa
 
 // reduce pass: as bn_bwd_reduce_kernel, but the CTA's per-channel (sum dz, sum dz*xhat) are ADDED to replica (blockIdx.x & 7)
 // of sums; the final LDS pass is laid out one channel per thread so that a wave-instruction adds 256 contiguous bytes
-template <typename T, int ACT>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_sums_kernel(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int lddo,
-                                                                 const T* __restrict__ out, int ldo,
-                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                 const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                 float* __restrict__ sums, long long npix, int Cp) {
+// RESM != 0 (ydl_bn_act_bwd_reduce_sums: no apply launch follows, the consumer of dy forms it itself) also writes the gradient of the
+// residual operand, as the apply kernel does: dout itself (1: joined after the activation) or dz (2: before it), optionally added to
+// what dres holds.  The sums are added in the same order either way.
+template <typename T, int RESM>
+__device__ __forceinline__ void bn_bwd_store_dres(T* rp, const float* dv, const float* dz, int dres_acc) {
+    constexpr int V = ET<T>::V;
+    float r[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) r[e] = RESM == 1 ? dv[e] : dz[e];
+    if (dres_acc) {
+        float old[V];
+        unpack16<T>(*(const uint4*)rp, old);
+#pragma unroll
+        for (int e = 0; e < V; ++e) r[e] += old[e];
+    }
+    *(uint4*)rp = pack16<T>(r);
+}
+template <typename T, int ACT, int RESM>
+__device__ __forceinline__ void bn_bwd_reduce_sums_body(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int lddo,
+                                                        const T* __restrict__ out, int ldo,
+                                                        const float* __restrict__ scale, const float* __restrict__ shift,
+                                                        const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                        float* __restrict__ sums, long long npix, int Cp,
+                                                        T* __restrict__ dres, int lddr, int dres_acc) {
     constexpr int V = ET<T>::V;
     const Lay L = make_lay<V>(Cp);
     float sb[V], sg[V], sc[V], sf[V], mu[V], is[V];
@@ -703,15 +699,26 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_sums_kernel(const T* __rest
             dz_xhat_q<T, ACT>(y0, d0, o0, sc, sf, mu, is, dz, xh);
 #pragma unroll
             for (int e = 0; e < V; ++e) { sb[e] += dz[e]; sg[e] += dz[e] * xh[e]; }
+            if (RESM != 0) {
+                float dv[V];
+                unpack16<T>(d0, dv);
+                bn_bwd_store_dres<T, RESM>(dres + pix * lddr + L.c, dv, dz, dres_acc);
+            }
             dz_xhat_q<T, ACT>(y1, d1, o1, sc, sf, mu, is, dz, xh);
 #pragma unroll
             for (int e = 0; e < V; ++e) { sb[e] += dz[e]; sg[e] += dz[e] * xh[e]; }
+            if (RESM != 0) {
+                float dv[V];
+                unpack16<T>(d1, dv);
+                bn_bwd_store_dres<T, RESM>(dres + (pix + stride) * lddr + L.c, dv, dz, dres_acc);
+            }
         }
         for (; pix < npix; pix += stride) {
             float dz[V], xh[V], dvr[V];
             dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dvr);
 #pragma unroll
             for (int e = 0; e < V; ++e) { sb[e] += dz[e]; sg[e] += dz[e] * xh[e]; }
+            if (RESM != 0) bn_bwd_store_dres<T, RESM>(dres + pix * lddr + L.c, dvr, dz, dres_acc);
         }
     }
     __shared__ float red[256 * 2 * 8];
@@ -770,6 +777,24 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_sums_kernel(const T* __rest
     }
 }
 
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_sums_kernel(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int lddo,
+                                                                 const T* __restrict__ out, int ldo,
+                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                 const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                 float* __restrict__ sums, long long npix, int Cp) {
+    bn_bwd_reduce_sums_body<T, ACT, 0>(y, ldy, dout, lddo, out, ldo, scale, shift, mean, invstd, sums, npix, Cp, nullptr, 0, 0);
+}
+template <typename T, int ACT, int RESM>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_res_sums_kernel(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int lddo,
+                                                                     const T* __restrict__ out, int ldo,
+                                                                     const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                     const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                     float* __restrict__ sums, long long npix, int Cp,
+                                                                     T* __restrict__ dres, int lddr, int dres_acc) {
+    bn_bwd_reduce_sums_body<T, ACT, RESM>(y, ldy, dout, lddo, out, ldo, scale, shift, mean, invstd, sums, npix, Cp, dres, lddr, dres_acc);
+}
+
 template <typename T, int ACT, int RESM>
 __global__ __launch_bounds__(256) void bn_bwd_apply_sums_kernel(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int lddo,
                                                                 const T* __restrict__ out, int ldo,
@@ -823,22 +848,26 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_sums_kernel(const T* __restr
         float dz[V], xh[V], o[V], dv[V];
         dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dv);
 #pragma unroll
-        for (int e = 0; e < V; ++e) o[e] = sc[e] * (dz[e] - kb[e] - xh[e] * kg[e]);
+        for (int e = 0; e < V; ++e) o[e] = bn_bwd_dy_1(sc[e], dz[e], xh[e], kb[e], kg[e]);
         *(uint4*)(dy + pix * lddy + L.c) = pack16<T>(o);
-        if (RESM != 0) {
-            T* rp = dres + pix * lddr + L.c;
-            float r[V];
-#pragma unroll
-            for (int e = 0; e < V; ++e) r[e] = RESM == 1 ? dv[e] : dz[e];
-            if (dres_acc) {
-                float old[V];
-                unpack16<T>(*(const uint4*)rp, old);
-#pragma unroll
-                for (int e = 0; e < V; ++e) r[e] += old[e];
-            }
-            *(uint4*)rp = pack16<T>(r);
-        }
+        if (RESM != 0) bn_bwd_store_dres<T, RESM>(dres + pix * lddr + L.c, dv, dz, dres_acc);
     }
+}
+
+// grids of the replica-sums backward: reduce (g1) and apply (g3)
+static void bwd_sums_grids(int64_t npix, int Cp, int V, dim3& g1, dim3& g3) {
+    g1 = lay_grid(npix, Cp, V, BWD_MAX_PARTIALS);
+    g3 = lay_grid(npix, Cp, V, 256 * 8);
+    // small tensors (40^2 / 20^2 layers): no more CTAs than pixel-row passes of eight (reduce: four 2-pixel iterations and an
+    // eighth of the per-CTA atomic passes) / four (apply) — every CTA pays a coefficient prologue of about 2 us
+    // (tools/bn_bench.py: 6400 x 512 19.8 -> 14.8 us, 6400 x 1024 26.5 -> 22.0 us; no change from 25 600 pixels up)
+    static const int small = getenv("YDL_BN_SMALLGRID") ? atoi(getenv("YDL_BN_SMALLGRID")) : 1;
+    static const int f1 = getenv("YDL_BN_SG_REDUCE") ? atoi(getenv("YDL_BN_SG_REDUCE")) : 8;
+    static const int f3 = getenv("YDL_BN_SG_APPLY") ? atoi(getenv("YDL_BN_SG_APPLY")) : 4;
+    const int cpp = Cp / V, cpb = cpp < 256 ? cpp : 256, R = 256 / cpb;
+    const long long w1 = (npix + (long long)R * f1 - 1) / ((long long)R * f1), w3 = (npix + (long long)R * f3 - 1) / ((long long)R * f3);
+    if (small && w1 < (long long)g1.x) g1.x = (unsigned)(w1 < 1 ? 1 : w1);
+    if (small && w3 < (long long)g3.x) g3.x = (unsigned)(w3 < 1 ? 1 : w3);
 }
 
 static int bn_act_bwd_sums_impl(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
@@ -859,20 +888,8 @@ static int bn_act_bwd_sums_impl(int dtype, const void* y, int ldy, const void* d
     YDL_CHECK(aligned16(y) && aligned16(dout) && aligned16(dy) && aligned16(sums), "16-byte alignment");
     YDL_CHECK(act == YDL_ACT_NONE || act == YDL_ACT_SILU || act == YDL_ACT_RELU, "unknown activation");
     hipStream_t st = (hipStream_t)stream;
-    dim3 g1 = lay_grid(npix, Cp, V, BWD_MAX_PARTIALS);
-    dim3 g3 = lay_grid(npix, Cp, V, 256 * 8);
-    {
-        // small tensors (40^2 / 20^2 layers): no more CTAs than pixel-row passes of eight (reduce: four 2-pixel iterations and an
-        // eighth of the per-CTA atomic passes) / four (apply) — every CTA pays a coefficient prologue of about 2 us
-        // (tools/bn_bench.py: 6400 x 512 19.8 -> 14.8 us, 6400 x 1024 26.5 -> 22.0 us; no change from 25 600 pixels up)
-        static const int small = getenv("YDL_BN_SMALLGRID") ? atoi(getenv("YDL_BN_SMALLGRID")) : 1;
-        static const int f1 = getenv("YDL_BN_SG_REDUCE") ? atoi(getenv("YDL_BN_SG_REDUCE")) : 8;
-        static const int f3 = getenv("YDL_BN_SG_APPLY") ? atoi(getenv("YDL_BN_SG_APPLY")) : 4;
-        const int cpp = Cp / V, cpb = cpp < 256 ? cpp : 256, R = 256 / cpb;
-        const long long w1 = (npix + (long long)R * f1 - 1) / ((long long)R * f1), w3 = (npix + (long long)R * f3 - 1) / ((long long)R * f3);
-        if (small && w1 < (long long)g1.x) g1.x = (unsigned)(w1 < 1 ? 1 : w1);
-        if (small && w3 < (long long)g3.x) g3.x = (unsigned)(w3 < 1 ? 1 : w3);
-    }
+    dim3 g1, g3;
+    bwd_sums_grids(npix, Cp, V, g1, g3);
 #define YDL_BS_APPLY(T, A, RM)                                                                                                     \
     bn_bwd_apply_sums_kernel<T, A, RM><<<g3, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale, shift, \
                                                            mean, invstd, sums, (T*)dy, lddy, (T*)dres, lddr, dres_acc, dgamma, dbeta, \
@@ -913,4 +930,50 @@ extern "C" int ydl_bn_act_bwd_apply_sums(int dtype, const void* y, int ldy, cons
                                          float* sums, int64_t npix, int C, int Cp, void* stream) {
     return bn_act_bwd_sums_impl(dtype, y, ldy, dout, lddo, out, ldo, mean, invstd, scale, shift, res_mode, act, dy, lddy, dres, lddr,
                                 dgamma, dbeta, accumulate_param_grads, sums, npix, C, Cp, stream, false);
+}
+
+// The reduce pass alone, for a layer whose dy is formed by the kernel that consumes it (ydl_conv_bwd_pw_bn): (sum dz, sum dz * xhat)
+// are ADDED to the zeroed replica slab, and the gradient of a residual operand, which the apply launch would have written, is
+// written here.  dgamma / dbeta are NOT written: the sums are complete only when this kernel has ended, the consumer finishes them.
+extern "C" int ydl_bn_act_bwd_reduce_sums(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                                          const float* mean, const float* invstd, const float* scale, const float* shift,
+                                          int res_mode, int act, void* dres, int lddr, float* sums, int64_t npix, int C, int Cp,
+                                          void* stream) {
+    const int dres_acc = (res_mode & YDL_RES_GRAD_ACCUMULATE) ? 1 : 0;
+    const int rmode = res_mode & 15;
+    YDL_CHECK(dtype == YDL_F32 || dtype == YDL_BF16, "bad dtype");
+    YDL_CHECK(rmode == YDL_RES_NONE || rmode == YDL_RES_AFTER_ACT || rmode == YDL_RES_BEFORE_ACT, "unknown residual mode");
+    const int resm = dres == nullptr ? 0 : (rmode == YDL_RES_AFTER_ACT ? 1 : 2);
+    YDL_CHECK(dres == nullptr || rmode != YDL_RES_NONE, "dres given without a residual mode");
+    YDL_CHECK(dres == nullptr || (lddr >= Cp && aligned16(dres)), "dres must be 16-byte aligned with a stride covering Cp");
+    const int V = dtype == YDL_F32 ? 4 : 8;
+    YDL_CHECK(y && dout && mean && invstd && scale && shift && sums, "null pointer");
+    YDL_CHECK(act != YDL_ACT_RELU || out != nullptr, "RELU backward needs the saved output");
+    YDL_CHECK(npix > 0 && Cp > 0 && Cp % V == 0 && C <= Cp && ldy >= Cp && lddo >= Cp, "bad channel geometry");
+    YDL_CHECK(aligned16(y) && aligned16(dout) && aligned16(sums), "16-byte alignment");
+    YDL_CHECK(act == YDL_ACT_NONE || act == YDL_ACT_SILU || act == YDL_ACT_RELU, "unknown activation");
+    hipStream_t st = (hipStream_t)stream;
+    dim3 g1, g3;
+    bwd_sums_grids(npix, Cp, V, g1, g3);
+#define YDL_BR_RES(T, A, RM)                                                                                                            \
+    bn_bwd_reduce_res_sums_kernel<T, A, RM><<<g1, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale, shift, \
+                                                                mean, invstd, sums, npix, Cp, (T*)dres, lddr, dres_acc)
+#define YDL_BR_LAUNCH(T, A)                                                                                                        \
+    do {                                                                                                                           \
+        if (resm == 0)                                                                                                             \
+            bn_bwd_reduce_sums_kernel<T, A><<<g1, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale, \
+                                                                shift, mean, invstd, sums, npix, Cp);                              \
+        else if (resm == 1) YDL_BR_RES(T, A, 1);                                                                                   \
+        else YDL_BR_RES(T, A, 2);                                                                                                  \
+    } while (0)
+#define YDL_BR_ACT(T)                                                   \
+    do {                                                                \
+        if (act == YDL_ACT_SILU) YDL_BR_LAUNCH(T, YDL_ACT_SILU);        \
+        else if (act == YDL_ACT_RELU) YDL_BR_LAUNCH(T, YDL_ACT_RELU);   \
+        else YDL_BR_LAUNCH(T, YDL_ACT_NONE);                            \
+    } while (0)
+    if (dtype == YDL_F32) YDL_BR_ACT(float);
+    else YDL_BR_ACT(bf16_t);
+    YDL_LAUNCH_CHECK();
+    return 0;
 }

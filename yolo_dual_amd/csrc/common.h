@@ -68,24 +68,37 @@ __device__ __forceinline__ float sigmoid_f(float z) {
 }
 __device__ __forceinline__ float silu_f(float z) { return z * sigmoid_f(z); }
 
-// BatchNorm backward, per 16-byte bf16 chunk: dz = dout * act'(y*scale + shift), xhat = (y - mean) * invstd (bn.hip: dz_xhat_q;
-// also used by the convolution epilogues that fuse the reduce pass: ydl_conv_dgrad_bnred)
-__device__ __forceinline__ void bn_dz_xhat_bf16x8(const uint4& yq, const uint4& dq, const float* sc, const float* sf, const float* mu,
-                                                  const float* is, bool silu, float* dz, float* xh) {
-    float yv[8], dv[8];
+// BatchNorm backward of ONE element, the only definition of its arithmetic (the streaming kernels of bn.hip and the convolution
+// backward kernels that form dy on the way in, igemm.hip: pwbw_kernel<S, ACC, BN>, must agree to the bit):
+//   dz = dout * act'(y*scale + shift),  xhat = (y - mean) * invstd      (ov: the stored output, read for the ReLU mask only)
+//   dy = scale * (dz - kb - xhat * kg)  with kb = sum(dz) / M, kg = sum(dz * xhat) / M
+template <int ACT>
+__device__ __forceinline__ void bn_dz_xhat_1(float yv, float d, float ov, float sc, float sf, float mu, float is, float& dz, float& xh) {
+    float z = yv * sc + sf;
+    if (ACT == YDL_ACT_SILU) {
+        float sg = sigmoid_f(z);
+        d *= sg * (1.f + z * (1.f - sg));
+    } else if (ACT == YDL_ACT_RELU) {
+        d = ov > 0.f ? d : 0.f;
+    }
+    dz = d;
+    xh = (yv - mu) * is;
+}
+__device__ __forceinline__ float bn_bwd_dy_1(float sc, float dz, float xh, float kb, float kg) { return sc * (dz - kb - xh * kg); }
+// the same per 16-byte bf16 chunk (ACT NONE or SILU): the eight dy values of one pixel, rounded to bf16
+template <int ACT>
+__device__ __forceinline__ uint4 bn_bwd_dy_bf16x8(const uint4& yq, const uint4& dq, const float* sc, const float* sf, const float* mu,
+                                                  const float* is, const float* kb, const float* kg) {
+    float yv[8], dv[8], o[8];
     unpack16<bf16_t>(yq, yv);
     unpack16<bf16_t>(dq, dv);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float z = yv[e] * sc[e] + sf[e];
-        float d = dv[e];
-        if (silu) {
-            const float sg = sigmoid_f(z);
-            d *= sg * (1.f + z * (1.f - sg));
-        }
-        dz[e] = d;
-        xh[e] = (yv[e] - mu[e]) * is[e];
+        float dz, xh;
+        bn_dz_xhat_1<ACT>(yv[e], dv[e], 0.f, sc[e], sf[e], mu[e], is[e], dz, xh);
+        o[e] = bn_bwd_dy_1(sc[e], dz, xh, kb[e], kg[e]);
     }
+    return pack16<bf16_t>(o);
 }
 
 // Sum over the 64 lanes with DPP row shifts + row broadcasts (six v_add_f32_dpp, no LDS crossbar): the total is valid in LANE 63 ONLY.

@@ -33,14 +33,14 @@ extern "C" int ydl_debug_attr_sets(void) { return g_attr_sets.load(); }
 // test hook: forget which devices were initialised for the tag words is not possible from here (they are call-site
 // statics); instead tests switch devices.  On a one-GPU box ydl_debug_attr_sets() is compared before/after a first launch.
 
-static std::atomic<const char*> g_last_kernel[6];
+static std::atomic<const char*> g_last_kernel[7];
 void ydl_note_kernel(int family, const char* name) {
-    if (family >= 0 && family < 6) g_last_kernel[family].store(name, std::memory_order_relaxed);
+    if (family >= 0 && family < 7) g_last_kernel[family].store(name, std::memory_order_relaxed);
 }
-// family: 0 conv_fwd, 1 conv_dgrad, 2 conv_wgrad, 3 bn_finalize, 4 deform_bwd, 5 deform_gather.  Returns a static string naming the kernel instantiation the
+// family: 0 conv_fwd, 1 conv_dgrad, 2 conv_wgrad, 3 bn_finalize, 4 deform_bwd, 5 deform_gather, 6 conv_bwd_pw_bn.  Returns a static string naming the kernel instantiation the
 // last call of that family launched (process-wide, diagnostics for the parity tests only), or "" if none yet.
 extern "C" const char* ydl_debug_last_kernel(int family) {
-    if (family < 0 || family >= 6) return "";
+    if (family < 0 || family >= 7) return "";
     const char* s = g_last_kernel[family].load(std::memory_order_relaxed);
     return s ? s : "";
 }

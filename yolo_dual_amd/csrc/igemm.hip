@@ -4201,22 +4201,75 @@ struct PwbwArgs {
     unsigned bytesX, bytesY, bytesDX, bytesWt;
 };
 #define PWBW_SP 32
-template <int S, bool ACC>
-__global__ __launch_bounds__(512, 2) void pwbw_kernel(const PwbwArgs p) {
+struct PwbwBnArgs {
+    PwbwArgs c;                     // c.dY is y, c.ldy its pixel stride
+    const bf16_t* dO; bf16_t* dYo;  // dout resource base (the lower segment pointer), optional dy_out
+    const float *mean, *invstd, *scale, *shift, *sums0, *sums1;
+    float *dgamma, *dbeta;
+    unsigned segoff[2], bytesDO, bytesDYo;
+    int lddo[2], lddyo, nseg, acc_param;
+    float invM;
+};
+__device__ __forceinline__ const PwbwArgs& pwbw_core(const PwbwArgs& a) { return a; }
+__device__ __forceinline__ const PwbwArgs& pwbw_core(const PwbwBnArgs& a) { return a.c; }
+// BN = 0: dy comes from memory (ydl_conv_bwd_pw, A = PwbwArgs).  BN = 1 + activation (YDL_ACT_NONE / YDL_ACT_SILU): dy is formed from y
+// and dout in the kernel (ydl_conv_bwd_pw_bn, A = PwbwBnArgs; see the comment in front of that entry point)
+template <int S, bool ACC, int BN = 0, typename A = PwbwArgs>
+__global__ __launch_bounds__(512, BN ? 1 : 2) void pwbw_kernel(const A pa) {
+    const PwbwArgs& p = pwbw_core(pa);
+    constexpr int ACT = BN - 1;
     constexpr int SP = PWBW_SP;
-    constexpr int YB = SP * 256;                          // one 32-row tile
-    constexpr int NT = ACC ? 3 : 2;                       // tiles per stage: dy, x, [old dx]
+    constexpr int YB = SP * 256;
+    constexpr int OD = BN ? 3 : 2;                        // tiles per stage: dy (BN: y, which becomes dy), x, [BN: dout,] [ACC: old dx]
+    constexpr int NT = OD + (ACC ? 1 : 0);
     constexpr int STAGE = NT * YB;
-    constexpr int LOPS = NT + 1;                          // vector-memory operations per thread and stage: NT DMAs + one store
-    constexpr int NWAIT = (S - 2) * LOPS + 1;             // younger than a stage's DMAs when its turn comes: its own store + S - 2 stages
+    constexpr int LOPS = NT + (BN ? 2 : 1);               // vector-memory operations per thread and stage: NT DMAs + the dx store [+ the dy_out store]
+    // younger than a stage's DMAs when its turn comes.  BN = 0: its own store + S - 2 stages.  BN: the stage is needed one iteration
+    // earlier, for the transform (derivation in front of ydl_conv_bwd_pw_bn)
+    constexpr int NWAIT0 = (S - 2) * LOPS + 1;
+    constexpr int NWAIT = BN ? (S - 3) * LOPS + 2 : (S - 2) * LOPS + 1;
+    static_assert(S >= 3, "the transform runs one stage ahead of compute()");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const sWt = smem + S * STAGE;          // [128 ci][256 B of co], chunk q of row r at slot q ^ (r & 15)
     unsigned char* const sSt = sWt + 128 * 256;           // [2][32 px][256 B of ci], chunk q of row r at slot q ^ (r & 15)
+    [[maybe_unused]] float* const sK = (float*)(sSt + 2 * SP * 256);       // BN: [6][128] scale, shift, mean, invstd, kb, kg
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int pbeg = blockIdx.x * p.chunk;
     const int pend = min(p.M, pbeg + p.chunk);
+    const int r = t >> 4, q = t & 15;
+    const unsigned qlog = (unsigned)((((q >> 1) ^ w3f<256>(r)) << 1) | (q & 1)) << 4;
+    // ---- BN: per-channel constants of this thread's eight channels, BEFORE the first DMA (the compiler's waits for these loads then
+    // drain nothing)
+    [[maybe_unused]] float sc[8], sf[8], mu[8], is[8], kb[8], kg[8];
+    if constexpr (BN != 0) {
+    const int ch0 = (int)(qlog >> 4) * 8;
+    if (t < 128) {
+        const int seg = pa.nseg == 2 ? t >> 6 : 0, cs = pa.nseg == 2 ? 64 : 128, c = t - seg * 64;
+        const float* sums = seg ? pa.sums1 : pa.sums0;
+        double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+        for (int rr = 0; rr < YDL_BN_REPLICAS; ++rr) {
+            s1 += (double)sums[(size_t)(2 * rr) * cs + c];
+            s2 += (double)sums[(size_t)(2 * rr + 1) * cs + c];
+        }
+        const float db = (float)s1, dg = (float)s2;
+        if (blockIdx.x == 0) {
+            if (pa.dbeta) pa.dbeta[t] = (pa.acc_param ? pa.dbeta[t] : 0.f) + db;
+            if (pa.dgamma) pa.dgamma[t] = (pa.acc_param ? pa.dgamma[t] : 0.f) + dg;
+        }
+        sK[t] = pa.scale[t]; sK[128 + t] = pa.shift[t]; sK[256 + t] = pa.mean[t]; sK[384 + t] = pa.invstd[t];
+        sK[512 + t] = db * pa.invM; sK[640 + t] = dg * pa.invM;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        sc[e] = sK[ch0 + e]; sf[e] = sK[128 + ch0 + e]; mu[e] = sK[256 + ch0 + e]; is[e] = sK[384 + ch0 + e];
+        kb[e] = sK[512 + ch0 + e]; kg[e] = sK[640 + ch0 + e];
+    }
+    }
     u32x4 rsX, rsY, rsD, rsW;
+    [[maybe_unused]] u32x4 rsO, rsYo;
     {
         const unsigned long long px = (unsigned long long)p.X, py = (unsigned long long)p.dY, pd = (unsigned long long)p.dX,
                                  pw = (unsigned long long)p.Wt;
@@ -4224,41 +4277,69 @@ __global__ __launch_bounds__(512, 2) void pwbw_kernel(const PwbwArgs p) {
         rsY = u32x4{(unsigned)py, (unsigned)(py >> 32) & 0xffffu, p.bytesY, 0x00020000u};
         rsD = u32x4{(unsigned)pd, (unsigned)(pd >> 32) & 0xffffu, p.bytesDX, 0x00020000u};
         rsW = u32x4{(unsigned)pw, (unsigned)(pw >> 32) & 0xffffu, p.bytesWt, 0x00020000u};
+        if constexpr (BN != 0) {
+            const unsigned long long po = (unsigned long long)pa.dO, pyo = (unsigned long long)pa.dYo;
+            rsO = u32x4{(unsigned)po, (unsigned)(po >> 32) & 0xffffu, pa.bytesDO, 0x00020000u};
+            rsYo = u32x4{(unsigned)pyo, (unsigned)(pyo >> 32) & 0xffffu, pa.bytesDYo, 0x00020000u};      // (no dy_out: zero bytes, every store dropped)
+        }
     }
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
-    // DMA slot of this thread: row r of the 32-row tile, 16-byte slot q; it fetches the logical chunk the swizzle puts there
-    const int r = t >> 4, q = t & 15;
-    const unsigned qlog = (unsigned)((((q >> 1) ^ w3f<256>(r)) << 1) | (q & 1)) << 4;
     const unsigned wave_lds = lds0 + (unsigned)wave * 1024u;
+    // BN, dout: the thread's chunk lies in segment (chunk >> 3) when there are two
+    [[maybe_unused]] unsigned dstride = 0, dcol = 0;
+    if constexpr (BN != 0) {
+        const int dseg = pa.nseg == 2 ? (int)(qlog >> 7) : 0;
+        dstride = (unsigned)((dseg ? pa.lddo[1] : pa.lddo[0]) * 2);
+        dcol = (dseg ? pa.segoff[1] : pa.segoff[0]) + (pa.nseg == 2 ? (qlog & 127u) : qlog);
+    }
     auto dx_off = [&](int p0) -> unsigned {
         const int m = p0 + r;
         return (m >= pbeg && m < pend) ? (unsigned)m * (unsigned)(p.lddx * 2) + (unsigned)(q << 4) : 0xFFFFFFFFu;
     };
-    // a stage = 32 rows of dy and of x in the swizzled image, and (ACC) the previous contents of the same 32 rows of dx, unswizzled:
-    // thread (r, q) reads back exactly the 16 bytes its own DMA lane wrote
     auto issue = [&](int p0, int buf) {
         const int m = p0 + r;
         const bool ok = m < pend;
         lds_dma16(rsY, wave_lds + (unsigned)buf * STAGE, ok ? (unsigned)m * (unsigned)(p.ldy * 2) + qlog : 0xFFFFFFFFu);
         lds_dma16(rsX, wave_lds + (unsigned)buf * STAGE + YB, ok ? (unsigned)m * (unsigned)(p.ldx * 2) + qlog : 0xFFFFFFFFu);
-        if constexpr (ACC) lds_dma16(rsD, wave_lds + (unsigned)buf * STAGE + 2 * YB, dx_off(p0));
+        if constexpr (BN != 0) lds_dma16(rsO, wave_lds + (unsigned)buf * STAGE + 2 * YB, ok ? (unsigned)m * dstride + dcol : 0xFFFFFFFFu);
+        if constexpr (ACC) lds_dma16(rsD, wave_lds + (unsigned)buf * STAGE + OD * YB, dx_off(p0));
     };
-    // weights: 4 passes of 32 rows
+    // BN: y and dout of this thread's slot -> dy, over the y slot (rows past the range: zeros, as the DMA of a dy tile leaves them)
+    [[maybe_unused]] auto fetch_ydo = [&](int buf, uint4& yq, uint4& dq) {
+        yq = *(const uint4*)(smem + buf * STAGE + t * 16);
+        dq = *(const uint4*)(smem + buf * STAGE + 2 * YB + t * 16);
+    };
+    [[maybe_unused]] auto transform = [&](int p0, int buf, const uint4& yq, const uint4& dq) {
+        if constexpr (BN != 0) {
+            const int m = p0 + r;
+            uint4 v = bn_bwd_dy_bf16x8<ACT>(yq, dq, sc, sf, mu, is, kb, kg);
+            if (m >= pend) v = make_uint4(0u, 0u, 0u, 0u);
+            *(uint4*)(smem + buf * STAGE + t * 16) = v;
+            buf_store16_asm(u32x4{v.x, v.y, v.z, v.w}, (m < pend && pa.dYo) ? (unsigned)m * (unsigned)(pa.lddyo * 2) + qlog : 0xFFFFFFFFu, rsYo);
+        }
+    };
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = r + 32 * i;
         lds_dma16(rsW, lds0 + (unsigned)(S * STAGE) + (unsigned)i * 8192u + (unsigned)wave * 1024u,
                   (unsigned)row * 256u + (unsigned)((q ^ (row & 15)) << 4));
     }
-    // prologue: S - 1 stages, each followed by the (dropped) store a loop iteration issues behind its DMAs: the count stays uniform
+    // prologue: S - 1 stages, each followed by the (dropped) store(s) a loop iteration issues behind its DMAs: the count stays uniform
+    // (BN: the last stage's second store is transform(0)'s)
 #pragma unroll
     for (int u = 0; u < S - 1; ++u) {
         issue(pbeg + u * SP, u);
         buf_store16_asm(u32x4{0u, 0u, 0u, 0u}, 0xFFFFFFFFu, rsD);
+        if (BN != 0 && u < S - 2) buf_store16_asm(u32x4{0u, 0u, 0u, 0u}, 0xFFFFFFFFu, rsD);
+    }
+    if constexpr (BN != 0) {
+        wait_vm_barrier<NWAIT0>();
+        uint4 yq, dq;
+        fetch_ydo(0, yq, dq);
+        transform(pbeg, 0, yq, dq);
     }
 
     const int lrow = lane & 15, lgrp = lane >> 4;
-    // ---- weight-gradient fragments (wgrad3's map): waves 2 (co) x 4 (ci), 64 x 32 per wave
     const int wi = wave >> 2, wj = wave & 3;
     const int g4 = lane >> 4, lq = (lane & 15) >> 2, lp = lane & 3;
     f32x4 accw[4][2];
@@ -4275,8 +4356,9 @@ __global__ __launch_bounds__(512, 2) void pwbw_kernel(const PwbwArgs p) {
         uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
         return make_uint4(l2.x, l2.y, h2.x, h2.y);
     };
-    // ---- input-gradient fragments: wave w owns ci 16 w .. 16 w + 15 (MFMA A rows), all 32 pixels (two B tiles)
     const unsigned char* const wrow = sWt + (wave * 16 + lrow) * 256;
+    // weight-gradient fragments (wgrad3's map): waves 2 (co) x 4 (ci), 64 x 32 per wave; input gradient: wave w owns ci 16 w .. 16 w + 15
+    // (MFMA A rows), all 32 pixels (two B tiles)
     auto compute = [&](int buf, int sbuf) {
         const unsigned char* by = smem + buf * STAGE;
         const unsigned char* bx = by + YB;
@@ -4294,7 +4376,7 @@ __global__ __launch_bounds__(512, 2) void pwbw_kernel(const PwbwArgs p) {
         f32x4 accd[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const int ch = ks * 4 + lgrp;                                 // 16-byte chunk of the 128 output channels (K)
+            const int ch = ks * 4 + lgrp;
             const uint4 a = *(const uint4*)(wrow + ((ch ^ lrow) << 4));
 #pragma unroll
             for (int pt = 0; pt < 2; ++pt) {
@@ -4302,7 +4384,6 @@ __global__ __launch_bounds__(512, 2) void pwbw_kernel(const PwbwArgs p) {
                 Mma<bf16_t>::run(a, b, accd[pt]);
             }
         }
-        // lane: 4 consecutive input channels (16 w + 4 lgrp ..) of pixel pt * 16 + lrow
         unsigned char* const st = sSt + sbuf * (SP * 256);
 #pragma unroll
         for (int pt = 0; pt < 2; ++pt) {
@@ -4314,10 +4395,9 @@ __global__ __launch_bounds__(512, 2) void pwbw_kernel(const PwbwArgs p) {
             *(uint2*)(st + px * 256 + ((chq ^ (px & 15)) << 4) + ((lgrp & 1) << 3)) = u;
         }
     };
-    // the rows of a finished stage: this thread's 16 bytes of the staging tile (and of the old dx tile that travelled with the stage)
     auto fetch_rows = [&](int sbuf, int obuf, uint4& v, uint4& o) {
         v = *(const uint4*)(sSt + sbuf * (SP * 256) + r * 256 + ((q ^ (r & 15)) << 4));
-        if constexpr (ACC) o = *(const uint4*)(smem + obuf * STAGE + 2 * YB + t * 16);
+        if constexpr (ACC) o = *(const uint4*)(smem + obuf * STAGE + OD * YB + t * 16);
     };
     auto store_rows = [&](int p0, uint4 v, const uint4& o) {
         if constexpr (ACC) {
@@ -4331,18 +4411,22 @@ __global__ __launch_bounds__(512, 2) void pwbw_kernel(const PwbwArgs p) {
         buf_store16_asm(u32x4{v.x, v.y, v.z, v.w}, dx_off(p0), rsD);
     };
 
-    int buf = 0, nxt = S - 1, k = 0;
+    int buf = 0, buf1 = 1, nxt = S - 1, k = 0;
     for (int p0 = pbeg; p0 < pend; p0 += SP, ++k) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // own staging writes / fragment reads of the previous stage are done
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // own staging / dy-tile writes and fragment reads of the previous stage are done
         wait_vm_barrier<NWAIT>();
-        // the previous stage's rows come out of LDS BEFORE the DMAs below overwrite the buffer its old-dx tile sits in (nxt)
+        // out of LDS BEFORE the DMAs below overwrite the buffer (nxt) the previous stage's old-dx tile sits in
         uint4 v, o = make_uint4(0u, 0u, 0u, 0u);
+        [[maybe_unused]] uint4 yq, dq;
         fetch_rows((k + 1) & 1, nxt, v, o);
+        if constexpr (BN != 0) fetch_ydo(buf1, yq, dq);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w), "+v"(o.x), "+v"(o.y), "+v"(o.z), "+v"(o.w)::"memory");
         issue(p0 + (S - 1) * SP, nxt);
         store_rows(p0 - SP, v, o);                               // (stage -1: out-of-range offset, dropped)
+        if constexpr (BN != 0) transform(p0 + SP, buf1, yq, dq);
         compute(buf, k & 1);
-        buf = buf + 1 == S ? 0 : buf + 1;
+        buf = buf1;
+        buf1 = buf1 + 1 == S ? 0 : buf1 + 1;
         nxt = nxt + 1 == S ? 0 : nxt + 1;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -4352,7 +4436,6 @@ __global__ __launch_bounds__(512, 2) void pwbw_kernel(const PwbwArgs p) {
         fetch_rows((k - 1) & 1, nxt, v, o);                      // (nxt == the last stage's buffer: (k - 1) % S)
         store_rows(pbeg + (k - 1) * SP, v, o);
     }
-    // weight gradient: one atomic pass over the CTA's 128 x 128 tile
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -4414,6 +4497,106 @@ extern "C" int ydl_conv_bwd_pw(const ydl_conv_geom* g, int dtype, const void* x,
         YDL_SET_MAX_LDS((pwbw_kernel<S, false>), smem);
         pwbw_kernel<S, false><<<ctas, 512, smem, st>>>(a);
     }
+    YDL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// pwbw_kernel<S, ACC, BN != 0>: pwbw for a layer whose dy is the output of a BatchNorm backward that nobody else reads.  The apply launch
+// (bn_bwd_apply_sums_kernel: y and dout in, dy out) disappears: a stage brings the 32 rows of y and of dout instead of dy, and the
+// thread that issued a 16-byte slot of the y tile (one pixel, the eight channels of logical chunk qlog >> 4 — fixed for the whole
+// kernel) reads back its own y and dout slots, forms the eight dy values with the apply kernel's own arithmetic (common.h:
+// bn_bwd_dy_bf16x8) and writes them OVER its y slot: the y tile becomes the swizzled dy tile compute() expects, with no change to the
+// fragment reads.  HBM: y + dout + x + dx [+ old dx] instead of (y + dout + dy) + (dy + x + dx [+ old dx]).
+//   * The transform of stage k + 1 runs in iteration k, behind the ring's barrier and in front of compute(k): the barrier of iteration
+//     k + 1 publishes it, there is no second barrier per stage.  A thread reads only what its own DMA lanes wrote, after its own
+//     counted vmcnt (and the barrier that follows it).
+//   * Per-channel constants (scale, shift, mean, invstd, kb = sum dz / M, kg = sum dz xhat / M) are formed once per CTA — the replica
+//     rows summed in double as the apply kernel does — pass through LDS and stay in 48 registers; block 0 writes dgamma / dbeta.
+//   * dout comes as one 128-channel segment or as two 64-channel segments with strides of their own (a fused sibling pair activates
+//     its halves into two places): ONE buffer resource based at the lower pointer, the segment's distance in the per-thread offset.
+//   * dy_out (optional): the thread also stores its 16 bytes, for a second reader of dy.
+// Stage = y | x | dout [| old dx] tiles, three (S = 4) or four (S = 3) of 8 KB: 96 KB of ring + 48 KB weights and staging + 3 KB.
+// Vector-memory operations per thread and stage, always all of them (out-of-range offsets where there is nothing to do):
+//   group j = [ NT DMAs of stage j | dx store of some earlier stage | dy_out store of some earlier stage ],  LOPS = NT + 2.
+// The prologue issues groups 0 .. S-2 (dummy stores; the last group's dy_out store is the one of transform(0)); iteration k
+// completes group k + S - 1.  Waits (operations younger than the DMAs that must have landed):
+//   * before transform(0), the DMAs of group 0: its own two stores, S - 3 whole groups, and group S - 2 without its last store:
+//     2 + (S - 3) LOPS + (LOPS - 1) = (S - 2) LOPS + 1;
+//   * top of iteration k, the DMAs of group k + 1 (transformed in this iteration; group k's are older): groups up to k + S - 2 are
+//     complete, so its own two stores and S - 3 whole groups:  NWAIT = (S - 3) LOPS + 2.
+// ------------------------------------------------------------------------------------------------------
+extern "C" int ydl_conv_bwd_pw_bn_supported(const ydl_conv_geom* g, int dtype) { return pwbw_ok(g, dtype) ? 1 : 0; }
+
+extern "C" int ydl_conv_bwd_pw_bn(const ydl_conv_geom* g, int dtype, const void* x, const void* y, int ldy, const void* dout0, int lddo0,
+                                  const void* dout1, int lddo1, const float* mean, const float* invstd, const float* scale,
+                                  const float* shift, const float* sums0, const float* sums1, int64_t npix, int act, float* dgamma,
+                                  float* dbeta, int accumulate_param_grads, void* dy_out, int lddy, const void* wt, void* dx, int lddx,
+                                  int accumulate, float* dw, void* stream) {
+    YDL_CHECK(pwbw_ok(g, dtype), "ydl_conv_bwd_pw_bn: geometry not supported (query ydl_conv_bwd_pw_bn_supported)");
+    YDL_CHECK(x && y && dout0 && wt && dx && dw && mean && invstd && scale && shift && sums0, "null pointer");
+    YDL_CHECK((dout1 == nullptr) == (sums1 == nullptr), "the second dout segment and its sums come together");
+    YDL_CHECK(act == YDL_ACT_NONE || act == YDL_ACT_SILU, "activation must be NONE or SILU");
+    YDL_CHECK(aligned16(x) && aligned16(y) && aligned16(dout0) && aligned16(dout1) && aligned16(wt) && aligned16(dx) && aligned16(dy_out),
+              "pointers must be 16-byte aligned");
+    const int nseg = dout1 ? 2 : 1, segw = dout1 ? 64 : 128;
+    YDL_CHECK(lddx >= 128 && (lddx & 7) == 0 && ldy >= 128 && (ldy & 7) == 0, "dx / y pixel stride");
+    YDL_CHECK(lddo0 >= segw && (lddo0 & 7) == 0 && (dout1 == nullptr || (lddo1 >= 64 && (lddo1 & 7) == 0)), "dout pixel stride");
+    YDL_CHECK(dy_out == nullptr || (lddy >= 128 && (lddy & 7) == 0), "dy_out pixel stride");
+    const int M = g->N * g->Ho * g->Wo;
+    YDL_CHECK(npix == (int64_t)M, "npix must be the layer's pixel count");
+    const unsigned long long rows = (unsigned long long)(M - 1);
+    YDL_CHECK((unsigned long long)M * (unsigned long long)lddx * 2ull < 0xFFFFFFF0ull, "dx larger than 4 GiB");
+    YDL_CHECK((unsigned long long)M * (unsigned long long)ldy * 2ull < 0xFFFFFFF0ull, "y larger than 4 GiB");
+    YDL_CHECK(dy_out == nullptr || (unsigned long long)M * (unsigned long long)lddy * 2ull < 0xFFFFFFF0ull, "dy_out larger than 4 GiB");
+    PwbwBnArgs b{};
+    PwbwArgs& a = b.c;
+    a.X = (const bf16_t*)x; a.dY = (const bf16_t*)y; a.Wt = (const bf16_t*)wt; a.dX = (bf16_t*)dx; a.dW = dw;
+    a.M = M; a.ldx = g->ldx; a.ldy = ldy; a.lddx = lddx; a.ldw = g->ldw ? g->ldw : 128;
+    int ctas = ydl_device_cus();
+    int chunk = (M + ctas - 1) / ctas;
+    chunk = (chunk + PWBW_SP - 1) / PWBW_SP * PWBW_SP;
+    ctas = (M + chunk - 1) / chunk;
+    a.chunk = chunk;
+    a.bytesX = (unsigned)(rows * g->ldx * 2ull + 256ull);
+    a.bytesY = (unsigned)(rows * ldy * 2ull + 256ull);
+    a.bytesDX = (unsigned)(rows * lddx * 2ull + 256ull);
+    a.bytesWt = 128u * 256u;
+    // dout: one resource from the lower segment pointer; both segments must end within 4 GiB of it
+    const uintptr_t d0 = (uintptr_t)dout0, d1 = dout1 ? (uintptr_t)dout1 : d0, dlo = d0 < d1 ? d0 : d1;
+    const unsigned long long end0 = (unsigned long long)(d0 - dlo) + rows * lddo0 * 2ull + (unsigned long long)segw * 2ull;
+    const unsigned long long end1 = dout1 ? (unsigned long long)(d1 - dlo) + rows * lddo1 * 2ull + 128ull : 0ull;
+    YDL_CHECK(end0 < 0xFFFFFFF0ull && end1 < 0xFFFFFFF0ull, "dout segments must lie within 4 GiB of each other");
+    b.dO = (const bf16_t*)dlo; b.dYo = (bf16_t*)dy_out;
+    b.segoff[0] = (unsigned)(d0 - dlo); b.segoff[1] = (unsigned)(d1 - dlo);
+    b.lddo[0] = lddo0; b.lddo[1] = dout1 ? lddo1 : lddo0;
+    b.bytesDO = (unsigned)(end0 > end1 ? end0 : end1);
+    b.bytesDYo = dy_out ? (unsigned)(rows * lddy * 2ull + 256ull) : 0u;
+    b.lddyo = dy_out ? lddy : 0; b.nseg = nseg; b.acc_param = accumulate_param_grads;
+    b.mean = mean; b.invstd = invstd; b.scale = scale; b.shift = shift; b.sums0 = sums0; b.sums1 = sums1;
+    b.dgamma = dgamma; b.dbeta = dbeta;
+    b.invM = 1.0f / (float)npix;
+    hipStream_t st = (hipStream_t)stream;
+    const bool silu = act == YDL_ACT_SILU;
+    // the kernel is pwbw_kernel, as for ydl_conv_bwd_pw (families 1 and 2); family 6 tells how this instantiation gets its dy
+    ydl_note_kernel(1, accumulate ? "pwbw_kernel<128,128,acc>" : "pwbw_kernel<128,128>");
+    ydl_note_kernel(2, "pwbw_kernel<128,128>");
+    ydl_note_kernel(6, accumulate ? (silu ? "pwbw_kernel<128,128,bn-silu,acc>" : "pwbw_kernel<128,128,bn-none,acc>")
+                                  : (silu ? "pwbw_kernel<128,128,bn-silu>" : "pwbw_kernel<128,128,bn-none>"));
+#define YDL_PWBWBN_LAUNCH(S_, ACC_, ACT_)                                                                       \
+    do {                                                                                                        \
+        const size_t smem = (size_t)(S_) * ((ACC_) ? 4 : 3) * PWBW_SP * 256 + 128 * 256 + 2 * PWBW_SP * 256 + 6 * 128 * 4; \
+        YDL_SET_MAX_LDS((pwbw_kernel<S_, ACC_, 1 + (ACT_), PwbwBnArgs>), smem);                                 \
+        pwbw_kernel<S_, ACC_, 1 + (ACT_), PwbwBnArgs><<<ctas, 512, smem, st>>>(b);                              \
+    } while (0)
+    if (accumulate) {          // four tiles per stage: three stages
+        if (silu) YDL_PWBWBN_LAUNCH(3, true, YDL_ACT_SILU);
+        else YDL_PWBWBN_LAUNCH(3, true, YDL_ACT_NONE);
+    } else {
+        if (silu) YDL_PWBWBN_LAUNCH(4, false, YDL_ACT_SILU);
+        else YDL_PWBWBN_LAUNCH(4, false, YDL_ACT_NONE);
+    }
+#undef YDL_PWBWBN_LAUNCH
     YDL_LAUNCH_CHECK();
     return 0;
 }

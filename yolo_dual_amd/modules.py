@@ -165,12 +165,19 @@ class YdlModule(nn.Module):
 def _launch_wgrad(tape: Tape, gp, x_ptr, dy_ptr, dw_ptr, st, fuse=None) -> bool:
     """dW += dy^T * im2col(x): f32 atomics (throughput mode) or the deterministic slab form (parity mode / config).
     ``fuse`` = (wt_ptr, dx_ptr, lddx, accumulate) of the SAME layer's input gradient: where the one-pass kernel applies (the
-    HBM-bound 128 -> 128 1x1 layers, ydl_conv_bwd_pw) both gradients come from one launch and the call returns True."""
+    HBM-bound 128 -> 128 1x1 layers, ydl_conv_bwd_pw) both gradients come from one launch and the call returns True.  A fifth
+    element holds ydl_conv_bwd_pw_bn's arguments between ``x`` and ``wt``: dy does not exist then (``dy_ptr`` is None), the kernel
+    forms it from the BatchNorm backward's operands, and there is no other way to run the layer."""
     if (fuse is not None and not config.deterministic(tape.dname) and config.fuse_pw_backward()
             and L.lib().ydl_conv_bwd_pw_supported(gp, tape.dt)):
-        wt_ptr, dx_ptr, lddx, acc = fuse
-        L.call("ydl_conv_bwd_pw", gp, tape.dt, x_ptr, dy_ptr, wt_ptr, dx_ptr, lddx, acc, dw_ptr, st)
+        wt_ptr, dx_ptr, lddx, acc = fuse[:4]
+        if len(fuse) > 4:
+            L.call("ydl_conv_bwd_pw_bn", gp, tape.dt, x_ptr, *fuse[4], wt_ptr, dx_ptr, lddx, acc, dw_ptr, st)
+        else:
+            L.call("ydl_conv_bwd_pw", gp, tape.dt, x_ptr, dy_ptr, wt_ptr, dx_ptr, lddx, acc, dw_ptr, st)
         return True
+    if dy_ptr is None:
+        raise RuntimeError("ydl_conv_bwd_pw_bn was planned for a layer the one-pass kernel does not take")
     if config.deterministic(tape.dname):
         nbytes = L.lib().ydl_conv_wgrad_ws_bytes(gp, tape.dt)
         ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=tape.device)
@@ -283,7 +290,7 @@ class _GemmWeights:
         cin_p = round_up(cin, 8)
         done = False
         if cin_p == cin and gk.is_contiguous():
-            done = _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), ctypes.c_void_p(gk.data_ptr() + 4 * col0), st, fuse)
+            done = _launch_wgrad(tape, gp, _p(x.t), _p(dy.t) if dy is not None else None, ctypes.c_void_p(gk.data_ptr() + 4 * col0), st, fuse)
         else:
             assert col0 == 0 and final
             tmp = zero_(torch.empty((rows, taps, cin_p), dtype=torch.float32, device=gk.device), st)
@@ -295,6 +302,13 @@ class _GemmWeights:
         if final and self.final:
             config.mark_touched(p)
         return done
+
+    def pw_bn_ready(self) -> bool:
+        """``wgrad`` would hand ``fuse`` to the kernel as it is (no padded staging buffer, no re-homed gradient): the condition
+        under which the tape may leave dy to ydl_conv_bwd_pw_bn"""
+        p = self._wparam
+        rows, taps, cin = self._gemm_dims()
+        return bool(p.requires_grad and cin % 8 == 0 and self._krsc(self._grad_of(p)).is_contiguous())
 
     # -- the BatchNorm behind the GEMM ---------------------------------------------------------------------
     def mark_step(self, tape: Tape) -> None:
@@ -640,10 +654,13 @@ class _FusedPair(_GemmWeights):
     def splittable(self) -> bool:
         return self.c1 % 8 == 0
 
+    def pw_bn_ready(self) -> bool:
+        return bool(self.trainable()[0])
+
     def wgrad(self, tape: Tape, gp, x: Var, dy: Var, st, col0: int = 0, final: bool = True, fuse=None) -> bool:
         p1, p2 = self._grads("w")
         gk = p1.grad.permute(0, 2, 3, 1)
-        done = _launch_wgrad(tape, gp, _p(x.t), _p(dy.t), ctypes.c_void_p(gk.data_ptr() + 4 * col0), st, fuse)
+        done = _launch_wgrad(tape, gp, _p(x.t), _p(dy.t) if dy is not None else None, ctypes.c_void_p(gk.data_ptr() + 4 * col0), st, fuse)
         if final:
             config.mark_touched(p1)
             config.mark_touched(p2)
@@ -922,6 +939,9 @@ class _DeformGemm(_GemmWeights):
                 self.bn.bias.requires_grad)
 
     def splittable(self) -> bool:
+        return False
+
+    def pw_bn_ready(self) -> bool:
         return False
 
     def wgrad(self, tape: Tape, gp, x: Var, dy: Var, st, col0: int = 0, final: bool = True, fuse=None) -> bool:

@@ -723,6 +723,34 @@ class Tape:
                 return                                   # frozen layer on a frozen prefix: nothing upstream wants a gradient
                                                          # (a residual operand that does is served by the BN-backward pass below)
             st2 = _stream()
+            from . import config as _cfg
+            if (sums_mode and subs is None and self.dt == L.YDL_BF16 and rep == 1 and act in (L.ACT_NONE, L.ACT_SILU)
+                    and train_w and x.need and _cfg.fuse_bn_pw_backward() and _cfg.fuse_pw_backward() and not _cfg.bn_bwd_fuse()
+                    and not _cfg.deterministic(self.dname) and all(o.is_set() for (_c, _w, o) in parts)
+                    and (single or (len(parts) == 2 and all(cw == 64 for (_c, cw, _o) in parts)))
+                    and L.lib().ydl_conv_bwd_pw_bn_supported(gp, self.dt) and getattr(m, "pw_bn_ready", lambda: False)()):
+                # dy has ONE reader, the one-pass 1x1 backward: only the reduce pass is launched (it also serves the residual
+                # operand), ydl_conv_bwd_pw_bn forms dy from y and dout itself and writes dgamma / dbeta; no dy buffer
+                gw, gb, accw = self._bn_grad_rows(m, Cout_p)
+                seg = []
+                for (co, cw, o) in parts:
+                    o.bnred = None
+                    dout = self._gbuf(o)
+                    dres_t, dres_ld, rmode = self._res_grad(res, res_mode, o, dout)
+                    sums_b = self.zeroed(L.BN_REPLICAS * 2 * cw)
+                    L.call("ydl_bn_act_bwd_reduce_sums", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(dout), o.ld,
+                           _p(o.t), o.ld, _p(cf["mean"][co:]), _p(cf["invstd"][co:]), _p(cf["scale"][co:]), _p(cf["shift"][co:]),
+                           rmode, act, _p(dres_t), dres_ld, _p(sums_b), npix, cw, cw, st2)
+                    seg.append((dout, o.ld, sums_b))
+                if single:
+                    seg.append((None, 0, None))
+                gx, acc = self.grad_target(x)
+                bn = (_p(y.t), y.ld, _p(seg[0][0]), seg[0][1], _p(seg[1][0]), seg[1][1], _p(cf["mean"]), _p(cf["invstd"]),
+                      _p(cf["scale"]), _p(cf["shift"]), _p(seg[0][2]), _p(seg[1][2]), npix, act, _p(gw), _p(gb), accw, None, 0)
+                m.wgrad(self, gp, x, None, st2, fuse=(_p(wt), _p(gx), x.ld, acc, bn))
+                m.touch_bn()          # after the launch that writes dgamma / dbeta
+                self._keep.append((geom, seg))
+                return
             dy = self.new(x.N, Cout, Ho, Wo)
             gw, gb, accw = self._bn_grad_rows(m, Cout_p)
             for (co, cw, o) in parts:
