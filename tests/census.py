@@ -609,7 +609,7 @@ def check_conv_bwd_pw(L, case, gen):
     kernel = L.last_kernel(1) + "|" + L.last_kernel(2)
     gd = g._replace(ldx=case["lddx"])
     own, ref, Q, A = conv_dgrad_ref(gd, dy.flat, wtr, prior)
-    # pwbw_kernel<.., ACC> (csrc/igemm.hip): compute() packs the launch's own input gradient to bf16 (f2bf) into the LDS staging tile,
+    # pwbw_kernel<.., ACC> (csrc/wgrad.hip): compute() packs the launch's own input gradient to bf16 (f2bf) into the LDS staging tile,
     # store_rows() unpacks it, adds the previous dx and packs again — the same second rounding as pw_kernel's transposed accumulate
     # store, 2^-8 |own contribution|
     extra = U8 * own.abs() if case["acc"] else None

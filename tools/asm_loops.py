@@ -4,7 +4,8 @@ loop that contains MFMAs, the instruction mix and every wait the compiler (or th
 a dynamic index into a byte array of the kernel arguments becomes `global_load_sbyte` + `s_waitcnt vmcnt(0)` (which drains the LDS-DMA
 ring in front of it), a control-flow join in front of an MFMA batch becomes `lgkmcnt(0..1)` (which waits for the fragment reads that
 were meant to stay in flight).
-usage: python tools/asm_loops.py [file.hip] [--kernel SUBSTR] [--dump]   (--dump prints the loop bodies)"""
+usage: python tools/asm_loops.py [file.hip] [--kernel SUBSTR] [--dump]   (--dump prints the loop bodies; file: igemm.hip (the default) for the
+forward and data-gradient kernels, wgrad.hip for the weight-gradient kernels)"""
 import argparse
 import os
 import re

@@ -69,7 +69,7 @@ __device__ __forceinline__ float sigmoid_f(float z) {
 __device__ __forceinline__ float silu_f(float z) { return z * sigmoid_f(z); }
 
 // BatchNorm backward of ONE element, the only definition of its arithmetic (the streaming kernels of bn.hip and the convolution
-// backward kernels that form dy on the way in, igemm.hip: pwbw_kernel<S, ACC, BN>, must agree to the bit):
+// backward kernels that form dy on the way in, wgrad.hip: pwbw_kernel<S, ACC, BN>, must agree to the bit):
 //   dz = dout * act'(y*scale + shift),  xhat = (y - mean) * invstd      (ov: the stored output, read for the ReLU mask only)
 //   dy = scale * (dz - kb - xhat * kg)  with kb = sum(dz) / M, kg = sum(dz * xhat) / M
 template <int ACT>
