@@ -159,6 +159,34 @@ int ydl_weight_prep_batched(int dtype, const int64_t* desc_dev, int nlayers, voi
 /* dw [Cout][kk][Cin_p] f32 -> master-layout grad [Cout][kk][Cin] (only needed when Cin_p != Cin) */
 int ydl_wgrad_unpad(const float* dw, float* grad, int Cout, int kk, int Cin, int accumulate, void* stream);
 
+/* ---- grouped convolution, 1 < groups < channels (csrc/gconv.hip) -----------------------------------
+ * nn.Conv2d(Cin, Cout, k, 1, k/2, groups=groups, bias=False) on the same ydl_conv_geom (Cin, Cout: the WHOLE tensors' channels):
+ * output channel c reads the input channels of group c / (Cout/groups) only.  ONE launch serves every group.
+ * Served set (ydl_gconv_supported != 0; everything else returns an error): groups >= 2, Cin/groups and Cout/groups multiples
+ * of 16, k in {1, 3}, s = 1, p = k/2, ldw = 0, pixel strides as for ydl_conv_fwd.  x, y, dy, dx may be channel slices of wider
+ * buffers (ldx / ldy larger than the channel count); channels outside the slice are never written.  f32 accumulation, no atomics:
+ * the same kernels serve throughput mode and deterministic mode, and every result is bitwise reproducible.
+ * Weights: w  = [Cout][k*k][Cin/groups]  (the KRSC master shape: nn.Conv2d(groups).weight in channels_last storage)
+ *          wt = [Cin][k*k][Cout/groups]  (per-group transpose, for the input gradient). */
+int ydl_gconv_supported(const ydl_conv_geom* g, int groups, int dtype);
+/* master (f32, w's shape) -> compute-dtype copies w and wt, one launch */
+int ydl_gconv_weight_prep(int dtype, const float* master, void* w, void* wt, int Cout, int kk, int Cin, int groups, void* stream);
+/* y = gconv(x, w).  stats_ws != NULL: also writes per-block (sum, M2) rows of the STORED output, [rows][2][round_up(Cout,8)] floats
+ * with rows = ceil(N*Ho*Wo / block_m), row b covering pixels [b*block_m, (b+1)*block_m), in the format ydl_bn_finalize consumes.
+ * ydl_gconv_fwd_block_m / _stats_ws_bytes are pure host functions of the geometry (0 for a geometry outside the served set); the
+ * workspace size includes the room ydl_bn_finalize needs behind the rows. */
+int ydl_gconv_fwd_block_m(const ydl_conv_geom* g, int groups, int dtype);
+int64_t ydl_gconv_fwd_stats_ws_bytes(const ydl_conv_geom* g, int groups, int dtype);
+int ydl_gconv_fwd(const ydl_conv_geom* g, int groups, int dtype, const void* x, const void* w, void* y, float* stats_ws, void* stream);
+/* dx (+)= gconv_transpose(dy, wt).  accumulate != 0 adds into dx. */
+int ydl_gconv_dgrad(const ydl_conv_geom* g, int groups, int dtype, const void* dy, const void* wt, void* dx, int accumulate,
+                    void* stream);
+/* dw [Cout][k*k][Cin/groups] (f32, the master gradient's layout) += sum over pixels dy^T * im2col(x).  Every block stores its
+ * partial tile into ws (ydl_gconv_wgrad_ws_bytes, a pure host function) and a second kernel adds the partials into dw in a
+ * fixed order: bitwise reproducible.  dw holds zeros or the running sum of gradient accumulation. */
+int64_t ydl_gconv_wgrad_ws_bytes(const ydl_conv_geom* g, int groups, int dtype);
+int ydl_gconv_wgrad(const ydl_conv_geom* g, int groups, int dtype, const void* x, const void* dy, float* dw, float* ws, void* stream);
+
 /* ---- train-mode BatchNorm + activation ------------------------------------------------------------- */
 /* Chan-merge the per-block partials; writes mean/invstd (saved for backward), scale=gamma*invstd,
  * shift=beta-mean*scale; updates running_mean/var (momentum, unbiased var) and is a no-op on them if NULL. */

@@ -63,6 +63,14 @@ SIGNATURES = {
     "ydl_weight_prep": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ydl_weight_prep_batched": (_i, [_i, _vp, _i, _vp]),
     "ydl_wgrad_unpad": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "ydl_gconv_supported": (_i, [_G, _i, _i]),
+    "ydl_gconv_weight_prep": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ydl_gconv_fwd_block_m": (_i, [_G, _i, _i]),
+    "ydl_gconv_fwd_stats_ws_bytes": (_i64, [_G, _i, _i]),
+    "ydl_gconv_fwd": (_i, [_G, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ydl_gconv_dgrad": (_i, [_G, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "ydl_gconv_wgrad_ws_bytes": (_i64, [_G, _i, _i]),
+    "ydl_gconv_wgrad": (_i, [_G, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ydl_bn_finalize": (_i, [_vp, _i, _i, _i64, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "ydl_bn_eval_coeffs": (_i, [_i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "ydl_bn_act_fwd": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i64, _i, _vp]),

@@ -229,7 +229,7 @@ class _YamlSegModel(YdlModule):
     def fuse(self):
         """models/yolo.py:140-148: fold every Conv's BatchNorm into its convolution (inference only)"""
         for m in self.modules():
-            if isinstance(m, Conv) and not m.depthwise:
+            if isinstance(m, Conv) and not m.depthwise and not m.grouped:
                 m.fuse()
         return self
 

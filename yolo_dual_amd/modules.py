@@ -93,7 +93,7 @@ def refresh_weights(fn: nn.Module, tape: Tape) -> None:
     """one batched launch re-deriving the compute-layout weights of every stale Conv under ``fn``"""
     convs = getattr(fn, "_ydl_convs", None)
     if convs is None:
-        convs = [m for m in fn.modules() if isinstance(m, Conv) and not m.depthwise and m.d == 1 and m.bn is not None]     # (a dilated Conv's GEMM view is _DeformGemm)
+        convs = [m for m in fn.modules() if isinstance(m, Conv) and not m.depthwise and not m.grouped and m.d == 1 and m.bn is not None]     # (a dilated Conv's GEMM view is _DeformGemm; a grouped Conv prepares its own block-diagonal copies)
         fn._ydl_convs = convs
         fn._ydl_csp = [m for m in fn.modules() if isinstance(getattr(m, "cv1", None), Conv) and isinstance(getattr(m, "cv2", None), Conv)]
     # sibling pairs that ran fused last time are prepared as ONE matrix (their masters are adjacent), their members not at all
@@ -386,8 +386,13 @@ class Conv(_GemmWeights, YdlModule):
         if g <= 0 or c1 % g != 0:
             raise ValueError(f"groups g={g} must be positive and divide c1={c1}")
         self.depthwise = g > 1 and g == c1 == c2
-        if g != 1 and not self.depthwise:
-            raise NotImplementedError("the HIP path implements groups=1 (implicit GEMM) and groups=c1=c2 (depth-wise, dilation=1)")
+        self.grouped = g > 1 and not self.depthwise
+        if self.grouped and not (c2 % g == 0 and (c1 // g) % 16 == 0 and (c2 // g) % 16 == 0 and k in (1, 3) and s == 1
+                                 and autopad(k, p) == k // 2 and d == 1):
+            raise NotImplementedError(f"the HIP path implements groups=1 (implicit GEMM), groups=c1=c2 (depth-wise, dilation=1) and grouped "
+                                      f"convolution with c1/groups and c2/groups multiples of 16, k in {{1,3}}, s=1, p=k//2, d=1; got "
+                                      f"c1={c1}, c2={c2}, k={k}, s={s}, p={p}, groups g={g}, d={d}")
+        self.groups = g
         if d != 1 and not (g == 1 and d > 1 and s == 1 and k == 3 and p in (None, d)):
             raise NotImplementedError(f"dilated Conv: the HIP path serves g=1, s=1, k=3, d>1 with p=None or p=d (column-form dilated "
                                       f"convolution); got g={g}, s={s}, k={k}, d={d}, p={p}")
@@ -411,7 +416,24 @@ class Conv(_GemmWeights, YdlModule):
         return self.conv.weight
 
     def _gemm_dims(self):
-        return self.c2, self.k * self.k, self.c1
+        return self.c2, self.k * self.k, self.c1 // self.groups if self.grouped else self.c1
+
+    def gconv_weights(self, tape: Tape):
+        """grouped Conv: compute-dtype copies w [c2][k*k][c1/g] (the master's own shape) and wt [c1][k*k][c2/g] (per-group transpose,
+        for the input gradient) from one ydl_gconv_weight_prep launch; cached and invalidated like ``compute_weights``"""
+        key = self._wkey(tape)
+        c = self._wcache
+        if c.get("key") == key:
+            return c["w"], c["wt"]
+        master = self._master_krsc()
+        kk, g = self.k * self.k, self.groups
+        w = c.get("w")
+        if w is None or c.get("dname") != tape.dname or w.device != master.device:
+            c.update(w=torch.empty((self.c2, kk, self.c1 // g), dtype=tape.tdt, device=master.device),
+                     wt=torch.empty((self.c1, kk, self.c2 // g), dtype=tape.tdt, device=master.device), dname=tape.dname, key=None)
+        L.call("ydl_gconv_weight_prep", tape.dt, _p(master), _p(c["w"]), _p(c["wt"]), self.c2, kk, self.c1, g, _stream())
+        c["key"] = key
+        return c["w"], c["wt"]
 
     def trainable(self):
         """(weight, BN weight, BN bias) ``requires_grad`` flags: a frozen parameter (``--freeze``, seg_diceloss_yolov5.py:955-959)
@@ -447,6 +469,8 @@ class Conv(_GemmWeights, YdlModule):
         self.mark_step(tape)
         if self.depthwise:
             return tape.dw_bn_act(x, self, self.s, act, out=out, res=res, res_mode=res_mode)
+        if self.grouped:
+            return tape.gconv_bn_act(x, self, act, out=out, res=res, res_mode=res_mode)
         if getattr(self, "_fused", None) is not None and not tape.train:
             y = tape.conv_bias_act(x, self, act, res=res, res_mode=res_mode)
             return y if out is None else tape.copy(y, out)
@@ -463,6 +487,8 @@ class Conv(_GemmWeights, YdlModule):
         """fold the BatchNorm running statistics into the convolution: eval-mode forward becomes act(conv(x, w') + b')"""
         if self.depthwise:
             raise NotImplementedError("fuse() of a depth-wise Conv")
+        if self.grouped:
+            raise NotImplementedError("fuse() of a grouped Conv (the folded eval path runs groups=1 convolutions only)")
         if self.d > 1:
             raise NotImplementedError("fuse() of a dilated Conv (the folded eval path runs undilated convolutions only)")
         from .checkpoint import fuse_conv_and_bn
@@ -1208,16 +1234,19 @@ class _CSPPool(YdlModule):
     ``_pools`` fills its other three slices, y1 = cv6(cv5(buffer)) and y2 = cv2(x) are written into the halves of cv7's input.
     ``n``, ``shortcut`` and ``g`` are accepted and unused, as in the reference (which never hands ``g`` to a convolution)."""
 
+    conv_groups = 1        # SPPCSPC_group: 4
+
     def __init__(self, c1, c2, e):
         super().__init__()
         c_ = int(2 * c2 * e)
-        self.cv1 = Conv(c1, c_, 1, 1)
-        self.cv2 = Conv(c1, c_, 1, 1)
-        self.cv3 = Conv(c_, c_, 3, 1)
-        self.cv4 = Conv(c_, c_, 1, 1)
-        self.cv5 = Conv(4 * c_, c_, 1, 1)
-        self.cv6 = Conv(c_, c_, 3, 1)
-        self.cv7 = Conv(2 * c_, c2, 1, 1)
+        g = self.conv_groups
+        self.cv1 = Conv(c1, c_, 1, 1, g=g)
+        self.cv2 = Conv(c1, c_, 1, 1, g=g)
+        self.cv3 = Conv(c_, c_, 3, 1, g=g)
+        self.cv4 = Conv(c_, c_, 1, 1, g=g)
+        self.cv5 = Conv(4 * c_, c_, 1, 1, g=g)
+        self.cv6 = Conv(c_, c_, 3, 1, g=g)
+        self.cv7 = Conv(2 * c_, c2, 1, 1, g=g)
         self.c_ = c_
 
     def _fwd(self, tape: Tape, x: Var) -> Var:
@@ -1256,14 +1285,10 @@ class SimCSPSPPF(_CSPPool):
         tape.sppf_pools(x1, self.k, outs)
 
 
-class SPPCSPC_group(YdlModule):
-    """models/common.py:1451-1468: SPPCSPC whose seven convolutions are all Conv(g=4).  Refused: grouped convolution with
-    1 < groups < channels is not implemented on the HIP path."""
-
-    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5, k=(5, 9, 13)):
-        super().__init__()
-        raise NotImplementedError("SPPCSPC_group: every convolution in it is Conv(g=4), and the HIP path implements groups=1 and "
-                                  "depth-wise groups only")
+class SPPCSPC_group(SPPCSPC):
+    """models/common.py:1451-1468: SPPCSPC whose seven convolutions are all Conv(g=4) (Tape.gconv_bn_act); every one of them must lie
+    in the grouped Conv's served set, i.e. c1 / 4 and c_ / 4 and c2 / 4 are multiples of 16."""
+    conv_groups = 4
 
 
 # ----------------------------------------------------------------------------------------------------------

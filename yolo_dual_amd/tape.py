@@ -1289,6 +1289,83 @@ class Tape:
         self.bw.append(bw)
         return out
 
+    def gconv_bn_act(self, x: Var, m, act: int, out: Optional[Var] = None, res: Optional[Var] = None,
+                     res_mode: int = L.RES_NONE) -> Var:
+        """grouped Conv+BN+act, 1 < groups < channels: out = act(bn(gconv(x))) [+ res] — models/common.py:1451-1468 (SPPCSPC_group) and
+        every Conv / Bottleneck / C3 / C2f with g > 1.  One ydl_gconv_fwd launch serves all groups and writes the BatchNorm partial rows
+        of its output, so train mode goes conv -> ydl_bn_finalize -> ydl_bn_act_fwd.  The kernels use no atomics: the same launches
+        serve throughput mode and deterministic mode.  ``out`` may be a concat slice."""
+        x = self._flat(x)
+        if res is not None:
+            res = self._flat(res)
+        if out is not None and not out.aligned():       # the BatchNorm kernels work on 8-channel groups: stage an odd slice
+            return self.copy(self.gconv_bn_act(x, m, act, None, res, res_mode), out)
+        Cin, Cout, k, G = m.c1, m.c2, m.k, m.groups
+        if x.C != Cin:
+            raise RuntimeError(f"grouped Conv input channel mismatch: got {x.C}, weight expects {Cin}")
+        N, H, W = x.N, x.H, x.W
+        y = self.new(N, Cout, H, W)
+        if out is None:
+            out = self.new(N, Cout, H, W)
+        elif (out.N, out.C, out.H, out.W) != (N, Cout, H, W):
+            raise RuntimeError("gconv_bn_act: output slice has the wrong shape")
+        st = _stream()
+        w, wt = m.gconv_weights(self)
+        cf = m.coeffs(self.device)
+        npix = N * H * W
+        cp = round_up(Cout, 8)
+        geom = L.ConvGeom(N, H, W, Cin, H, W, Cout, k, 1, k // 2, x.ld, y.ld, 0)
+        gp = ctypes.byref(geom)
+        if not L.lib().ydl_gconv_supported(gp, G, self.dt):
+            raise RuntimeError("gconv_bn_act: " + (L.lib().ydl_last_error() or b"?").decode())
+        if self.train:
+            ws = torch.empty(L.lib().ydl_gconv_fwd_stats_ws_bytes(gp, G, self.dt) // 4, dtype=torch.float32, device=self.device)
+            bm = L.lib().ydl_gconv_fwd_block_m(gp, G, self.dt)
+            L.call("ydl_gconv_fwd", gp, G, self.dt, _p(x.t), _p(w), _p(y.t), _p(ws), st)
+            self._bn_coeffs(m, cf, Cout, st, (ws, (npix + bm - 1) // bm, bm, npix, 1))
+        else:
+            L.call("ydl_gconv_fwd", gp, G, self.dt, _p(x.t), _p(w), _p(y.t), None, st)
+            self._bn_coeffs(m, cf, Cout, st)
+        L.call("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
+               res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
+        if not self.record:
+            return out
+        if not self.train:
+            raise RuntimeError("backward through eval-mode BatchNorm is not supported")
+        if x.need:
+            self._use(x)
+        if res is not None and res.need and res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
+            self._use(res)
+        self._keep.append(geom)
+
+        def bw():
+            if not out.is_set():
+                return
+            st2 = _stream()
+            dy = self.new(N, Cout, H, W)
+            dout = self._gbuf(out)
+            gw, gb, accw = self._bn_grad_rows(m, cp)
+            dres_t, dres_ld, rmode = self._res_grad(res, res_mode, out, dout)
+            ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
+            L.call("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
+                   _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rmode, act,
+                   _p(dy.t), dy.ld, _p(dres_t), dres_ld, _p(gw), _p(gb), accw, _p(ws2), npix, Cout, cp, st2)
+            m.touch_bn()
+            gb_ = L.ConvGeom(N, H, W, Cin, H, W, Cout, k, 1, k // 2, x.ld, dy.ld, 0)
+            gpb = ctypes.byref(gb_)
+            self._keep.append(gb_)
+            if m.trainable()[0]:
+                gk = m.grad_dw()                                 # KRSC [Cout][k*k][Cin/groups]: the kernel's dw layout
+                ws3 = torch.empty(max(L.lib().ydl_gconv_wgrad_ws_bytes(gpb, G, self.dt) // 4, 4), dtype=torch.float32, device=self.device)
+                L.call("ydl_gconv_wgrad", gpb, G, self.dt, _p(x.t), _p(dy.t), _p(gk), _p(ws3), st2)
+                from . import config as _cfg
+                _cfg.mark_touched(m.conv.weight)
+            if x.need:
+                gx, acc = self.grad_target(x)
+                L.call("ydl_gconv_dgrad", gpb, G, self.dt, _p(dy.t), _p(wt), _p(gx), acc, st2)
+        self.bw.append(bw)
+        return out
+
     def group_softmax(self, x: Var, G: int, P: int) -> Var:
         """softmax over the P sampling points of each group (modules/dcnv3.py:122-123)"""
         x = self._flat(x)
