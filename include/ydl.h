@@ -247,6 +247,9 @@ int ydl_bn_act_bwd_reduce_sums(int dtype, const void* y, int ldy, const void* do
                                int res_mode, int act, void* dres, int lddr, float* sums, int64_t npix, int C, int Cp, void* stream);
 
 /* ---- spatial ops (NHWC, channel-vectorised) -------------------------------------------------------- */
+/* The pixel tensors of this section (x, y, dy, dx, a, b; not the per-image rows avg / max / davg / dmax and not gate) are read and
+ * written as 16-byte channel vectors: their pointers must be 16-byte aligned and their pixel strides whole chunks (4 f32 / 8 bf16
+ * elements), or the call is refused without a launch.  ydl_copy2d alone serves any alignment (an element-granular kernel). */
 /* max pool (k,s,p), -inf padding; idx (uint8 window offset of the arg-max, first max in scan order) is
  * written when non-NULL and consumed by the backward. */
 int ydl_maxpool_fwd(int dtype, const void* x, int ldx, void* y, int ldy, uint8_t* idx,
@@ -304,7 +307,8 @@ int ydl_scale_channels(int dtype, const void* x, int ldx, const float* gate /*[N
                        int N, int64_t hw, int C, void* stream);
 
 /* GAM (unet-lite/yolo9-seg/seg_diceloss_yolov9.py:475-510): global average / max pooling to 1x1 (argmax = pixel index of the
- * first maximum, int32 [N][round_up(C,8)]), sigmoid gate of two pooled branches, per-(n,c) dot product */
+ * first maximum -- a NaN wins and the last NaN stays, as in ATen's scan --, int32 [N][C rounded up to a 16-byte chunk of the
+ * dtype]; avg and max are written for that many channels), sigmoid gate of two pooled branches, per-(n,c) dot product */
 int ydl_global_pool_fwd(int dtype, const void* x, int ldx, void* avg, int lda, void* mx, int ldm, int32_t* argmax,
                         int N, int64_t HW, int C, void* stream);
 int ydl_global_pool_bwd(int dtype, const void* davg, int lda, const void* dmx, int ldm, const int32_t* argmax,

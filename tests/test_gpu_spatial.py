@@ -1,4 +1,5 @@
-"""Spatial kernels driven through the C ABI (bilinear resize backward: the integer-factor form against the generic gather form)."""
+"""Spatial kernels driven through the C ABI (bilinear resize backward: the integer-factor form against the generic gather form).
+The same kernels per element against float64: tests/test_gpu_spatial_f64.py and tests/test_gpu_spatial_exact.py."""
 import ctypes
 
 import pytest
@@ -70,6 +71,14 @@ def test_resize_accumulate_with_statistics(dtype, mode, N, Hi, Wi, Ho, Wo, C):
     got = sums.double().sum(0)[:, :C]
     ref = torch.stack([want32.double().sum((0, 1, 2)), (want32.double() ** 2).sum((0, 1, 2))])
     assert float((got - ref).abs().max() / ref.abs().max()) < 2e-5
+    # and against float64 directly (tests/spatial_ref.py shares no code with the kernels): values per element, statistics per channel
+    from tests import spatial_ref as R
+    vals, stats = R.case_acc_sums(dtype, mode, N, Hi, Wi, Ho, Wo, C, x.float().cpu().numpy(), y0.float().cpu().numpy())
+    for what, case, out in [("values", vals, y.float().cpu().numpy()), ("statistics", stats, got.cpu().numpy())]:
+        lay = R.Layout(case["layout"].rows, C, C)
+        error, floor, bound = R.check_acc_sums(lay.embed(out, out.dtype), dict(case, layout=lay))
+        print(f"  resize_acc_sums {what} against float64: gpu {error:.2e}  floor {floor:.2e}  bound {bound:.2e}")
+        assert floor <= bound and error <= bound, (what, error, floor, bound)
     # without statistics: the same values, nothing else written
     y2 = y0.clone()
     L.call("ydl_resize_acc_sums", dt, mode, P(x), C, P(y2), C, N, Hi, Wi, Ho, Wo, C, 0.0, 0.0, None, 0, st)

@@ -105,6 +105,7 @@ extern "C" int ydl_maxpool_fwd(int dtype, const void* x, int ldx, void* y, int l
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
     YDL_CHECK(x && y && ldx >= Cp && ldy >= Cp && k * k <= 255, "bad arguments");
+    YDL_CHECK(aligned16(x) && aligned16(y) && ldx % V == 0 && ldy % V == 0, "16-byte alignment");
     YDL_CHECK(Ho == (Hi + 2 * p - k) / s + 1 && Wo == (Wi + 2 * p - k) / s + 1, "output size mismatch");
     hipStream_t st = (hipStream_t)stream;
     int grid = sgrid((long long)N * Ho * Wo * (Cp / V));
@@ -118,6 +119,7 @@ extern "C" int ydl_maxpool_bwd(int dtype, const void* dy, int lddy, const uint8_
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
     YDL_CHECK(dy && dx && idx && lddy >= Cp && lddx >= Cp, "bad arguments");
+    YDL_CHECK(aligned16(dy) && aligned16(dx) && lddy % V == 0 && lddx % V == 0, "16-byte alignment");
     hipStream_t st = (hipStream_t)stream;
     int grid = sgrid((long long)N * Hi * Wi * (Cp / V));
     if (dtype == YDL_F32) maxpool_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)dy, lddy, idx, (float*)dx, lddx, accumulate, N, Hi, Wi, Ho, Wo, Cp, k, s, p);
@@ -624,6 +626,7 @@ extern "C" int ydl_resize_fwd(int dtype, int mode, const void* x, int ldx, void*
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
     YDL_CHECK(x && y && mode >= 0 && mode <= 2 && ldx >= Cp && ldy >= Cp, "bad arguments");
+    YDL_CHECK(aligned16(x) && aligned16(y) && ldx % V == 0 && ldy % V == 0, "16-byte alignment");
     float sh = axis_scale(mode, Hi, Ho, scale_h), sw = axis_scale(mode, Wi, Wo, scale_w);
     hipStream_t st = (hipStream_t)stream;
     if (g_resize_rows && (long long)N * Ho < (1ll << 30)) {
@@ -664,6 +667,7 @@ extern "C" int ydl_resize_bwd(int dtype, int mode, const void* dy, int lddy, voi
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
     YDL_CHECK(dy && dx && mode >= 0 && mode <= 2 && lddy >= Cp && lddx >= Cp, "bad arguments");
+    YDL_CHECK(aligned16(dy) && aligned16(dx) && lddy % V == 0 && lddx % V == 0, "16-byte alignment");
     float sh = axis_scale(mode, Hi, Ho, scale_h), sw = axis_scale(mode, Wi, Wo, scale_w);
     hipStream_t st = (hipStream_t)stream;
     int grid = sgrid((long long)N * Hi * Wi * (Cp / V));
@@ -788,6 +792,7 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const T* __restrict__
 }
 extern "C" int ydl_nchw_to_nhwc(int dtype, const float* src, void* dst, int ldd, int N, int C, int H, int W, void* stream) {
     YDL_CHECK(src && dst && ldd >= C && ldd % 8 == 0, "ldd must cover C and be a multiple of 8");
+    YDL_CHECK(aligned16(dst), "16-byte alignment");
     long long HW = (long long)H * W;
     dim3 grid((unsigned)((HW + 255) / 256), N);
     hipStream_t st = (hipStream_t)stream;
@@ -880,6 +885,7 @@ extern "C" int ydl_nchw_to_s2d(int dtype, const float* src, void* dst, int ldd, 
 }
 extern "C" int ydl_nhwc_to_nchw(int dtype, const void* src, int lds_, float* dst, int N, int C, int H, int W, int accumulate, void* stream) {
     YDL_CHECK(src && dst && lds_ >= round_up(C, dtype == YDL_F32 ? 4 : 8), "source stride must cover C rounded to a chunk");
+    YDL_CHECK(aligned16(src) && lds_ % (dtype == YDL_F32 ? 4 : 8) == 0, "16-byte alignment");
     long long HW = (long long)H * W;
     dim3 grid((unsigned)((HW + 255) / 256), N);
     hipStream_t st = (hipStream_t)stream;
@@ -912,6 +918,7 @@ extern "C" int ydl_scale_channels(int dtype, const void* x, int ldx, const float
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
     YDL_CHECK(x && y && gate && ldx >= Cp && ldy >= Cp, "bad arguments");
+    YDL_CHECK(aligned16(x) && aligned16(y) && ldx % V == 0 && ldy % V == 0, "16-byte alignment");
     hipStream_t st = (hipStream_t)stream;
     int grid = sgrid((long long)N * hw * (Cp / V));
     if (dtype == YDL_F32) scale_channels_kernel<float><<<grid, 256, 0, st>>>((const float*)x, ldx, gate, (float*)y, ldy, N, hw, C, Cp);
@@ -954,12 +961,15 @@ __global__ __launch_bounds__(256) void global_pool_fwd_kernel(const T* __restric
         const int e = threadIdx.x;
         float a = 0.f, b = -INFINITY;
         int bi = 0;
+        bool bnan = false;
         for (int t = 0; t < 256; ++t) {
             a += ss[t][e];
             float v = sm[t][e];
             int vi = si[t][e];
-            // first maximum in scan order (ATen adaptive_max_pool semantics): larger value, or equal value at lower index
-            if (v > b || (v == b && vi < bi)) { b = v; bi = vi; }
+            const bool vnan = v != v;
+            // ATen adaptive_max_pool semantics (one scan in pixel order with `v > best || isnan(v)`): the first maximum, i.e. the
+            // larger value or the equal value at the lower index; a NaN beats every number and the LAST NaN stays
+            if (bnan ? (vnan && vi > bi) : (vnan || v > b || (v == b && vi < bi))) { b = v; bi = vi; bnan = vnan; }
         }
         ET<T>::st(avg + (size_t)n * lda + c + e, a / (float)HW);
         ET<T>::st(mx + (size_t)n * ldm + c + e, b);
@@ -997,6 +1007,7 @@ extern "C" int ydl_global_pool_fwd(int dtype, const void* x, int ldx, void* avg,
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
     YDL_CHECK(x && avg && mx && argmax && ldx >= Cp && lda >= Cp && ldm >= Cp, "bad arguments");
+    YDL_CHECK(aligned16(x) && ldx % V == 0, "16-byte alignment");
     dim3 grid(Cp / V, N);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == YDL_F32) global_pool_fwd_kernel<float><<<grid, 256, 0, st>>>((const float*)x, ldx, (float*)avg, lda, (float*)mx, ldm, argmax, HW, Cp);
@@ -1009,6 +1020,7 @@ extern "C" int ydl_global_pool_bwd(int dtype, const void* davg, int lda, const v
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
     YDL_CHECK(dx && argmax && lddx >= Cp && (davg || dmx), "bad arguments");
+    YDL_CHECK(aligned16(dx) && lddx % V == 0, "16-byte alignment");
     hipStream_t st = (hipStream_t)stream;
     int grid = sgrid((long long)N * HW * (Cp / V));
     if (dtype == YDL_F32) global_pool_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)davg, lda, (const float*)dmx, ldm, argmax, (float*)dx, lddx, accumulate, N, HW, Cp);
@@ -1090,6 +1102,7 @@ extern "C" int ydl_channel_dot(int dtype, const void* a, int lda, const void* b,
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
     YDL_CHECK(a && b && out && lda >= Cp && ldb >= Cp, "bad arguments");
+    YDL_CHECK(aligned16(a) && aligned16(b) && lda % V == 0 && ldb % V == 0, "16-byte alignment");
     dim3 grid(Cp / V, N);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == YDL_F32) channel_dot_kernel<float><<<grid, 256, 0, st>>>((const float*)a, lda, (const float*)b, ldb, out, HW, C);
