@@ -187,6 +187,35 @@ int ydl_gconv_dgrad(const ydl_conv_geom* g, int groups, int dtype, const void* d
 int64_t ydl_gconv_wgrad_ws_bytes(const ydl_conv_geom* g, int groups, int dtype);
 int ydl_gconv_wgrad(const ydl_conv_geom* g, int groups, int dtype, const void* x, const void* dy, float* dw, float* ws, void* stream);
 
+/* ---- cross convolution: k taps along ONE image axis (csrc/xconv.hip) -------------------------------
+ * YDL_AXIS_W: nn.Conv2d(Cin, Cout, (1,k), (1,s), (0,p), bias=False);  YDL_AXIS_H: nn.Conv2d(Cin, Cout, (k,1), (s,1), (p,0), bias=False)
+ * — the two convolutions of CrossConv (models/common.py:147-158) — on the same ydl_conv_geom: k, s and p apply along the named axis;
+ * along the other axis the kernel is 1, the stride 1 and the padding 0, so Ho = Hi (W) or Wo = Wi (H).
+ * Served set (ydl_xconv_supported != 0; everything else returns an error that names the failing condition, on the host, before
+ * anything is enqueued): k odd with 3 <= k <= 9, s in {1, 2}, p = k/2, Cin and Cout multiples of 8, ldw = 0, output size
+ * (L + 2p - k)/s + 1 along the axis, pixel strides as for ydl_conv_fwd.  x, y, dy, dx may be channel slices of wider buffers;
+ * channels outside the slice are never read into a result and never written.  f32 accumulation, no atomics: the same launches
+ * serve throughput mode and deterministic mode, and every result is bitwise reproducible.
+ * Weights: the KRSC master [Cout][k][Cin] is nn.Conv2d(...).weight in channels_last storage for BOTH orientations; the compute
+ * copies w = [Cout][k][Cin] and wt = [Cin][k][Cout] come from ydl_weight_prep with kk = k. */
+enum { YDL_AXIS_W = 0, YDL_AXIS_H = 1 };
+int ydl_xconv_supported(const ydl_conv_geom* g, int axis, int dtype);
+/* y = xconv(x, w).  stats_ws != NULL: also writes per-block (sum, M2) rows of the STORED output, [rows][2][Cout] floats with
+ * rows = ceil(N*Ho*Wo / block_m), row b covering pixels [b*block_m, (b+1)*block_m), in the format ydl_bn_finalize consumes.
+ * ydl_xconv_fwd_block_m / _stats_ws_bytes are pure host functions of the geometry (0 outside the served set); the workspace size
+ * includes the room ydl_bn_finalize needs behind the rows. */
+int ydl_xconv_fwd_block_m(const ydl_conv_geom* g, int axis, int dtype);
+int64_t ydl_xconv_fwd_stats_ws_bytes(const ydl_conv_geom* g, int axis, int dtype);
+int ydl_xconv_fwd(const ydl_conv_geom* g, int axis, int dtype, const void* x, const void* w, void* y, float* stats_ws, void* stream);
+/* dx (+)= xconv_transpose(dy, wt); at stride 2 a gather over the exact quotients (i + p - t)/2.  accumulate != 0 adds into dx. */
+int ydl_xconv_dgrad(const ydl_conv_geom* g, int axis, int dtype, const void* dy, const void* wt, void* dx, int accumulate,
+                    void* stream);
+/* dw [Cout][k][Cin] (f32, the master gradient's layout) += sum over pixels dy^T * shifted x.  Every block stores its partial tile
+ * into ws (ydl_xconv_wgrad_ws_bytes, a pure host function: the split count depends on the geometry alone) and a second kernel adds
+ * the partials into dw in a fixed order: bitwise reproducible.  dw holds zeros or the running sum of gradient accumulation. */
+int64_t ydl_xconv_wgrad_ws_bytes(const ydl_conv_geom* g, int axis, int dtype);
+int ydl_xconv_wgrad(const ydl_conv_geom* g, int axis, int dtype, const void* x, const void* dy, float* dw, float* ws, void* stream);
+
 /* ---- train-mode BatchNorm + activation ------------------------------------------------------------- */
 /* Chan-merge the per-block partials; writes mean/invstd (saved for backward), scale=gamma*invstd,
  * shift=beta-mean*scale; updates running_mean/var (momentum, unbiased var) and is a no-op on them if NULL. */

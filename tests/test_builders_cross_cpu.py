@@ -1,0 +1,190 @@
+"""CPU: cross convolutions.  ``Conv`` takes a kernel of (1, k) or (k, 1) with stride (1, s) / (s, 1) under one rule (k odd in 3..9, s in
+{1, 2}, p = None or autopad(k), g = 1, d = 1, channels multiples of 8); ``CrossConv`` (models/common.py:147-158) and ``C3x`` (:175-180)
+have the reference's constructor signatures, attribute names and state_dict layout (key lists and shapes recorded from the reference's
+own classes by tools/make_cross_golden.py); ``parse_model`` resolves both rows, everything outside the rule is refused by name, and the
+library's host-side queries ``ydl_xconv_supported`` / ``_fwd_block_m`` / ``_fwd_stats_ws_bytes`` / ``_wgrad_ws_bytes`` draw the same
+line as the constructor."""
+import ctypes
+import glob
+import json
+import os
+
+import numpy as np
+import pytest
+
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+FILES = sorted(glob.glob(os.path.join(GOLDEN, "cross_*.npz")))
+NAMES = ["cross_c3x_32_32_n2", "cross_conv_1x3_16_24", "cross_conv_5x1_s2_16_16", "cross_crossconv_16_16_add", "cross_crossconv_16_32_s2"]
+# 3 x 32 x 32 input -> 16 ch @ 16^2 -> CrossConv as a down-sampler (k = 3, s = 2: 32 ch @ 8^2) -> C3x with n = round(6 * 0.33) = 2
+# CrossConvs with shortcuts on 16 hidden channels -> 12 classes
+YAML = {"nc": 12, "width_multiple": 0.5, "depth_multiple": 0.33,
+        "backbone": [[-1, 1, "Conv", [32, 6, 2, 2]], [-1, 1, "CrossConv", [64, 3, 2]], [-1, 6, "C3x", [64]]],
+        "head": [[-1, 1, "Conv", [12, 1, 1]]]}
+
+# (c1, c2, k, s, p) -> served
+CASES = [((16, 24, (1, 3), (1, 1), None), True), ((16, 16, (5, 1), (2, 1), None), True), ((8, 8, (1, 9), (1, 2), None), True),
+         ((64, 32, (7, 1), 1, None), True), ((16, 16, (1, 3), (1, 1), [0, 1]), True), ((16, 16, (3, 1), (1, 1), (1, 0)), True),
+         ((16, 16, (1, 4), (1, 1), None), False), ((16, 16, (1, 11), (1, 1), None), False), ((16, 16, (1, 3), (1, 3), None), False),
+         ((12, 16, (1, 3), (1, 1), None), False), ((16, 12, (3, 1), (1, 1), None), False), ((16, 16, (1, 3), (1, 1), 0), False),
+         ((16, 16, (3, 1), (1, 1), (0, 0)), False)]
+
+
+def build(z):
+    """the module a fixture describes (weights not loaded); JSON turned the kernel and stride pairs into lists"""
+    import yolo_dual_amd as ydl
+    return getattr(ydl, str(z["cls"]))(*json.loads(str(z["args"])))
+
+
+def test_the_five_fixtures_are_present_small_and_carry_the_floors():
+    assert [os.path.basename(f)[:-4] for f in FILES] == NAMES
+    assert all(os.path.getsize(f) < (1 << 20) for f in FILES)
+    assert [str(np.load(f)["cls"]) for f in FILES] == ["C3x", "Conv", "Conv", "CrossConv", "CrossConv"]
+    for f in FILES:
+        z = np.load(f)
+        for kind in ("out", "grad", "run"):
+            v = float(z["floor." + kind])
+            assert 2.0 ** -10 < v < 0.1, (f, kind, v)      # at least a fraction of one bf16 rounding of the largest element
+
+
+@pytest.mark.parametrize("path", FILES, ids=lambda p: os.path.basename(p)[:-4])
+def test_state_dict_matches_the_reference_modules(path):
+    import torch
+    z = np.load(path)
+    mod = build(z)
+    want = [(str(k), tuple(z["p." + str(k)].shape)) for k in z["keys"]]
+    assert [(k, tuple(v.shape)) for k, v in mod.state_dict().items()] == want
+    mod.load_state_dict({k: torch.from_numpy(z["p." + k]).to(mod.state_dict()[k].dtype) for k, _ in want})
+    for m in mod.modules():                                 # loading leaves the KRSC master in place
+        if isinstance(m, torch.nn.Conv2d):
+            assert m.weight.permute(0, 2, 3, 1).is_contiguous()
+
+
+def test_constructor_forms():
+    import torch.nn as nn
+    import yolo_dual_amd as ydl
+    from yolo_dual_amd import _lib as L
+    c = ydl.Conv(16, 24, (1, 3), (1, 1))
+    assert c.conv.weight.shape == (24, 16, 1, 3) and c.conv.padding == (0, 1) and c.conv.stride == (1, 1) and c.conv.kernel_size == (1, 3)
+    assert c.cross and c.axis == L.AXIS_W and (c.k, c.s, c.p) == (3, 1, 1) and not c.grouped and not c.depthwise
+    assert c.conv.weight.permute(0, 2, 3, 1).is_contiguous()            # KRSC master [c2][k][c1]
+    assert c._gemm_dims() == (24, 3, 16) and isinstance(c.act, nn.SiLU) and c.conv.bias is None
+    h = ydl.Conv(16, 16, (5, 1), (2, 1))
+    assert h.conv.weight.shape == (16, 16, 5, 1) and h.conv.padding == (2, 0) and h.conv.stride == (2, 1)
+    assert h.cross and h.axis == L.AXIS_H and (h.k, h.s, h.p) == (5, 2, 2) and h.conv.weight.permute(0, 2, 3, 1).is_contiguous()
+    assert ydl.Conv(16, 16, (1, 3), 1).conv.stride == (1, 1)            # the int stride 1
+    assert ydl.Conv(16, 16, (1, 3), (1, 1), None, 1, False).act_code == 0 and ydl.Conv(16, 16, (3, 1), (1, 1), act=nn.ReLU()).act_code == 2
+    # a pair with equal entries means the int
+    a, b = ydl.Conv(8, 16, (3, 3), (2, 2)), ydl.Conv(8, 16, 3, 2)
+    assert not a.cross and (a.k, a.s, a.p) == (b.k, b.s, b.p) == (3, 2, 1) and a.conv.weight.shape == b.conv.weight.shape == (16, 8, 3, 3)
+    assert a.conv.kernel_size == b.conv.kernel_size and a.conv.stride == b.conv.stride and a.conv.padding == b.conv.padding
+    assert not ydl.Conv(8, 8, (1, 1), (1, 1)).cross and ydl.Conv(8, 8, (1, 1)).k == 1 and not ydl.Conv(8, 8, 3).cross
+    # attribute layout of the blocks
+    x = ydl.CrossConv(16, 32, 3, 2)
+    assert [n for n, _ in x.named_children()] == ["cv1", "cv2"] and x.add is False
+    assert x.cv1.conv.weight.shape == (32, 16, 1, 3) and x.cv1.conv.stride == (1, 2) and x.cv2.conv.weight.shape == (32, 32, 3, 1)
+    assert x.cv2.conv.stride == (2, 1) and x.cv2.conv.padding == (1, 0)
+    assert ydl.CrossConv(16, 16, 3, 1, 1, 1.0, True).add is True and ydl.CrossConv(16, 32, 3, 1, 1, 1.0, True).add is False
+    assert ydl.CrossConv(16, 32, 5, 1, 1, 0.5).cv1.conv.weight.shape == (16, 16, 1, 5)
+    m = ydl.C3x(32, 32, 2)
+    assert isinstance(m, ydl.C3Common) and [n for n, _ in m.named_children()] == ["cv1", "cv2", "cv3", "m"] and m.c_ == 16
+    assert len(m.m) == 2 and all(type(b) is ydl.CrossConv and b.add for b in m.m)
+    assert m.m[0].cv1.conv.weight.shape == (16, 16, 1, 3) and m.m[1].cv2.conv.weight.shape == (16, 16, 3, 1)
+    assert not any(b.add for b in ydl.C3x(32, 32, 2, False).m)
+
+
+def test_parse_model_builds_the_cross_rows():
+    import torch.nn as nn
+    import yolo_dual_amd as ydl
+    net = ydl.SegYoloModel(YAML)
+    down, c3x, last = net.model[1], net.model[2], net.model[3]
+    assert [type(m) for m in (down, c3x, last)] == [ydl.CrossConv, ydl.C3x, ydl.Conv]
+    assert down.type == "models.common.CrossConv" and c3x.type == "models.common.C3x"
+    # width gain 0.5 on c2, c1 from the previous row; n is inserted for C3x only (depth gain 0.33: 6 -> 2)
+    assert down.cv1.conv.weight.shape == (32, 16, 1, 3) and down.cv1.conv.stride == (1, 2) and down.cv2.conv.stride == (2, 1) and not down.add
+    assert len(c3x.m) == 2 and c3x.cv1.conv.weight.shape == (16, 32, 1, 1) and c3x.m[0].cv1.conv.weight.shape == (16, 16, 1, 3)
+    assert last.conv.weight.shape == (12, 32, 1, 1)
+    rep = ydl.parse_model({"nc": 12, "backbone": [[-1, 1, "Conv", [16, 3, 2]], [-1, 2, "CrossConv", [16, 3, 1, 1, 1.0, True]]], "head": []}, [3])[0][1]
+    assert isinstance(rep, nn.Sequential) and len(rep) == 2 and all(type(m) is ydl.CrossConv and m.add for m in rep)
+
+
+def test_what_lies_outside_the_served_set_is_refused():
+    import yolo_dual_amd as ydl
+    for args in ((16, 16, (3, 5)), (16, 16, (5, 3), (1, 1)),                     # both entries > 1 and unequal
+                 (16, 16, (1, 3), (2, 1)), (16, 16, (3, 1), (1, 2)), (16, 16, (1, 3), 2), (16, 16, 3, (1, 2)),   # the stride's axis
+                 (16, 16, (1, 3), (1, 1), None, 2), (16, 16, (1, 3), (1, 1), None, 1, 2, True),                  # g > 1, d > 1
+                 (12, 16, (1, 3), (1, 1)), (16, 12, (3, 1), (1, 1)),             # channels that are no multiples of 8
+                 (16, 16, (1, 4), (1, 1)), (16, 16, (11, 1), (1, 1)),            # k even, k > 9
+                 (16, 16, (1, 3), (1, 3)), (16, 16, (1, 3), (1, 1), 0)):         # s = 3; a padding that is not autopad's
+        with pytest.raises(NotImplementedError, match="cross"):
+            ydl.Conv(*args)
+    with pytest.raises(NotImplementedError, match="groups"):
+        ydl.CrossConv(16, 16, 3, 1, 2)
+    with pytest.raises(NotImplementedError, match="groups"):
+        ydl.C3x(32, 32, 1, True, 2)
+    with pytest.raises(NotImplementedError, match="cross"):
+        ydl.Conv(16, 16, (1, 3), (1, 1)).fuse()
+    # the model-level fuse() skips cross Convs the way it skips grouped and depth-wise ones
+    from yolo_dual_amd.models import _YamlSegModel
+    net = ydl.SegYoloModel(YAML)
+    _YamlSegModel.fuse(net)
+    assert getattr(net.model[1].cv1, "_fused", None) is None and getattr(net.model[2].m[0].cv2, "_fused", None) is None
+    assert net.model[3]._fused is not None and net.model[2].cv1._fused is not None
+
+
+def test_the_library_queries_agree_with_the_constructor():
+    import yolo_dual_amd as ydl
+    from yolo_dual_amd import _lib as L
+    lib = L.lib()
+    for (c1, c2, k, s, p), served in CASES:
+        try:
+            ydl.Conv(c1, c2, k, s, p)
+            made = True
+        except NotImplementedError:
+            made = False
+        assert made == served, (c1, c2, k, s, p)
+        axis = L.AXIS_W if k[0] == 1 else L.AXIS_H
+        kk = max(k)
+        sv = s if isinstance(s, int) else max(s)
+        pad = kk // 2 if p is None else max(p) if isinstance(p, (tuple, list)) else p
+        H, W = 12, 10
+        Lo = ((W if axis == L.AXIS_W else H) + 2 * pad - kk) // sv + 1
+        Ho, Wo = (H, Lo) if axis == L.AXIS_W else (Lo, W)
+        for dt in (L.YDL_F32, L.YDL_BF16):
+            geom = L.ConvGeom(2, H, W, c1, Ho, Wo, c2, kk, sv, pad, c1, c2, 0)
+            gp = ctypes.byref(geom)
+            assert lib.ydl_xconv_supported(gp, axis, dt) == int(served), (c1, c2, k, s, p, dt)
+            assert (lib.ydl_xconv_fwd_block_m(gp, axis, dt) > 0) == served
+            assert (lib.ydl_xconv_fwd_stats_ws_bytes(gp, axis, dt) > 0) == served
+            assert (lib.ydl_xconv_wgrad_ws_bytes(gp, axis, dt) > 0) == served
+    # the output extent belongs to the axis: a W geometry is no H geometry, a weight row stride is refused, so is an unknown axis
+    geom = L.ConvGeom(2, 12, 10, 16, 12, 5, 16, 3, 2, 1, 16, 16, 0)
+    gp = ctypes.byref(geom)
+    assert lib.ydl_xconv_supported(gp, L.AXIS_W, L.YDL_BF16) == 1 and lib.ydl_xconv_supported(gp, L.AXIS_H, L.YDL_BF16) == 0
+    assert lib.ydl_xconv_supported(gp, 2, L.YDL_BF16) == 0
+    geom.ldw = 64
+    assert lib.ydl_xconv_supported(gp, L.AXIS_W, L.YDL_BF16) == 0
+    geom.ldw, geom.ldx = 0, 20                              # a pixel stride that is no 16-byte multiple
+    assert lib.ydl_xconv_supported(gp, L.AXIS_W, L.YDL_BF16) == 0
+    # the split count of the weight gradient is a function of the geometry alone: the same answer twice
+    geom = L.ConvGeom(16, 160, 160, 64, 160, 160, 64, 3, 1, 1, 64, 64, 0)
+    gp = ctypes.byref(geom)
+    assert lib.ydl_xconv_wgrad_ws_bytes(gp, L.AXIS_H, L.YDL_BF16) == lib.ydl_xconv_wgrad_ws_bytes(gp, L.AXIS_H, L.YDL_BF16) > 0
+
+
+def test_a_refused_launch_is_an_error_with_a_message_on_the_host():
+    from yolo_dual_amd import _lib as L
+    lib = L.lib()
+    for (Cin, Cout, k, s, p), word in (((12, 16, 3, 1, 1), b"multiples of 8"), ((16, 16, 4, 1, 2), b"k must be odd"),
+                                       ((16, 16, 3, 3, 1), b"s must be 1 or 2"), ((16, 16, 3, 1, 0), b"p must be k/2")):
+        Wo = (10 + 2 * p - k) // s + 1
+        geom = L.ConvGeom(2, 12, 10, Cin, 12, Wo, Cout, k, s, p, 16, 16, 0)
+        gp = ctypes.byref(geom)
+        for rc in (lib.ydl_xconv_fwd(gp, L.AXIS_W, L.YDL_BF16, None, None, None, None, None),
+                   lib.ydl_xconv_dgrad(gp, L.AXIS_W, L.YDL_BF16, None, None, None, 0, None),
+                   lib.ydl_xconv_wgrad(gp, L.AXIS_W, L.YDL_BF16, None, None, None, None, None)):
+            assert rc != 0
+            assert word in lib.ydl_last_error(), lib.ydl_last_error()
+    # a served geometry with null pointers is refused too, before anything is enqueued
+    geom = L.ConvGeom(2, 12, 10, 16, 12, 10, 16, 3, 1, 1, 16, 16, 0)
+    assert lib.ydl_xconv_fwd(ctypes.byref(geom), L.AXIS_W, L.YDL_BF16, None, None, None, None, None) != 0
+    assert b"null pointer" in lib.ydl_last_error()

@@ -14,6 +14,7 @@ ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2
 RES_NONE, RES_AFTER_ACT, RES_BEFORE_ACT = 0, 1, 2
 RES_GRAD_ACCUMULATE = 16
 LOSS_DICE, LOSS_JACCARD = 0, 1
+AXIS_W, AXIS_H = 0, 1             # YDL_AXIS_* of ydl.h
 OPT_ADAM, OPT_ADAMW, OPT_RMSPROP = 1, 2, 3      # YDL_OPT_* of ydl.h
 OPT_MAX_CLASSES, OPT_HYPER_FLOATS = 16, 76
 RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BILINEAR_AC = 0, 1, 2
@@ -71,6 +72,13 @@ SIGNATURES = {
     "ydl_gconv_dgrad": (_i, [_G, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "ydl_gconv_wgrad_ws_bytes": (_i64, [_G, _i, _i]),
     "ydl_gconv_wgrad": (_i, [_G, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ydl_xconv_supported": (_i, [_G, _i, _i]),
+    "ydl_xconv_fwd_block_m": (_i, [_G, _i, _i]),
+    "ydl_xconv_fwd_stats_ws_bytes": (_i64, [_G, _i, _i]),
+    "ydl_xconv_fwd": (_i, [_G, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ydl_xconv_dgrad": (_i, [_G, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "ydl_xconv_wgrad_ws_bytes": (_i64, [_G, _i, _i]),
+    "ydl_xconv_wgrad": (_i, [_G, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ydl_bn_finalize": (_i, [_vp, _i, _i, _i64, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "ydl_bn_eval_coeffs": (_i, [_i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "ydl_bn_act_fwd": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i64, _i, _vp]),
@@ -247,10 +255,11 @@ def profile_end():
     for name, e0, e1, g in rec:
         flops, nbytes = 0.0, 0.0
         if isinstance(g, ConvGeom):
-            flops = 2.0 * g.N * g.Ho * g.Wo * g.Cout * g.k * g.k * g.Cin
+            taps = g.k if "xconv" in name else g.k * g.k        # a cross convolution has k taps along one axis
+            flops = 2.0 * g.N * g.Ho * g.Wo * g.Cout * taps * g.Cin
             # algorithmic bytes: input, output and weights once (the weight gradient is f32)
             es = getattr(g, "_es", 2)
-            wb = float(g.Cout) * g.k * g.k * g.Cin
+            wb = float(g.Cout) * taps * g.Cin
             nbytes = (float(g.N) * g.Hi * g.Wi * g.Cin + float(g.N) * g.Ho * g.Wo * g.Cout) * es + wb * (4 if "wgrad" in name else es)
             if getattr(g, "_both", False):
                 flops *= 2.0
@@ -318,6 +327,12 @@ def call(name: str, *args):
         g._kernel = last_kernel(6 if g._bn else 1 if ("dgrad" in name or "bwd_pw" in name) else 2 if "wgrad" in name else 0)
         g._acc = (int(args[25]) if g._bn else int(args[5]) if "dgrad" in name else int(args[6]) if name.startswith("ydl_conv_fwd")
                   else int(args[7]) if g._both else 0)
+    elif name in ("ydl_xconv_fwd", "ydl_xconv_dgrad", "ydl_xconv_wgrad"):      # k taps, not k*k: profile_end() goes by the name
+        src = args[0]._obj
+        g = ConvGeom(*[getattr(src, f) for f, _ in ConvGeom._fields_])
+        g._es = 4 if args[2] == YDL_F32 else 2
+        g._kernel = "xconv_h" if args[1] else "xconv_w"
+        g._acc = int(args[6]) if name == "ydl_xconv_dgrad" else 0
     elif name == "ydl_bn_act_fwd":          # algorithmic bytes: y (+ residual) read once, out written once
         es = 4 if args[0] == YDL_F32 else 2
         g = float(args[11]) * args[12] * es * (2 + (1 if args[7] else 0))

@@ -27,7 +27,7 @@ from . import _lib as L
 from .modules import (ASPP, RFB, GAM, AttentionConv, AttentionStem, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C2f_DCN, C3, C3_DCN, C3_DCNCommon, C3_DCNV3,
                       C3Common, C3Ghost, C3k2, C3TR, Concat, DWConv, GhostBottleneck, GhostConv, TransformerBlock,
                       Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region,
-                      SPP, C3SPP, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF)
+                      SPP, C3SPP, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF, CrossConv, C3x)
 from .tape import Tape, Var
 
 LOGGER = logging.getLogger("yolo_dual_amd")
@@ -229,7 +229,7 @@ class _YamlSegModel(YdlModule):
     def fuse(self):
         """models/yolo.py:140-148: fold every Conv's BatchNorm into its convolution (inference only)"""
         for m in self.modules():
-            if isinstance(m, Conv) and not m.depthwise and not m.grouped:
+            if isinstance(m, Conv) and not m.depthwise and not m.grouped and not m.cross:
                 m.fuse()
         return self
 
@@ -529,7 +529,7 @@ _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": 
                 "AttentionConv": AttentionConv, "AttentionStem": AttentionStem, "DWConv": DWConv, "GhostConv": GhostConv,
                 "GhostBottleneck": GhostBottleneck, "C3Ghost": C3Ghost, "C3TR": C3TR, "TransformerBlock": TransformerBlock,
                 "ASPP": ASPP, "RFB": RFB, "SPP": SPP, "C3SPP": C3SPP, "SimSPPF": SimSPPF, "SPPCSPC": SPPCSPC,
-                "SPPCSPC_group": SPPCSPC_group, "SimCSPSPPF": SimCSPSPPF}
+                "SPPCSPC_group": SPPCSPC_group, "SimCSPSPPF": SimCSPSPPF, "CrossConv": CrossConv, "C3x": C3x}
 
 
 def parse_model(d: dict, ch: List[int], deformable: bool = False):
@@ -550,12 +550,12 @@ def parse_model(d: dict, ch: List[int], deformable: bool = False):
         n = n_ = max(round(n * gd), 1) if n > 1 else n
         if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3, C3_DCNCommon, AttentionConv, AttentionStem,
                    DWConv, GhostConv, GhostBottleneck, C3Ghost, C3TR, ASPP, RFB, SPP, C3SPP, SimSPPF, SPPCSPC, SPPCSPC_group,
-                   SimCSPSPPF):
+                   SimCSPSPPF, CrossConv, C3x):
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)
             args = [c1, c2, *args[1:]]
-            if cls in (C3Common, C3_DCNV3, C3_DCNCommon, C3Ghost, C3TR):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
+            if cls in (C3Common, C3_DCNV3, C3_DCNCommon, C3Ghost, C3TR, C3x):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
                 args.insert(2, n)
                 n = 1
         elif cls is Concat:

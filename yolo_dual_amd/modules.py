@@ -27,7 +27,7 @@ __all__ = ["autopad", "Conv", "C3", "C3Common", "Bottleneck", "C2f", "C3k2", "GA
            "BasicBlock", "BottleneckBlock", "SegmentHead", "run_region", "Linear", "DCNv3", "DCNV3_YoLo", "Bottleneck_DCNV3",
            "C3_DCNV3", "DeformConv2d", "C3_DCN", "C2f_DCN", "DCNv2",
            "Bottleneck_DCN", "C3_DCNCommon", "AttentionConv", "AttentionStem", "DWConv", "GhostConv", "GhostBottleneck", "C3Ghost",
-           "BasicConv", "RFB", "ASPP"]
+           "BasicConv", "RFB", "ASPP", "CrossConv", "C3x"]
 
 
 def autopad(k, p=None, d=1):
@@ -93,7 +93,7 @@ def refresh_weights(fn: nn.Module, tape: Tape) -> None:
     """one batched launch re-deriving the compute-layout weights of every stale Conv under ``fn``"""
     convs = getattr(fn, "_ydl_convs", None)
     if convs is None:
-        convs = [m for m in fn.modules() if isinstance(m, Conv) and not m.depthwise and not m.grouped and m.d == 1 and m.bn is not None]     # (a dilated Conv's GEMM view is _DeformGemm; a grouped Conv prepares its own block-diagonal copies)
+        convs = [m for m in fn.modules() if isinstance(m, Conv) and not m.depthwise and not m.grouped and not m.cross and m.d == 1 and m.bn is not None]     # (a dilated Conv's GEMM view is _DeformGemm; a grouped Conv prepares its own block-diagonal copies)
         fn._ydl_convs = convs
         fn._ydl_csp = [m for m in fn.modules() if isinstance(getattr(m, "cv1", None), Conv) and isinstance(getattr(m, "cv2", None), Conv)]
     # sibling pairs that ran fused last time are prepared as ONE matrix (their masters are adjacent), their members not at all
@@ -367,6 +367,52 @@ def _act_code(act) -> int:
     raise NotImplementedError(f"activation {act!r} is not supported by the HIP path (SiLU/ReLU/Identity)")
 
 
+def _cross_args(c1, c2, k, s, p, g, d):
+    """Conv with a tuple kernel or stride.  Equal entries mean the int: -> (k, s, p, None).  A kernel (1, k) / (k, 1) with stride
+    (1, s) / (s, 1) (or the int 1) is a cross convolution along W / H: -> (k, s, p, axis) with the axis's own k, s, p.  Everything else
+    is refused: the served set is ydl_xconv_supported's."""
+    def pair(v, what):
+        if isinstance(v, (tuple, list)):
+            if len(v) != 2 or not all(isinstance(e, int) and not isinstance(e, bool) for e in v):
+                raise TypeError(f"Conv: {what}={v!r} must be an int or a pair of ints")
+            return tuple(v)
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise TypeError(f"Conv: {what}={v!r} must be an int or a pair of ints")
+        return None
+    kt, st = pair(k, "k"), pair(s, "s")
+    got = f"got c1={c1}, c2={c2}, k={k}, s={s}, p={p}, g={g}, d={d}"
+    rule = ("cross convolution: the HIP path serves k = (1, k) with s = (1, s) and k = (k, 1) with s = (s, 1) (or the int s = 1), k odd in "
+            "3..9, s in {1, 2}, p = None or autopad(k), g = 1, d = 1, c1 and c2 multiples of 8; ")
+    if kt is None:
+        kt = (k, k)
+    if kt[0] == kt[1]:                         # a square kernel written as a pair
+        if st is not None and st[0] != st[1]:
+            raise NotImplementedError(rule + "a rectangular stride needs a cross kernel; " + got)
+        if isinstance(p, (tuple, list)):
+            if len(p) != 2 or p[0] != p[1]:
+                raise NotImplementedError(rule + "a rectangular padding needs a cross kernel; " + got)
+            p = p[0]
+        return kt[0], (s if st is None else st[0]), p, None
+    if kt[0] != 1 and kt[1] != 1:
+        raise NotImplementedError(rule + "general (kh, kw) kernels with both entries > 1 are not implemented; " + got)
+    axis = L.AXIS_W if kt[0] == 1 else L.AXIS_H
+    kk = kt[1] if axis == L.AXIS_W else kt[0]
+    if st is None:
+        if s != 1:
+            raise NotImplementedError(rule + "an int stride with a cross kernel must be 1; " + got)
+        sv = 1
+    else:
+        sv, other = (st[1], st[0]) if axis == L.AXIS_W else (st[0], st[1])
+        if other != 1:
+            raise NotImplementedError(rule + "the stride lies along the wrong axis; " + got)
+    want = [0, kk // 2] if axis == L.AXIS_W else [kk // 2, 0]
+    if not (p is None or (isinstance(p, (tuple, list)) and list(p) == want)):
+        raise NotImplementedError(rule + got)
+    if g != 1 or d != 1 or c1 % 8 or c2 % 8 or kk % 2 == 0 or not 3 <= kk <= 9 or sv not in (1, 2):
+        raise NotImplementedError(rule + got)
+    return kk, sv, None, axis
+
+
 class Conv(_GemmWeights, YdlModule):
     """``Conv(c1, c2, k=1, s=1, p=None, g=1, act=True)`` (seg scripts) and
     ``Conv(c1, c2, k=1, s=1, p=None, g=1, d=1, act=True)`` (models/common.py): the 7th positional argument is taken
@@ -381,6 +427,11 @@ class Conv(_GemmWeights, YdlModule):
                 d, act = int(d_or_act), True
         else:
             d = int(d_or_act) if not isinstance(d_or_act, bool) else 1
+        self.cross, self.axis = False, L.AXIS_W
+        if isinstance(k, (tuple, list)) or isinstance(s, (tuple, list)):
+            k, s, p, axis = _cross_args(c1, c2, k, s, p, g, d)
+            if axis is not None:
+                self.cross, self.axis = True, axis
         if not all(isinstance(v, int) and not isinstance(v, bool) for v in (c1, c2, k, s, g)):
             raise TypeError(f"Conv arguments must be int: c1={c1}({type(c1)}), c2={c2}({type(c2)})")
         if g <= 0 or c1 % g != 0:
@@ -401,7 +452,11 @@ class Conv(_GemmWeights, YdlModule):
             raise NotImplementedError(f"depth-wise Conv: stride s in {{1,2}}, k in {{1,3,5,7}}, 'same' padding p = k // 2 (got s={s}, k={k}, p={p})")
         self.c1, self.c2, self.k, self.s = c1, c2, k, s
         self.p = autopad(k, p, d)
-        self.conv = nn.Conv2d(c1, c2, k, s, self.p, groups=g, dilation=d, bias=False)
+        if self.cross:                # k taps along one axis: k, s and p are that axis's; (1, k) along W or (k, 1) along H
+            kt, st_, pt = ((1, k), (1, s), (0, self.p)) if self.axis == L.AXIS_W else ((k, 1), (s, 1), (self.p, 0))
+            self.conv = nn.Conv2d(c1, c2, kt, st_, pt, bias=False)
+        else:
+            self.conv = nn.Conv2d(c1, c2, k, s, self.p, groups=g, dilation=d, bias=False)
         self.conv.weight.data = self.conv.weight.data.contiguous(memory_format=torch.channels_last)
         self.bn = _BNHolder(c2)
         self.act = nn.SiLU() if act is True else (act if isinstance(act, nn.Module) else nn.Identity())
@@ -416,6 +471,8 @@ class Conv(_GemmWeights, YdlModule):
         return self.conv.weight
 
     def _gemm_dims(self):
+        if self.cross:                # KRSC master [c2][k][c1], the same memory for (1, k) and (k, 1)
+            return self.c2, self.k, self.c1
         return self.c2, self.k * self.k, self.c1 // self.groups if self.grouped else self.c1
 
     def gconv_weights(self, tape: Tape):
@@ -457,7 +514,7 @@ class Conv(_GemmWeights, YdlModule):
     def grad_dw(self) -> torch.Tensor:
         g = self._grad_of(self.conv.weight).permute(0, 2, 3, 1)
         if not g.is_contiguous():
-            raise RuntimeError("depth-wise weight gradient must be KRSC-contiguous")
+            raise RuntimeError("Conv weight gradient must be KRSC-contiguous (channels_last storage)")
         return g
 
     # -- forward ----------------------------------------------------------------------------------------
@@ -471,6 +528,8 @@ class Conv(_GemmWeights, YdlModule):
             return tape.dw_bn_act(x, self, self.s, act, out=out, res=res, res_mode=res_mode)
         if self.grouped:
             return tape.gconv_bn_act(x, self, act, out=out, res=res, res_mode=res_mode)
+        if self.cross:
+            return tape.xconv_bn_act(x, self, act, out=out, res=res, res_mode=res_mode)
         if getattr(self, "_fused", None) is not None and not tape.train:
             y = tape.conv_bias_act(x, self, act, res=res, res_mode=res_mode)
             return y if out is None else tape.copy(y, out)
@@ -489,6 +548,8 @@ class Conv(_GemmWeights, YdlModule):
             raise NotImplementedError("fuse() of a depth-wise Conv")
         if self.grouped:
             raise NotImplementedError("fuse() of a grouped Conv (the folded eval path runs groups=1 convolutions only)")
+        if self.cross:
+            raise NotImplementedError("fuse() of a cross Conv (the folded eval path runs square convolutions only)")
         if self.d > 1:
             raise NotImplementedError("fuse() of a dilated Conv (the folded eval path runs undilated convolutions only)")
         from .checkpoint import fuse_conv_and_bn
@@ -884,6 +945,39 @@ class C3Ghost(C3Common):
     def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
         super().__init__(c1, c2, n, shortcut, g, e)
         self.m = nn.Sequential(*(GhostBottleneck(self.c_, self.c_) for _ in range(n)))
+
+
+# ----------------------------------------------------------------------------------------------------------
+# cross convolutions (models/common.py:147-158, 175-180)
+# ----------------------------------------------------------------------------------------------------------
+class CrossConv(YdlModule):
+    """models/common.py:147-158: cv2(cv1(x)) (+ x) with cv1 = Conv(c1, c_, (1, k), (1, s)) and cv2 = Conv(c_, c2, (k, 1), (s, 1)), both on
+    Tape.xconv_bn_act; the shortcut is joined after cv2's activation.  g = 1 only."""
+
+    def __init__(self, c1, c2, k=3, s=1, g=1, e=1.0, shortcut=False):
+        super().__init__()
+        if g != 1:
+            raise NotImplementedError(f"CrossConv: groups g={g} is not implemented on the HIP path (g = 1 only)")
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, (1, k), (1, s))
+        self.cv2 = Conv(c_, c2, (k, 1), (s, 1), g=g)
+        self.add = shortcut and c1 == c2
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        h = self.cv1._fwd(tape, x)
+        if self.add:
+            return self.cv2._fwd(tape, h, out=out, res=x, res_mode=L.RES_AFTER_ACT)
+        return self.cv2._fwd(tape, h, out=out)
+
+
+class C3x(C3Common):
+    """models/common.py:175-180: C3 whose m is n CrossConv(c_, c_, 3, 1, g, 1.0, shortcut)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        if g != 1:
+            raise NotImplementedError(f"C3x: groups g={g} is not implemented on the HIP path (g = 1 only)")
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.Sequential(*(CrossConv(self.c_, self.c_, 3, 1, g, 1.0, shortcut) for _ in range(n)))
 
 
 # ----------------------------------------------------------------------------------------------------------

@@ -1366,6 +1366,85 @@ class Tape:
         self.bw.append(bw)
         return out
 
+    def xconv_bn_act(self, x: Var, m, act: int, out: Optional[Var] = None, res: Optional[Var] = None,
+                     res_mode: int = L.RES_NONE) -> Var:
+        """cross Conv+BN+act, a kernel of m.k taps along the axis m.axis with stride m.s along it: out = act(bn(xconv(x))) [+ res] — the
+        two convolutions of CrossConv (models/common.py:147-158).  ydl_xconv_fwd writes the BatchNorm partial rows of its output, so
+        train mode goes conv -> ydl_bn_finalize -> ydl_bn_act_fwd.  The kernels use no atomics: the same launches serve throughput
+        mode and deterministic mode.  ``out`` may be a concat slice."""
+        x = self._flat(x)
+        if res is not None:
+            res = self._flat(res)
+        if out is not None and not out.aligned():       # the BatchNorm kernels work on 8-channel groups: stage an odd slice
+            return self.copy(self.xconv_bn_act(x, m, act, None, res, res_mode), out)
+        Cin, Cout, k, s, ax = m.c1, m.c2, m.k, m.s, m.axis
+        if x.C != Cin:
+            raise RuntimeError(f"cross Conv input channel mismatch: got {x.C}, weight expects {Cin}")
+        N, H, W = x.N, x.H, x.W
+        Ho = (H + 2 * (k // 2) - k) // s + 1 if ax == L.AXIS_H else H
+        Wo = (W + 2 * (k // 2) - k) // s + 1 if ax == L.AXIS_W else W
+        y = self.new(N, Cout, Ho, Wo)
+        if out is None:
+            out = self.new(N, Cout, Ho, Wo)
+        elif (out.N, out.C, out.H, out.W) != (N, Cout, Ho, Wo):
+            raise RuntimeError("xconv_bn_act: output slice has the wrong shape")
+        st = _stream()
+        w, wt = m.compute_weights(self)                 # [Cout][k][Cin] and [Cin][k][Cout]: ydl_weight_prep with kk = k
+        cf = m.coeffs(self.device)
+        npix = N * Ho * Wo
+        cp = round_up(Cout, 8)
+        geom = L.ConvGeom(N, H, W, Cin, Ho, Wo, Cout, k, s, k // 2, x.ld, y.ld, 0)
+        gp = ctypes.byref(geom)
+        if not L.lib().ydl_xconv_supported(gp, ax, self.dt):
+            raise RuntimeError("xconv_bn_act: " + (L.lib().ydl_last_error() or b"?").decode())
+        if self.train:
+            ws = torch.empty(L.lib().ydl_xconv_fwd_stats_ws_bytes(gp, ax, self.dt) // 4, dtype=torch.float32, device=self.device)
+            bm = L.lib().ydl_xconv_fwd_block_m(gp, ax, self.dt)
+            L.call("ydl_xconv_fwd", gp, ax, self.dt, _p(x.t), _p(w), _p(y.t), _p(ws), st)
+            self._bn_coeffs(m, cf, Cout, st, (ws, (npix + bm - 1) // bm, bm, npix, 1))
+        else:
+            L.call("ydl_xconv_fwd", gp, ax, self.dt, _p(x.t), _p(w), _p(y.t), None, st)
+            self._bn_coeffs(m, cf, Cout, st)
+        L.call("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
+               res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
+        if not self.record:
+            return out
+        if not self.train:
+            raise RuntimeError("backward through eval-mode BatchNorm is not supported")
+        if x.need:
+            self._use(x)
+        if res is not None and res.need and res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
+            self._use(res)
+        self._keep.append(geom)
+
+        def bw():
+            if not out.is_set():
+                return
+            st2 = _stream()
+            dy = self.new(N, Cout, Ho, Wo)
+            dout = self._gbuf(out)
+            gw, gb, accw = self._bn_grad_rows(m, cp)
+            dres_t, dres_ld, rmode = self._res_grad(res, res_mode, out, dout)
+            ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
+            L.call("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
+                   _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rmode, act,
+                   _p(dy.t), dy.ld, _p(dres_t), dres_ld, _p(gw), _p(gb), accw, _p(ws2), npix, Cout, cp, st2)
+            m.touch_bn()
+            gb_ = L.ConvGeom(N, H, W, Cin, Ho, Wo, Cout, k, s, k // 2, x.ld, dy.ld, 0)
+            gpb = ctypes.byref(gb_)
+            self._keep.append(gb_)
+            if m.trainable()[0]:
+                gk = m.grad_dw()                                 # KRSC [Cout][k][Cin]: the kernel's dw layout
+                ws3 = torch.empty(max(L.lib().ydl_xconv_wgrad_ws_bytes(gpb, ax, self.dt) // 4, 4), dtype=torch.float32, device=self.device)
+                L.call("ydl_xconv_wgrad", gpb, ax, self.dt, _p(x.t), _p(dy.t), _p(gk), _p(ws3), st2)
+                from . import config as _cfg
+                _cfg.mark_touched(m.conv.weight)
+            if x.need:
+                gx, acc = self.grad_target(x)
+                L.call("ydl_xconv_dgrad", gpb, ax, self.dt, _p(dy.t), _p(wt), _p(gx), acc, st2)
+        self.bw.append(bw)
+        return out
+
     def group_softmax(self, x: Var, G: int, P: int) -> Var:
         """softmax over the P sampling points of each group (modules/dcnv3.py:122-123)"""
         x = self._flat(x)
