@@ -33,7 +33,9 @@ extern "C" {
 #endif
 
 enum { YDL_F32 = 0, YDL_BF16 = 1, YDL_F16 = 2 /* DCNv3 op only */ };
-enum { YDL_ACT_NONE = 0, YDL_ACT_SILU = 1, YDL_ACT_RELU = 2 };
+enum { YDL_ACT_NONE = 0, YDL_ACT_SILU = 1, YDL_ACT_RELU = 2,
+       YDL_ACT_LEAKY = 3 /* z > 0 ? z : slope * z; the slope is the act_param of the *_p entry points, 0 <= slope < 1 */,
+       YDL_ACT_HSWISH = 4 /* z * relu6(z + 3) / 6 */, YDL_ACT_MISH = 5 /* z * tanh(softplus(z)) */ };
 /* residual handling of the fused BN/activation kernels */
 enum { YDL_RES_NONE = 0, YDL_RES_AFTER_ACT = 1 /* C3/C2f: act(bn(y)) + r */, YDL_RES_BEFORE_ACT = 2 /* ResNet: act(bn(y) + r) */,
        YDL_RES_GRAD_ACCUMULATE = 16 /* ydl_bn_act_bwd only, or-ed into res_mode: dres += instead of dres = */ };
@@ -654,6 +656,59 @@ int ydl_aug_crop_mask(const void* src, int h, int w, int x1, int y1, int cw, int
  * ydl_fill_zero: `bytes` bytes at dst (hipMemsetAsync);  ydl_zero2d: dst[p][0:C] = 0 for npix rows of pixel stride ldd */
 int ydl_fill_zero(void* dst, int64_t bytes, void* stream);
 int ydl_zero2d(int dtype, void* dst, int ldd, int64_t npix, int C, void* stream);
+
+/* ---- activations with a run-time parameter ----------------------------------------------------------------------------
+ * The six streaming BatchNorm entry points above, each with one more argument after `act`: act_param, the parameter of the
+ * activation (the negative slope of YDL_ACT_LEAKY; ignored by every other code).  The entry points without it are these with
+ * act_param = 0, and refuse YDL_ACT_LEAKY.  YDL_ACT_LEAKY, YDL_ACT_HSWISH and YDL_ACT_MISH recompute z = y*scale + shift in
+ * the backward, as YDL_ACT_SILU does: they need no saved output, and their backward refuses YDL_RES_BEFORE_ACT. */
+int ydl_bn_act_fwd_p(int dtype, const void* y, int ldy, const float* scale, const float* shift,
+                     const void* res, int ldr, int res_mode, int act, float act_param, void* out, int ldo,
+                     int64_t npix, int Cp, void* stream);
+int ydl_bn_act_bwd_p(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                     const float* gamma, const float* mean, const float* invstd, const float* scale, const float* shift,
+                     int res_mode, int act, float act_param, void* dy, int lddy, void* dres, int lddr,
+                     float* dgamma, float* dbeta, int accumulate_param_grads,
+                     float* ws, int64_t npix, int C, int Cp, void* stream);
+int ydl_bn_act_fwd_sums_p(int dtype, const void* y, int ldy, const float* sums, int sums_ld, int64_t count,
+                          const float* gamma, const float* beta, float eps, float momentum,
+                          float* running_mean, float* running_var, float* mean, float* invstd, float* scale, float* shift,
+                          int replication, const void* res, int ldr, int res_mode, int act, float act_param, void* out, int ldo,
+                          int64_t npix, int C, int Cp, void* stream);
+int ydl_bn_act_bwd_sums_p(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                          const float* mean, const float* invstd, const float* scale, const float* shift,
+                          int res_mode, int act, float act_param, void* dy, int lddy, void* dres, int lddr,
+                          float* dgamma, float* dbeta, int accumulate_param_grads,
+                          float* sums, int64_t npix, int C, int Cp, void* stream);
+int ydl_bn_act_bwd_apply_sums_p(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                                const float* mean, const float* invstd, const float* scale, const float* shift,
+                                int res_mode, int act, float act_param, void* dy, int lddy, void* dres, int lddr,
+                                float* dgamma, float* dbeta, int accumulate_param_grads,
+                                float* sums, int64_t npix, int C, int Cp, void* stream);
+int ydl_bn_act_bwd_reduce_sums_p(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                                 const float* mean, const float* invstd, const float* scale, const float* shift,
+                                 int res_mode, int act, float act_param, void* dres, int lddr, float* sums, int64_t npix, int C, int Cp,
+                                 void* stream);
+
+/* ---- learnable Conv activations (csrc/act.hip) --------------------------------------------------------------------------
+ * AconC (utils/activations.py): out = d * sigmoid(beta * d) + p2 * z with d = (p1 - p2) * z, per channel, on the materialised
+ * BatchNorm output z.  NHWC with pixel strides, 16-byte accesses (pointers 16-byte aligned, strides whole chunks); p1 / p2 hold C
+ * floats and channels [C, Cp) are computed with zeros.  beta is read at beta[sample * beta_stride + c], a sample being hw
+ * consecutive pixels: beta_stride = 0 is AconC's single row, a per-sample row is what a generated beta (MetaAconC) needs. */
+int ydl_acon_fwd(int dtype, const void* z, int ldz, const float* p1, const float* p2, const float* beta, int64_t beta_stride,
+                 void* out, int ldo, int64_t npix, int64_t hw, int C, int Cp, void* stream);
+int64_t ydl_acon_bwd_ws_bytes(int64_t npix, int64_t hw, int64_t beta_stride, int Cp);
+/* one pass over z and dout: dz (dz_accumulate != 0: added to what dz holds, in f32 with one rounding) and the per-channel sums
+ * dp1, dp2 [C] and dbeta (one row of C floats per beta row, same stride), stored or, with accumulate_param_grads != 0, added.
+ * One partial row per CTA in ws and a fixed-order fold: no atomics, two runs give the same bits. */
+int ydl_acon_bwd(int dtype, const void* z, int ldz, const void* dout, int lddo, const float* p1, const float* p2, const float* beta,
+                 int64_t beta_stride, void* dz, int lddz, int dz_accumulate, float* dp1, float* dp2, float* dbeta,
+                 int accumulate_param_grads, float* ws, int64_t npix, int64_t hw, int C, int Cp, void* stream);
+/* FReLU's merge: out = max(a, b).  The backward routes dout to the larger operand and gives half to each on a tie (torch.max(a, b));
+ * da or db may be NULL (not wanted); *_accumulate != 0 adds to what the gradient holds, in f32 with one rounding. */
+int ydl_max2_fwd(int dtype, const void* a, int lda, const void* b, int ldb, void* out, int ldo, int64_t npix, int Cp, void* stream);
+int ydl_max2_bwd(int dtype, const void* a, int lda, const void* b, int ldb, const void* dout, int lddo, void* da, int ldda,
+                 int da_accumulate, void* db, int lddb, int db_accumulate, int64_t npix, int Cp, void* stream);
 
 /* ---- launch-list replay: the training step without its host wall -------------------------------------------------------
  * The reference's hot loop (seg_diceloss_yolov5.py:1084-1103) issues the same sequence of device work every step.  The host

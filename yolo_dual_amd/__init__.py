@@ -11,12 +11,14 @@ from .data import AugmentGPU, LetterboxGPU, draw_augmentations, letterbox_geomet
 from .evaluate import ConfusionMatrix
 from .loss import JaccardSegmentationLoss, SegmentationLoss
 from .models import (ResNet18, ResNet18Seg, ResNet50, ResNet50Seg, ResNet50SegYaml, SegYoloModel, YOLOv5Seg, YOLOv8Seg,
-                     YOLOv9Seg, parse_model)
+                     YOLOv9Seg, default_activation, parse_model, resolve_activation)
 from .modules import (GAM, AttentionConv, AttentionStem, C2f, C3, C3k2, C3_DCNV3, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C3Common, Concat,
                       Conv, C2f_DCN, C3_DCN, C3_DCNCommon, Bottleneck_DCN, DCNv2, DCNv3, DCNV3_YoLo, DeformConv2d, Linear, MaxPool2d, SegmentHead, SPPF, Upsample, autopad,
                       C3Ghost, DWConv, GhostBottleneck, GhostConv, C3TR, TransformerBlock, TransformerLayer, ASPP, RFB, BasicConv,
                       SPP, C3SPP, SimConv, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF, CrossConv, C3x)
 from .deform import deform_conv2d
+from . import activations
+from .activations import AconC, FReLU, Hardswish, MemoryEfficientMish, MetaAconC, Mish, SiLU
 from .optim import FlatAdamEMA, FlatAdamWEMA, FlatArenaOptimizer, FlatRMSPropEMA, FlatSGDEMA, smart_optimizer
 
 __all__ = [n for n in dir() if not n.startswith("_")]

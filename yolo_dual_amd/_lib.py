@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get("YDL_LIB", os.path.join(_HERE, "lib", "libydl_hip.so")
 YDL_F32, YDL_BF16, YDL_F16 = 0, 1, 2
 BN_REPLICAS = 8             # YDL_BN_REPLICAS of ydl.h
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2
+ACT_LEAKY, ACT_HSWISH, ACT_MISH = 3, 4, 5      # YDL_ACT_* of ydl.h; ACT_LEAKY carries its slope (ActCode.param)
+ACT_ACON, ACT_FRELU = 100, 101                 # host side only: the Conv runs ACT_NONE and the layer's own kernels follow (act.hip)
 RES_NONE, RES_AFTER_ACT, RES_BEFORE_ACT = 0, 1, 2
 RES_GRAD_ACCUMULATE = 16
 LOSS_DICE, LOSS_JACCARD = 0, 1
@@ -177,6 +179,11 @@ SIGNATURES = {
     "ydl_aug_crop_mask": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ydl_fill_zero": (_i, [_vp, _i64, _vp]),
     "ydl_zero2d": (_i, [_i, _vp, _i, _i64, _i, _vp]),
+    "ydl_acon_fwd": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _vp]),
+    "ydl_acon_bwd_ws_bytes": (_i64, [_i64, _i64, _i64, _i]),
+    "ydl_acon_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i64, _i64, _i, _i, _vp]),
+    "ydl_max2_fwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp]),
+    "ydl_max2_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i64, _i, _vp]),
     "ydl_replay_create": (_vp, []),
     "ydl_replay_destroy": (None, [_vp]),
     "ydl_replay_fn_count": (_i, []),
@@ -187,6 +194,32 @@ SIGNATURES = {
     "ydl_replay_size": (_i, [_vp]),
     "ydl_replay_run": (_i, [_vp, _i, _i, C.POINTER(_vp), _i]),
 }
+
+# position of `act` in the streaming BatchNorm entry points; the `_p` sibling of each takes one float act_param right after it
+BN_ACT_ARG = {"ydl_bn_act_fwd": 8, "ydl_bn_act_fwd_sums": 20, "ydl_bn_act_bwd": 13, "ydl_bn_act_bwd_sums": 12,
+              "ydl_bn_act_bwd_apply_sums": 12, "ydl_bn_act_bwd_reduce_sums": 12}
+for _n, _k in BN_ACT_ARG.items():
+    _r, _a = SIGNATURES[_n]
+    SIGNATURES[_n + "_p"] = (_r, _a[:_k + 1] + [_f] + _a[_k + 1:])
+
+
+class ActCode(int):
+    """an activation code that carries the activation's run-time parameter (the slope of ACT_LEAKY): it compares and hashes as the
+    plain code, so ``act in (ACT_NONE, ACT_SILU)`` guards keep their meaning, and ``call_act`` routes it to the ``_p`` entry points"""
+
+    def __new__(cls, code: int, param: float):
+        o = super().__new__(cls, code)
+        o.param = float(param)
+        return o
+
+    def __repr__(self):
+        return f"ActCode({int(self)}, {self.param})"
+
+
+def act_key(act):
+    """(code, parameter) of an activation code: what two layers must share to run as one launch"""
+    return int(act), float(getattr(act, "param", 0.0))
+
 
 _lib = None
 
@@ -303,6 +336,16 @@ def launch_count() -> int:
     return _LAUNCHES[0]
 
 
+def call_act(name: str, *args):
+    """``call`` for a streaming BatchNorm entry point: an activation with a parameter (ActCode) goes to the ``_p`` sibling with the
+    parameter after the code; every other activation takes the entry point as named, with the arguments as given"""
+    k = BN_ACT_ARG[name]
+    act = args[k]
+    if isinstance(act, ActCode):
+        return call(name + "_p", *args[:k], int(act), act.param, *args[k + 1:])
+    return call(name, *args)
+
+
 def call(name: str, *args):
     """Call an int-returning entry point and raise on error."""
     _LAUNCHES[0] += 1
@@ -317,6 +360,11 @@ def call(name: str, *args):
     check(getattr(lib(), name)(*args), name)
     e1.record()
     g = None
+    if name.endswith("_p") and name[:-2] in BN_ACT_ARG:       # byte accounting of the sibling without its act_param
+        k = BN_ACT_ARG[name[:-2]] + 1
+        pname, name, args = name, name[:-2], args[:k] + args[k + 1:]
+    else:
+        pname = name
     if name in ("ydl_conv_fwd", "ydl_conv_fwd_sums", "ydl_conv_dgrad", "ydl_conv_dgrad_bnred", "ydl_conv_wgrad", "ydl_conv_wgrad_det",
                 "ydl_conv_bwd_pw", "ydl_conv_bwd_pw_bn"):
         src = args[0]._obj
@@ -358,4 +406,4 @@ def call(name: str, *args):
         g = float(es) * (N * H * W * C + N * Ho * Wo * (C + pts))
         if o:
             g += 4.0 * (N * H * W * C + N * Ho * Wo * pts)
-    _PROFILE.append((name, e0, e1, g))
+    _PROFILE.append((pname, e0, e1, g))

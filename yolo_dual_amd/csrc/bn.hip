@@ -183,29 +183,30 @@ extern "C" int ydl_bn_eval_coeffs(int C, const float* gamma, const float* beta, 
 #ifndef BN_APPLY_REVERSE
 #define BN_APPLY_REVERSE 1
 #endif
-struct Lay { int cpb, R, cq, pl; bool live; int c; };
-template <int V>
-__device__ __forceinline__ Lay make_lay(int Cp) {
-    Lay L;
-    const int cpp = Cp / V;
-    L.cpb = cpp < 256 ? cpp : 256;
-    L.R = 256 / L.cpb;
-    L.cq = threadIdx.x % L.cpb;
-    L.pl = threadIdx.x / L.cpb;
-    const int chunk = blockIdx.y * 256 + L.cq;
-    L.live = L.pl < L.R && chunk < cpp;
-    L.c = chunk * V;
-    return L;
-}
-static inline dim3 lay_grid(long long npix, int Cp, int V, int max_x) {
-    int cpp = Cp / V;
-    int cpb = cpp < 256 ? cpp : 256;
-    int R = 256 / cpb;
-    long long gx = (npix + R - 1) / R;
-    if (gx > max_x) gx = max_x;
-    if (gx < 1) gx = 1;
-    return dim3((unsigned)gx, (unsigned)((cpp + 255) / 256));
-}
+// the activation codes of the streaming kernels.  ap is the run-time parameter of the activation: the negative slope of
+// YDL_ACT_LEAKY (0 <= ap < 1), unused by every other code.  The entry points without an act_param pass 0 and refuse YDL_ACT_LEAKY.
+static inline bool act_known(int act) { return act >= YDL_ACT_NONE && act <= YDL_ACT_MISH; }
+static inline bool act_recomputes_z(int act) { return act == YDL_ACT_LEAKY || act == YDL_ACT_HSWISH || act == YDL_ACT_MISH; }
+#define YDL_ACT_CHECKS(act, ap)                                                                                      \
+    YDL_CHECK(act_known(act), "unknown activation");                                                                 \
+    YDL_CHECK(act != YDL_ACT_LEAKY || (ap >= 0.f && ap < 1.f), "YDL_ACT_LEAKY: the slope must lie in [0, 1)")
+#define YDL_NO_PARAM(act, name) YDL_CHECK(act != YDL_ACT_LEAKY, "YDL_ACT_LEAKY needs its slope: call " name "_p")
+// the backward recomputes z = y*scale + shift without the residual: SiLU's rule, see bn_dz_xhat_1
+#define YDL_ACT_BWD_CHECKS(act, ap, rmode)  \
+    YDL_ACT_CHECKS(act, ap);                \
+    YDL_CHECK(!(act_recomputes_z(act) && rmode == YDL_RES_BEFORE_ACT), "LeakyReLU / Hardswish / Mish backward: a residual joined before the activation is not served")
+// M(T, A) once, with A the compile-time activation code
+#define YDL_ACT_SWITCH(M, T)                                  \
+    do {                                                      \
+        switch (act) {                                        \
+            case YDL_ACT_SILU: M(T, YDL_ACT_SILU); break;     \
+            case YDL_ACT_RELU: M(T, YDL_ACT_RELU); break;     \
+            case YDL_ACT_LEAKY: M(T, YDL_ACT_LEAKY); break;   \
+            case YDL_ACT_HSWISH: M(T, YDL_ACT_HSWISH); break; \
+            case YDL_ACT_MISH: M(T, YDL_ACT_MISH); break;     \
+            default: M(T, YDL_ACT_NONE); break;               \
+        }                                                     \
+    } while (0)
 
 // apply: out = act(y*scale + shift) (+res).
 // scale/shift arrays must be readable up to Cp (padded entries = 0 => padded channels stay 0 for SiLU/none).
@@ -213,7 +214,7 @@ template <typename T, int ACT, int RES>
 __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ y, int ldy, const float* __restrict__ scale,
                                                          const float* __restrict__ shift, const T* __restrict__ res, int ldr,
                                                          T* __restrict__ out, int ldo,
-                                                         long long npix, int Cp) {
+                                                         long long npix, int Cp, float ap) {
     constexpr int V = ET<T>::V;
     const Lay L = make_lay<V>(Cp);
     if (!L.live) return;
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ y
         for (int e = 0; e < V; ++e) {
             float z = v[e] * sc[e] + sf[e];
             if (RES == YDL_RES_BEFORE_ACT) z += r[e];
-            float o = ACT == YDL_ACT_SILU ? silu_f(z) : (ACT == YDL_ACT_RELU ? fmaxf(z, 0.f) : z);
+            float o = act_f<ACT>(z, ap);
             if (RES == YDL_RES_AFTER_ACT) o += r[e];
             v[e] = o;
         }
@@ -237,9 +238,9 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ y
     }
 }
 
-extern "C" int ydl_bn_act_fwd(int dtype, const void* y, int ldy, const float* scale, const float* shift,
-                              const void* res, int ldr, int res_mode, int act, void* out, int ldo,
-                              int64_t npix, int Cp, void* stream) {
+static int bn_act_fwd_impl(int dtype, const void* y, int ldy, const float* scale, const float* shift,
+                           const void* res, int ldr, int res_mode, int act, float ap, void* out, int ldo,
+                           int64_t npix, int Cp, void* stream) {
     const int V = dtype == YDL_F32 ? 4 : 8;
     YDL_CHECK(y && out && scale && shift, "null pointer");
     YDL_CHECK(Cp > 0 && Cp % V == 0 && ldy >= Cp && ldo >= Cp, "Cp must be a chunk multiple covered by the strides");
@@ -247,27 +248,32 @@ extern "C" int ydl_bn_act_fwd(int dtype, const void* y, int ldy, const float* sc
     YDL_CHECK(aligned16(y) && aligned16(out) && (res == nullptr || aligned16(res)), "16-byte alignment");
     hipStream_t st = (hipStream_t)stream;
     dim3 grid = lay_grid(npix, Cp, V, 256 * 8);
-    YDL_CHECK(act == YDL_ACT_NONE || act == YDL_ACT_SILU || act == YDL_ACT_RELU, "unknown activation");
+    YDL_ACT_CHECKS(act, ap);
     YDL_CHECK(res_mode == YDL_RES_NONE || res_mode == YDL_RES_BEFORE_ACT || res_mode == YDL_RES_AFTER_ACT, "unknown residual mode");
     // activation and residual mode are compile-time: a run-time switch inside the unrolled element loop made the compiler emit a
     // scalar branch per element
-#define YDL_FWD_LAUNCH(T, A, R) bn_act_fwd_kernel<T, A, R><<<grid, 256, 0, st>>>((const T*)y, ldy, scale, shift, (const T*)res, ldr, (T*)out, ldo, npix, Cp)
+#define YDL_FWD_LAUNCH(T, A, R) bn_act_fwd_kernel<T, A, R><<<grid, 256, 0, st>>>((const T*)y, ldy, scale, shift, (const T*)res, ldr, (T*)out, ldo, npix, Cp, ap)
 #define YDL_FWD_RES(T, A)                                                                  \
     do {                                                                                   \
         if (res_mode == YDL_RES_NONE) YDL_FWD_LAUNCH(T, A, YDL_RES_NONE);                  \
         else if (res_mode == YDL_RES_BEFORE_ACT) YDL_FWD_LAUNCH(T, A, YDL_RES_BEFORE_ACT); \
         else YDL_FWD_LAUNCH(T, A, YDL_RES_AFTER_ACT);                                      \
     } while (0)
-#define YDL_FWD_ACT(T)                                                 \
-    do {                                                               \
-        if (act == YDL_ACT_SILU) YDL_FWD_RES(T, YDL_ACT_SILU);         \
-        else if (act == YDL_ACT_RELU) YDL_FWD_RES(T, YDL_ACT_RELU);    \
-        else YDL_FWD_RES(T, YDL_ACT_NONE);                             \
-    } while (0)
-    if (dtype == YDL_F32) YDL_FWD_ACT(float);
-    else YDL_FWD_ACT(bf16_t);
+    if (dtype == YDL_F32) YDL_ACT_SWITCH(YDL_FWD_RES, float);
+    else YDL_ACT_SWITCH(YDL_FWD_RES, bf16_t);
     YDL_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int ydl_bn_act_fwd(int dtype, const void* y, int ldy, const float* scale, const float* shift,
+                              const void* res, int ldr, int res_mode, int act, void* out, int ldo,
+                              int64_t npix, int Cp, void* stream) {
+    YDL_NO_PARAM(act, "ydl_bn_act_fwd");
+    return bn_act_fwd_impl(dtype, y, ldy, scale, shift, res, ldr, res_mode, act, 0.f, out, ldo, npix, Cp, stream);
+}
+extern "C" int ydl_bn_act_fwd_p(int dtype, const void* y, int ldy, const float* scale, const float* shift,
+                                const void* res, int ldr, int res_mode, int act, float act_param, void* out, int ldo,
+                                int64_t npix, int Cp, void* stream) {
+    return bn_act_fwd_impl(dtype, y, ldy, scale, shift, res, ldr, res_mode, act, act_param, out, ldo, npix, Cp, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -284,27 +290,27 @@ static inline int bwd_nblk(long long npix, int Cp, int V) {
 
 template <typename T, int ACT>
 __device__ __forceinline__ void dz_xhat_q(const uint4& yq, const uint4& dq, const uint4& oq, const float* sc, const float* sf,
-                                          const float* mu, const float* is, float* dz, float* xh) {
+                                          const float* mu, const float* is, float* dz, float* xh, float ap) {
     constexpr int V = ET<T>::V;
     float yv[V], dv[V], ov[V];
     unpack16<T>(yq, yv);
     unpack16<T>(dq, dv);
     if (ACT == YDL_ACT_RELU) unpack16<T>(oq, ov);
 #pragma unroll
-    for (int e = 0; e < V; ++e) bn_dz_xhat_1<ACT>(yv[e], dv[e], ACT == YDL_ACT_RELU ? ov[e] : 0.f, sc[e], sf[e], mu[e], is[e], dz[e], xh[e]);
+    for (int e = 0; e < V; ++e) bn_dz_xhat_1<ACT>(yv[e], dv[e], ACT == YDL_ACT_RELU ? ov[e] : 0.f, sc[e], sf[e], mu[e], is[e], dz[e], xh[e], ap);
 }
 
 template <typename T, int ACT>
 __device__ __forceinline__ void dz_xhat(const T* y, const T* dout, const T* out, long long pix, int ldy, int lddo, int ldo,
                                         int c, const float* sc, const float* sf, const float* mu, const float* is,
-                                        float* dz, float* xh, float* dv) {
+                                        float* dz, float* xh, float* dv, float ap) {
     constexpr int V = ET<T>::V;
     float yv[V], ov[V];
     unpack16<T>(*(const uint4*)(y + pix * ldy + c), yv);
     unpack16<T>(*(const uint4*)(dout + pix * lddo + c), dv);
     if (ACT == YDL_ACT_RELU) unpack16<T>(*(const uint4*)(out + pix * ldo + c), ov);
 #pragma unroll
-    for (int e = 0; e < V; ++e) bn_dz_xhat_1<ACT>(yv[e], dv[e], ACT == YDL_ACT_RELU ? ov[e] : 0.f, sc[e], sf[e], mu[e], is[e], dz[e], xh[e]);
+    for (int e = 0; e < V; ++e) bn_dz_xhat_1<ACT>(yv[e], dv[e], ACT == YDL_ACT_RELU ? ov[e] : 0.f, sc[e], sf[e], mu[e], is[e], dz[e], xh[e], ap);
 }
 
 template <typename T, int ACT>
@@ -312,7 +318,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
                                                             const T* __restrict__ out, int ldo,
                                                             const float* __restrict__ scale, const float* __restrict__ shift,
                                                             const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                            float* __restrict__ part, long long npix, int Cp) {
+                                                            float* __restrict__ part, long long npix, int Cp, float ap) {
     constexpr int V = ET<T>::V;
     const Lay L = make_lay<V>(Cp);
     float sb[V], sg[V], sc[V], sf[V], mu[V], is[V];
@@ -331,16 +337,16 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
             uint4 o0 = make_uint4(0, 0, 0, 0), o1 = o0;
             if (ACT == YDL_ACT_RELU) { o0 = *(const uint4*)(out + pix * ldo + L.c); o1 = *(const uint4*)(out + (pix + stride) * ldo + L.c); }
             float dz[V], xh[V];
-            dz_xhat_q<T, ACT>(y0, d0, o0, sc, sf, mu, is, dz, xh);
+            dz_xhat_q<T, ACT>(y0, d0, o0, sc, sf, mu, is, dz, xh, ap);
 #pragma unroll
             for (int e = 0; e < V; ++e) { sb[e] += dz[e]; sg[e] += dz[e] * xh[e]; }
-            dz_xhat_q<T, ACT>(y1, d1, o1, sc, sf, mu, is, dz, xh);
+            dz_xhat_q<T, ACT>(y1, d1, o1, sc, sf, mu, is, dz, xh, ap);
 #pragma unroll
             for (int e = 0; e < V; ++e) { sb[e] += dz[e]; sg[e] += dz[e] * xh[e]; }
         }
         for (; pix < npix; pix += stride) {
             float dz[V], xh[V], dvr[V];
-            dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dvr);
+            dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dvr, ap);
 #pragma unroll
             for (int e = 0; e < V; ++e) { sb[e] += dz[e]; sg[e] += dz[e] * xh[e]; }
         }
@@ -417,7 +423,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
                                                            const float* __restrict__ mean, const float* __restrict__ invstd,
                                                            const float* __restrict__ sums, T* __restrict__ dy, int lddy,
-                                                           T* __restrict__ dres, int lddr, int dres_acc, long long npix, int Cp) {
+                                                           T* __restrict__ dres, int lddr, int dres_acc, long long npix, int Cp,
+                                                           float ap) {
     constexpr int V = ET<T>::V;
     const Lay L = make_lay<V>(Cp);
     if (!L.live) return;
@@ -436,7 +443,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     for (long long pix = BN_APPLY_REVERSE ? plast : pfirst; BN_APPLY_REVERSE ? pix >= pfirst : pix < npix;
          pix += BN_APPLY_REVERSE ? -stride : stride) {
         float dz[V], xh[V], o[V], dv[V];
-        dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dv);
+        dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dv, ap);
 #pragma unroll
         for (int e = 0; e < V; ++e) o[e] = bn_bwd_dy_1(sc[e], dz[e], xh[e], kb[e], kg[e]);
         *(uint4*)(dy + pix * lddy + L.c) = pack16<T>(o);
@@ -461,11 +468,11 @@ extern "C" int64_t ydl_bn_bwd_ws_bytes(int64_t npix, int Cp) {
     return ((int64_t)BWD_MAX_PARTIALS * 2 * Cp + 2 * Cp) * (int64_t)sizeof(float);
 }
 
-extern "C" int ydl_bn_act_bwd(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
-                              const float* gamma, const float* mean, const float* invstd, const float* scale, const float* shift,
-                              int res_mode, int act, void* dy, int lddy, void* dres, int lddr,
-                              float* dgamma, float* dbeta, int accumulate_param_grads,
-                              float* ws, int64_t npix, int C, int Cp, void* stream) {
+static int bn_act_bwd_impl(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                           const float* gamma, const float* mean, const float* invstd, const float* scale, const float* shift,
+                           int res_mode, int act, float ap, void* dy, int lddy, void* dres, int lddr,
+                           float* dgamma, float* dbeta, int accumulate_param_grads,
+                           float* ws, int64_t npix, int C, int Cp, void* stream) {
     (void)gamma;
     const int dres_acc = (res_mode & YDL_RES_GRAD_ACCUMULATE) ? 1 : 0;
     const int rmode = res_mode & 15;
@@ -483,32 +490,43 @@ extern "C" int ydl_bn_act_bwd(int dtype, const void* y, int ldy, const void* dou
     float* part = ws;
     float* sums = ws + (size_t)BWD_MAX_PARTIALS * 2 * Cp;
     dim3 g3 = lay_grid(npix, Cp, V, 256 * 8);
-    YDL_CHECK(act == YDL_ACT_NONE || act == YDL_ACT_SILU || act == YDL_ACT_RELU, "unknown activation");
+    YDL_ACT_BWD_CHECKS(act, ap, rmode);
 #define YDL_BWD_LAUNCH(T, A)                                                                                                          \
     do {                                                                                                                              \
         bn_bwd_reduce_kernel<T, A><<<g1, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale, shift,     \
-                                                       mean, invstd, part, npix, Cp);                                                \
+                                                       mean, invstd, part, npix, Cp, ap);                                            \
         bn_bwd_merge_kernel<<<(Cp + 7) / 8, 256, 0, st>>>(part, nblk, Cp, C, sums, dgamma, dbeta, accumulate_param_grads);            \
         if (resm == 0)                                                                                                                \
             bn_bwd_apply_kernel<T, A, 0><<<g3, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale,      \
-                                                             shift, mean, invstd, sums, (T*)dy, lddy, (T*)dres, lddr, dres_acc, npix, Cp); \
+                                                             shift, mean, invstd, sums, (T*)dy, lddy, (T*)dres, lddr, dres_acc, npix, Cp, ap); \
         else if (resm == 1)                                                                                                           \
             bn_bwd_apply_kernel<T, A, 1><<<g3, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale,      \
-                                                             shift, mean, invstd, sums, (T*)dy, lddy, (T*)dres, lddr, dres_acc, npix, Cp); \
+                                                             shift, mean, invstd, sums, (T*)dy, lddy, (T*)dres, lddr, dres_acc, npix, Cp, ap); \
         else                                                                                                                          \
             bn_bwd_apply_kernel<T, A, 2><<<g3, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale,      \
-                                                             shift, mean, invstd, sums, (T*)dy, lddy, (T*)dres, lddr, dres_acc, npix, Cp); \
+                                                             shift, mean, invstd, sums, (T*)dy, lddy, (T*)dres, lddr, dres_acc, npix, Cp, ap); \
     } while (0)
-#define YDL_BWD_ACT(T)                                                                                                                \
-    do {                                                                                                                              \
-        if (act == YDL_ACT_SILU) YDL_BWD_LAUNCH(T, YDL_ACT_SILU);                                                                     \
-        else if (act == YDL_ACT_RELU) YDL_BWD_LAUNCH(T, YDL_ACT_RELU);                                                                \
-        else YDL_BWD_LAUNCH(T, YDL_ACT_NONE);                                                                                         \
-    } while (0)
-    if (dtype == YDL_F32) YDL_BWD_ACT(float);
-    else YDL_BWD_ACT(bf16_t);
+    if (dtype == YDL_F32) YDL_ACT_SWITCH(YDL_BWD_LAUNCH, float);
+    else YDL_ACT_SWITCH(YDL_BWD_LAUNCH, bf16_t);
     YDL_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int ydl_bn_act_bwd(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                              const float* gamma, const float* mean, const float* invstd, const float* scale, const float* shift,
+                              int res_mode, int act, void* dy, int lddy, void* dres, int lddr,
+                              float* dgamma, float* dbeta, int accumulate_param_grads,
+                              float* ws, int64_t npix, int C, int Cp, void* stream) {
+    YDL_NO_PARAM(act, "ydl_bn_act_bwd");
+    return bn_act_bwd_impl(dtype, y, ldy, dout, lddo, out, ldo, gamma, mean, invstd, scale, shift, res_mode, act, 0.f, dy, lddy, dres, lddr,
+                           dgamma, dbeta, accumulate_param_grads, ws, npix, C, Cp, stream);
+}
+extern "C" int ydl_bn_act_bwd_p(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                                const float* gamma, const float* mean, const float* invstd, const float* scale, const float* shift,
+                                int res_mode, int act, float act_param, void* dy, int lddy, void* dres, int lddr,
+                                float* dgamma, float* dbeta, int accumulate_param_grads,
+                                float* ws, int64_t npix, int C, int Cp, void* stream) {
+    return bn_act_bwd_impl(dtype, y, ldy, dout, lddo, out, ldo, gamma, mean, invstd, scale, shift, res_mode, act, act_param, dy, lddy, dres,
+                           lddr, dgamma, dbeta, accumulate_param_grads, ws, npix, C, Cp, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -525,7 +543,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_sums_kernel(const T* __restric
                                                               const float* __restrict__ beta, float eps, float momentum,
                                                               float* running_mean, float* running_var, float* mean_o, float* invstd_o,
                                                               float* scale_o, float* shift_o, int rep, const T* __restrict__ res, int ldr,
-                                                              T* __restrict__ out, int ldo, long long npix, int C, int Cp) {
+                                                              T* __restrict__ out, int ldo, long long npix, int C, int Cp, float ap) {
     constexpr int V = ET<T>::V;
     const Lay L = make_lay<V>(Cp);
     // coefficients of the CTA's channels: ONE channel per thread (replica rows summed in double), shared through LDS — deriving
@@ -599,7 +617,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_sums_kernel(const T* __restric
             for (int e = 0; e < V; ++e) {
                 float z = v[e] * sc[e] + sf[e];
                 if (RES == YDL_RES_BEFORE_ACT) z += r[e];
-                float o = ACT == YDL_ACT_SILU ? silu_f(z) : (ACT == YDL_ACT_RELU ? fmaxf(z, 0.f) : z);
+                float o = act_f<ACT>(z, ap);
                 if (RES == YDL_RES_AFTER_ACT) o += r[e];
                 v[e] = o;
             }
@@ -608,11 +626,11 @@ __global__ __launch_bounds__(256) void bn_act_fwd_sums_kernel(const T* __restric
     }
 }
 
-extern "C" int ydl_bn_act_fwd_sums(int dtype, const void* y, int ldy, const float* sums, int sums_ld, int64_t count,
-                                   const float* gamma, const float* beta, float eps, float momentum,
-                                   float* running_mean, float* running_var, float* mean, float* invstd, float* scale, float* shift,
-                                   int replication, const void* res, int ldr, int res_mode, int act, void* out, int ldo,
-                                   int64_t npix, int C, int Cp, void* stream) {
+static int bn_act_fwd_sums_impl(int dtype, const void* y, int ldy, const float* sums, int sums_ld, int64_t count,
+                                const float* gamma, const float* beta, float eps, float momentum,
+                                float* running_mean, float* running_var, float* mean, float* invstd, float* scale, float* shift,
+                                int replication, const void* res, int ldr, int res_mode, int act, float ap, void* out, int ldo,
+                                int64_t npix, int C, int Cp, void* stream) {
     const int V = dtype == YDL_F32 ? 4 : 8;
     YDL_CHECK(dtype == YDL_F32 || dtype == YDL_BF16, "bad dtype");
     YDL_CHECK(y && out && sums && mean && invstd && scale && shift, "null pointer");
@@ -621,7 +639,7 @@ extern "C" int ydl_bn_act_fwd_sums(int dtype, const void* y, int ldy, const floa
     YDL_CHECK((running_mean == nullptr) == (running_var == nullptr), "running_mean and running_var come together");
     YDL_CHECK(res_mode == YDL_RES_NONE || (res != nullptr && ldr >= Cp), "residual requested but missing");
     YDL_CHECK(aligned16(y) && aligned16(out) && aligned16(sums) && (res == nullptr || aligned16(res)), "16-byte alignment");
-    YDL_CHECK(act == YDL_ACT_NONE || act == YDL_ACT_SILU || act == YDL_ACT_RELU, "unknown activation");
+    YDL_ACT_CHECKS(act, ap);
     YDL_CHECK(res_mode == YDL_RES_NONE || res_mode == YDL_RES_BEFORE_ACT || res_mode == YDL_RES_AFTER_ACT, "unknown residual mode");
     hipStream_t st = (hipStream_t)stream;
     dim3 grid = lay_grid(npix, Cp, V, 256 * 8);
@@ -635,23 +653,34 @@ extern "C" int ydl_bn_act_fwd_sums(int dtype, const void* y, int ldy, const floa
 #define YDL_FS_LAUNCH(T, A, R)                                                                                                      \
     bn_act_fwd_sums_kernel<T, A, R><<<grid, 256, 0, st>>>((const T*)y, ldy, sums, sums_ld, (long long)count, gamma, beta, eps, momentum, \
                                                           running_mean, running_var, mean, invstd, scale, shift, replication,         \
-                                                          (const T*)res, ldr, (T*)out, ldo, npix, C, Cp)
+                                                          (const T*)res, ldr, (T*)out, ldo, npix, C, Cp, ap)
 #define YDL_FS_RES(T, A)                                                                  \
     do {                                                                                  \
         if (res_mode == YDL_RES_NONE) YDL_FS_LAUNCH(T, A, YDL_RES_NONE);                  \
         else if (res_mode == YDL_RES_BEFORE_ACT) YDL_FS_LAUNCH(T, A, YDL_RES_BEFORE_ACT); \
         else YDL_FS_LAUNCH(T, A, YDL_RES_AFTER_ACT);                                      \
     } while (0)
-#define YDL_FS_ACT(T)                                                 \
-    do {                                                              \
-        if (act == YDL_ACT_SILU) YDL_FS_RES(T, YDL_ACT_SILU);         \
-        else if (act == YDL_ACT_RELU) YDL_FS_RES(T, YDL_ACT_RELU);    \
-        else YDL_FS_RES(T, YDL_ACT_NONE);                             \
-    } while (0)
-    if (dtype == YDL_F32) YDL_FS_ACT(float);
-    else YDL_FS_ACT(bf16_t);
+    if (dtype == YDL_F32) YDL_ACT_SWITCH(YDL_FS_RES, float);
+    else YDL_ACT_SWITCH(YDL_FS_RES, bf16_t);
     YDL_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int ydl_bn_act_fwd_sums(int dtype, const void* y, int ldy, const float* sums, int sums_ld, int64_t count,
+                                   const float* gamma, const float* beta, float eps, float momentum,
+                                   float* running_mean, float* running_var, float* mean, float* invstd, float* scale, float* shift,
+                                   int replication, const void* res, int ldr, int res_mode, int act, void* out, int ldo,
+                                   int64_t npix, int C, int Cp, void* stream) {
+    YDL_NO_PARAM(act, "ydl_bn_act_fwd_sums");
+    return bn_act_fwd_sums_impl(dtype, y, ldy, sums, sums_ld, count, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd,
+                                scale, shift, replication, res, ldr, res_mode, act, 0.f, out, ldo, npix, C, Cp, stream);
+}
+extern "C" int ydl_bn_act_fwd_sums_p(int dtype, const void* y, int ldy, const float* sums, int sums_ld, int64_t count,
+                                     const float* gamma, const float* beta, float eps, float momentum,
+                                     float* running_mean, float* running_var, float* mean, float* invstd, float* scale, float* shift,
+                                     int replication, const void* res, int ldr, int res_mode, int act, float act_param, void* out,
+                                     int ldo, int64_t npix, int C, int Cp, void* stream) {
+    return bn_act_fwd_sums_impl(dtype, y, ldy, sums, sums_ld, count, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd,
+                                scale, shift, replication, res, ldr, res_mode, act, act_param, out, ldo, npix, C, Cp, stream);
 }
 
 // reduce pass: as bn_bwd_reduce_kernel, but the CTA's per-channel (sum dz, sum dz*xhat) are ADDED to replica (blockIdx.x & 7)
@@ -679,7 +708,7 @@ __device__ __forceinline__ void bn_bwd_reduce_sums_body(const T* __restrict__ y,
                                                         const float* __restrict__ scale, const float* __restrict__ shift,
                                                         const float* __restrict__ mean, const float* __restrict__ invstd,
                                                         float* __restrict__ sums, long long npix, int Cp,
-                                                        T* __restrict__ dres, int lddr, int dres_acc) {
+                                                        T* __restrict__ dres, int lddr, int dres_acc, float ap) {
     constexpr int V = ET<T>::V;
     const Lay L = make_lay<V>(Cp);
     float sb[V], sg[V], sc[V], sf[V], mu[V], is[V];
@@ -696,7 +725,7 @@ __device__ __forceinline__ void bn_bwd_reduce_sums_body(const T* __restrict__ y,
             uint4 o0 = make_uint4(0, 0, 0, 0), o1 = o0;
             if (ACT == YDL_ACT_RELU) { o0 = *(const uint4*)(out + pix * ldo + L.c); o1 = *(const uint4*)(out + (pix + stride) * ldo + L.c); }
             float dz[V], xh[V];
-            dz_xhat_q<T, ACT>(y0, d0, o0, sc, sf, mu, is, dz, xh);
+            dz_xhat_q<T, ACT>(y0, d0, o0, sc, sf, mu, is, dz, xh, ap);
 #pragma unroll
             for (int e = 0; e < V; ++e) { sb[e] += dz[e]; sg[e] += dz[e] * xh[e]; }
             if (RESM != 0) {
@@ -704,7 +733,7 @@ __device__ __forceinline__ void bn_bwd_reduce_sums_body(const T* __restrict__ y,
                 unpack16<T>(d0, dv);
                 bn_bwd_store_dres<T, RESM>(dres + pix * lddr + L.c, dv, dz, dres_acc);
             }
-            dz_xhat_q<T, ACT>(y1, d1, o1, sc, sf, mu, is, dz, xh);
+            dz_xhat_q<T, ACT>(y1, d1, o1, sc, sf, mu, is, dz, xh, ap);
 #pragma unroll
             for (int e = 0; e < V; ++e) { sb[e] += dz[e]; sg[e] += dz[e] * xh[e]; }
             if (RESM != 0) {
@@ -715,7 +744,7 @@ __device__ __forceinline__ void bn_bwd_reduce_sums_body(const T* __restrict__ y,
         }
         for (; pix < npix; pix += stride) {
             float dz[V], xh[V], dvr[V];
-            dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dvr);
+            dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dvr, ap);
 #pragma unroll
             for (int e = 0; e < V; ++e) { sb[e] += dz[e]; sg[e] += dz[e] * xh[e]; }
             if (RESM != 0) bn_bwd_store_dres<T, RESM>(dres + pix * lddr + L.c, dvr, dz, dres_acc);
@@ -782,8 +811,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_sums_kernel(const T* __rest
                                                                  const T* __restrict__ out, int ldo,
                                                                  const float* __restrict__ scale, const float* __restrict__ shift,
                                                                  const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                 float* __restrict__ sums, long long npix, int Cp) {
-    bn_bwd_reduce_sums_body<T, ACT, 0>(y, ldy, dout, lddo, out, ldo, scale, shift, mean, invstd, sums, npix, Cp, nullptr, 0, 0);
+                                                                 float* __restrict__ sums, long long npix, int Cp, float ap) {
+    bn_bwd_reduce_sums_body<T, ACT, 0>(y, ldy, dout, lddo, out, ldo, scale, shift, mean, invstd, sums, npix, Cp, nullptr, 0, 0, ap);
 }
 template <typename T, int ACT, int RESM>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_res_sums_kernel(const T* __restrict__ y, int ldy, const T* __restrict__ dout, int lddo,
@@ -791,8 +820,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_res_sums_kernel(const T* __
                                                                      const float* __restrict__ scale, const float* __restrict__ shift,
                                                                      const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                      float* __restrict__ sums, long long npix, int Cp,
-                                                                     T* __restrict__ dres, int lddr, int dres_acc) {
-    bn_bwd_reduce_sums_body<T, ACT, RESM>(y, ldy, dout, lddo, out, ldo, scale, shift, mean, invstd, sums, npix, Cp, dres, lddr, dres_acc);
+                                                                     T* __restrict__ dres, int lddr, int dres_acc, float ap) {
+    bn_bwd_reduce_sums_body<T, ACT, RESM>(y, ldy, dout, lddo, out, ldo, scale, shift, mean, invstd, sums, npix, Cp, dres, lddr, dres_acc,
+                                          ap);
 }
 
 template <typename T, int ACT, int RESM>
@@ -802,7 +832,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_sums_kernel(const T* __restr
                                                                 const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                 const float* __restrict__ sums, T* __restrict__ dy, int lddy,
                                                                 T* __restrict__ dres, int lddr, int dres_acc, float* dgamma, float* dbeta,
-                                                                int acc_param, long long npix, int C, int Cp) {
+                                                                int acc_param, long long npix, int C, int Cp, float ap) {
     constexpr int V = ET<T>::V;
     const Lay L = make_lay<V>(Cp);
     const float invM = 1.0f / (float)npix;
@@ -846,7 +876,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_sums_kernel(const T* __restr
     for (long long pix = BN_APPLY_REVERSE ? plast : pfirst; BN_APPLY_REVERSE ? pix >= pfirst : pix < npix;
          pix += BN_APPLY_REVERSE ? -stride : stride) {
         float dz[V], xh[V], o[V], dv[V];
-        dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dv);
+        dz_xhat<T, ACT>(y, dout, out, pix, ldy, lddo, ldo, L.c, sc, sf, mu, is, dz, xh, dv, ap);
 #pragma unroll
         for (int e = 0; e < V; ++e) o[e] = bn_bwd_dy_1(sc[e], dz[e], xh[e], kb[e], kg[e]);
         *(uint4*)(dy + pix * lddy + L.c) = pack16<T>(o);
@@ -872,7 +902,7 @@ static void bwd_sums_grids(int64_t npix, int Cp, int V, dim3& g1, dim3& g3) {
 
 static int bn_act_bwd_sums_impl(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
                                 const float* mean, const float* invstd, const float* scale, const float* shift,
-                                int res_mode, int act, void* dy, int lddy, void* dres, int lddr,
+                                int res_mode, int act, float ap, void* dy, int lddy, void* dres, int lddr,
                                 float* dgamma, float* dbeta, int accumulate_param_grads,
                                 float* sums, int64_t npix, int C, int Cp, void* stream, bool with_reduce) {
     const int dres_acc = (res_mode & YDL_RES_GRAD_ACCUMULATE) ? 1 : 0;
@@ -886,31 +916,25 @@ static int bn_act_bwd_sums_impl(int dtype, const void* y, int ldy, const void* d
     YDL_CHECK(act != YDL_ACT_RELU || out != nullptr, "RELU backward needs the saved output");
     YDL_CHECK(Cp > 0 && Cp % V == 0 && C <= Cp && ldy >= Cp && lddo >= Cp && lddy >= Cp, "bad channel geometry");
     YDL_CHECK(aligned16(y) && aligned16(dout) && aligned16(dy) && aligned16(sums), "16-byte alignment");
-    YDL_CHECK(act == YDL_ACT_NONE || act == YDL_ACT_SILU || act == YDL_ACT_RELU, "unknown activation");
+    YDL_ACT_BWD_CHECKS(act, ap, rmode);
     hipStream_t st = (hipStream_t)stream;
     dim3 g1, g3;
     bwd_sums_grids(npix, Cp, V, g1, g3);
 #define YDL_BS_APPLY(T, A, RM)                                                                                                     \
     bn_bwd_apply_sums_kernel<T, A, RM><<<g3, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale, shift, \
                                                            mean, invstd, sums, (T*)dy, lddy, (T*)dres, lddr, dres_acc, dgamma, dbeta, \
-                                                           accumulate_param_grads, npix, C, Cp)
+                                                           accumulate_param_grads, npix, C, Cp, ap)
 #define YDL_BS_LAUNCH(T, A)                                                                                                        \
     do {                                                                                                                           \
         if (with_reduce)                                                                                                           \
             bn_bwd_reduce_sums_kernel<T, A><<<g1, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale, \
-                                                                shift, mean, invstd, sums, npix, Cp);                              \
+                                                                shift, mean, invstd, sums, npix, Cp, ap);                          \
         if (resm == 0) YDL_BS_APPLY(T, A, 0);                                                                                      \
         else if (resm == 1) YDL_BS_APPLY(T, A, 1);                                                                                 \
         else YDL_BS_APPLY(T, A, 2);                                                                                                \
     } while (0)
-#define YDL_BS_ACT(T)                                                   \
-    do {                                                                \
-        if (act == YDL_ACT_SILU) YDL_BS_LAUNCH(T, YDL_ACT_SILU);        \
-        else if (act == YDL_ACT_RELU) YDL_BS_LAUNCH(T, YDL_ACT_RELU);   \
-        else YDL_BS_LAUNCH(T, YDL_ACT_NONE);                            \
-    } while (0)
-    if (dtype == YDL_F32) YDL_BS_ACT(float);
-    else YDL_BS_ACT(bf16_t);
+    if (dtype == YDL_F32) YDL_ACT_SWITCH(YDL_BS_LAUNCH, float);
+    else YDL_ACT_SWITCH(YDL_BS_LAUNCH, bf16_t);
     YDL_LAUNCH_CHECK();
     return 0;
 }
@@ -920,25 +944,43 @@ extern "C" int ydl_bn_act_bwd_sums(int dtype, const void* y, int ldy, const void
                                    int res_mode, int act, void* dy, int lddy, void* dres, int lddr,
                                    float* dgamma, float* dbeta, int accumulate_param_grads,
                                    float* sums, int64_t npix, int C, int Cp, void* stream) {
-    return bn_act_bwd_sums_impl(dtype, y, ldy, dout, lddo, out, ldo, mean, invstd, scale, shift, res_mode, act, dy, lddy, dres, lddr,
+    YDL_NO_PARAM(act, "ydl_bn_act_bwd_sums");
+    return bn_act_bwd_sums_impl(dtype, y, ldy, dout, lddo, out, ldo, mean, invstd, scale, shift, res_mode, act, 0.f, dy, lddy, dres, lddr,
                                 dgamma, dbeta, accumulate_param_grads, sums, npix, C, Cp, stream, true);
+}
+extern "C" int ydl_bn_act_bwd_sums_p(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                                     const float* mean, const float* invstd, const float* scale, const float* shift,
+                                     int res_mode, int act, float act_param, void* dy, int lddy, void* dres, int lddr,
+                                     float* dgamma, float* dbeta, int accumulate_param_grads,
+                                     float* sums, int64_t npix, int C, int Cp, void* stream) {
+    return bn_act_bwd_sums_impl(dtype, y, ldy, dout, lddo, out, ldo, mean, invstd, scale, shift, res_mode, act, act_param, dy, lddy, dres,
+                                lddr, dgamma, dbeta, accumulate_param_grads, sums, npix, C, Cp, stream, true);
 }
 extern "C" int ydl_bn_act_bwd_apply_sums(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
                                          const float* mean, const float* invstd, const float* scale, const float* shift,
                                          int res_mode, int act, void* dy, int lddy, void* dres, int lddr,
                                          float* dgamma, float* dbeta, int accumulate_param_grads,
                                          float* sums, int64_t npix, int C, int Cp, void* stream) {
-    return bn_act_bwd_sums_impl(dtype, y, ldy, dout, lddo, out, ldo, mean, invstd, scale, shift, res_mode, act, dy, lddy, dres, lddr,
+    YDL_NO_PARAM(act, "ydl_bn_act_bwd_apply_sums");
+    return bn_act_bwd_sums_impl(dtype, y, ldy, dout, lddo, out, ldo, mean, invstd, scale, shift, res_mode, act, 0.f, dy, lddy, dres, lddr,
                                 dgamma, dbeta, accumulate_param_grads, sums, npix, C, Cp, stream, false);
+}
+extern "C" int ydl_bn_act_bwd_apply_sums_p(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                                           const float* mean, const float* invstd, const float* scale, const float* shift,
+                                           int res_mode, int act, float act_param, void* dy, int lddy, void* dres, int lddr,
+                                           float* dgamma, float* dbeta, int accumulate_param_grads,
+                                           float* sums, int64_t npix, int C, int Cp, void* stream) {
+    return bn_act_bwd_sums_impl(dtype, y, ldy, dout, lddo, out, ldo, mean, invstd, scale, shift, res_mode, act, act_param, dy, lddy, dres,
+                                lddr, dgamma, dbeta, accumulate_param_grads, sums, npix, C, Cp, stream, false);
 }
 
 // The reduce pass alone, for a layer whose dy is formed by the kernel that consumes it (ydl_conv_bwd_pw_bn): (sum dz, sum dz * xhat)
 // are ADDED to the zeroed replica slab, and the gradient of a residual operand, which the apply launch would have written, is
 // written here.  dgamma / dbeta are NOT written: the sums are complete only when this kernel has ended, the consumer finishes them.
-extern "C" int ydl_bn_act_bwd_reduce_sums(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
-                                          const float* mean, const float* invstd, const float* scale, const float* shift,
-                                          int res_mode, int act, void* dres, int lddr, float* sums, int64_t npix, int C, int Cp,
-                                          void* stream) {
+static int bn_act_bwd_reduce_sums_impl(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                                       const float* mean, const float* invstd, const float* scale, const float* shift,
+                                       int res_mode, int act, float ap, void* dres, int lddr, float* sums, int64_t npix, int C, int Cp,
+                                       void* stream) {
     const int dres_acc = (res_mode & YDL_RES_GRAD_ACCUMULATE) ? 1 : 0;
     const int rmode = res_mode & 15;
     YDL_CHECK(dtype == YDL_F32 || dtype == YDL_BF16, "bad dtype");
@@ -951,29 +993,38 @@ extern "C" int ydl_bn_act_bwd_reduce_sums(int dtype, const void* y, int ldy, con
     YDL_CHECK(act != YDL_ACT_RELU || out != nullptr, "RELU backward needs the saved output");
     YDL_CHECK(npix > 0 && Cp > 0 && Cp % V == 0 && C <= Cp && ldy >= Cp && lddo >= Cp, "bad channel geometry");
     YDL_CHECK(aligned16(y) && aligned16(dout) && aligned16(sums), "16-byte alignment");
-    YDL_CHECK(act == YDL_ACT_NONE || act == YDL_ACT_SILU || act == YDL_ACT_RELU, "unknown activation");
+    YDL_ACT_BWD_CHECKS(act, ap, rmode);
     hipStream_t st = (hipStream_t)stream;
     dim3 g1, g3;
     bwd_sums_grids(npix, Cp, V, g1, g3);
 #define YDL_BR_RES(T, A, RM)                                                                                                            \
     bn_bwd_reduce_res_sums_kernel<T, A, RM><<<g1, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale, shift, \
-                                                                mean, invstd, sums, npix, Cp, (T*)dres, lddr, dres_acc)
+                                                                mean, invstd, sums, npix, Cp, (T*)dres, lddr, dres_acc, ap)
 #define YDL_BR_LAUNCH(T, A)                                                                                                        \
     do {                                                                                                                           \
         if (resm == 0)                                                                                                             \
             bn_bwd_reduce_sums_kernel<T, A><<<g1, 256, 0, st>>>((const T*)y, ldy, (const T*)dout, lddo, (const T*)out, ldo, scale, \
-                                                                shift, mean, invstd, sums, npix, Cp);                              \
+                                                                shift, mean, invstd, sums, npix, Cp, ap);                          \
         else if (resm == 1) YDL_BR_RES(T, A, 1);                                                                                   \
         else YDL_BR_RES(T, A, 2);                                                                                                  \
     } while (0)
-#define YDL_BR_ACT(T)                                                   \
-    do {                                                                \
-        if (act == YDL_ACT_SILU) YDL_BR_LAUNCH(T, YDL_ACT_SILU);        \
-        else if (act == YDL_ACT_RELU) YDL_BR_LAUNCH(T, YDL_ACT_RELU);   \
-        else YDL_BR_LAUNCH(T, YDL_ACT_NONE);                            \
-    } while (0)
-    if (dtype == YDL_F32) YDL_BR_ACT(float);
-    else YDL_BR_ACT(bf16_t);
+    if (dtype == YDL_F32) YDL_ACT_SWITCH(YDL_BR_LAUNCH, float);
+    else YDL_ACT_SWITCH(YDL_BR_LAUNCH, bf16_t);
     YDL_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int ydl_bn_act_bwd_reduce_sums(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                                          const float* mean, const float* invstd, const float* scale, const float* shift,
+                                          int res_mode, int act, void* dres, int lddr, float* sums, int64_t npix, int C, int Cp,
+                                          void* stream) {
+    YDL_NO_PARAM(act, "ydl_bn_act_bwd_reduce_sums");
+    return bn_act_bwd_reduce_sums_impl(dtype, y, ldy, dout, lddo, out, ldo, mean, invstd, scale, shift, res_mode, act, 0.f, dres, lddr, sums,
+                                       npix, C, Cp, stream);
+}
+extern "C" int ydl_bn_act_bwd_reduce_sums_p(int dtype, const void* y, int ldy, const void* dout, int lddo, const void* out, int ldo,
+                                            const float* mean, const float* invstd, const float* scale, const float* shift,
+                                            int res_mode, int act, float act_param, void* dres, int lddr, float* sums, int64_t npix,
+                                            int C, int Cp, void* stream) {
+    return bn_act_bwd_reduce_sums_impl(dtype, y, ldy, dout, lddo, out, ldo, mean, invstd, scale, shift, res_mode, act, act_param, dres, lddr,
+                                       sums, npix, C, Cp, stream);
 }

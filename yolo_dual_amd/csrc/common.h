@@ -67,19 +67,54 @@ __device__ __forceinline__ float sigmoid_f(float z) {
 #endif
 }
 __device__ __forceinline__ float silu_f(float z) { return z * sigmoid_f(z); }
+// Mish = z * tanh(softplus(z)).  With w = exp(min(z, 20)) and n = w * (w + 2), tanh(softplus(z)) = n / (n + 2): no cancellation for
+// negative z (n -> 0 gives t -> 0), and beyond z = 20 the quotient is 1 to f32 precision.  d t / d z = 4 w (w + 1) / (n + 2)^2
+// (= sigmoid(z) * 4 (n + 1) / (n + 2)^2, since n + 1 = (w + 1)^2): one v_exp_f32 and one v_rcp_f32 serve value and derivative.
+__device__ __forceinline__ void mish_parts(float z, float& t, float& dt) {
+    const float w = __builtin_amdgcn_exp2f(1.4426950408889634f * fminf(z, 20.f));
+    const float n = w * (w + 2.f);
+    const float r = __builtin_amdgcn_rcpf(n + 2.f);
+    t = n * r;
+    dt = 4.f * (w * r) * ((w + 1.f) * r);
+}
+// the activation of the streaming BatchNorm kernels (ap: the negative slope of YDL_ACT_LEAKY, unused otherwise)
+template <int ACT>
+__device__ __forceinline__ float act_f(float z, float ap) {
+    if (ACT == YDL_ACT_SILU) return silu_f(z);
+    if (ACT == YDL_ACT_RELU) return fmaxf(z, 0.f);
+    if (ACT == YDL_ACT_LEAKY) return z > 0.f ? z : ap * z;
+    if (ACT == YDL_ACT_HSWISH) return z * fminf(fmaxf(z + 3.f, 0.f), 6.f) * (1.f / 6.f);
+    if (ACT == YDL_ACT_MISH) {
+        float t, dt;
+        mish_parts(z, t, dt);
+        return z * t;
+    }
+    return z;
+}
 
 // BatchNorm backward of ONE element, the only definition of its arithmetic (the streaming kernels of bn.hip and the convolution
 // backward kernels that form dy on the way in, wgrad.hip: pwbw_kernel<S, ACC, BN>, must agree to the bit):
 //   dz = dout * act'(y*scale + shift),  xhat = (y - mean) * invstd      (ov: the stored output, read for the ReLU mask only)
 //   dy = scale * (dz - kb - xhat * kg)  with kb = sum(dz) / M, kg = sum(dz * xhat) / M
+// LeakyReLU (slope ap), Hardswish and Mish recompute z as SiLU does: they need no stored output, and a residual may be joined after
+// the activation only.
 template <int ACT>
-__device__ __forceinline__ void bn_dz_xhat_1(float yv, float d, float ov, float sc, float sf, float mu, float is, float& dz, float& xh) {
+__device__ __forceinline__ void bn_dz_xhat_1(float yv, float d, float ov, float sc, float sf, float mu, float is, float& dz, float& xh,
+                                             float ap = 0.f) {
     float z = yv * sc + sf;
     if (ACT == YDL_ACT_SILU) {
         float sg = sigmoid_f(z);
         d *= sg * (1.f + z * (1.f - sg));
     } else if (ACT == YDL_ACT_RELU) {
         d = ov > 0.f ? d : 0.f;
+    } else if (ACT == YDL_ACT_LEAKY) {
+        d *= z > 0.f ? 1.f : ap;
+    } else if (ACT == YDL_ACT_HSWISH) {
+        d *= z < -3.f ? 0.f : (z > 3.f ? 1.f : (2.f * z + 3.f) * (1.f / 6.f));
+    } else if (ACT == YDL_ACT_MISH) {
+        float t, dt;
+        mish_parts(z, t, dt);
+        d *= t + z * dt;
     }
     dz = d;
     xh = (yv - mu) * is;
@@ -99,6 +134,33 @@ __device__ __forceinline__ uint4 bn_bwd_dy_bf16x8(const uint4& yq, const uint4& 
         o[e] = bn_bwd_dy_1(sc[e], dz, xh, kb[e], kg[e]);
     }
     return pack16<bf16_t>(o);
+}
+
+// Lane layout of the streaming kernels (bn.hip, act.hip): a thread owns ONE 16-byte channel chunk for the whole kernel and walks
+// pixels; a CTA of 256 threads covers R = 256/cpb pixels per iteration, cpb = min(chunks per pixel, 256); blockIdx.y counts blocks of
+// 256 chunks.
+struct Lay { int cpb, R, cq, pl; bool live; int c; };
+template <int V>
+__device__ __forceinline__ Lay make_lay(int Cp) {
+    Lay L;
+    const int cpp = Cp / V;
+    L.cpb = cpp < 256 ? cpp : 256;
+    L.R = 256 / L.cpb;
+    L.cq = threadIdx.x % L.cpb;
+    L.pl = threadIdx.x / L.cpb;
+    const int chunk = blockIdx.y * 256 + L.cq;
+    L.live = L.pl < L.R && chunk < cpp;
+    L.c = chunk * V;
+    return L;
+}
+static inline dim3 lay_grid(long long npix, int Cp, int V, int max_x) {
+    int cpp = Cp / V;
+    int cpb = cpp < 256 ? cpp : 256;
+    int R = 256 / cpb;
+    long long gx = (npix + R - 1) / R;
+    if (gx > max_x) gx = max_x;
+    if (gx < 1) gx = 1;
+    return dim3((unsigned)gx, (unsigned)((cpp + 255) / 256));
 }
 
 // Sum over the 64 lanes with DPP row shifts + row broadcasts (six v_add_f32_dpp, no LDS crossbar): the total is valid in LANE 63 ONLY.

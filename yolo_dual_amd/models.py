@@ -13,9 +13,12 @@ autograd node; parameter names/shapes match the reference so ``state_dict``s int
 """
 from __future__ import annotations
 
+import ast
 import logging
 import math
 import os
+import re
+from contextlib import contextmanager
 from copy import deepcopy
 from typing import Dict, List, Optional, Sequence
 
@@ -532,7 +535,77 @@ _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": 
                 "SPPCSPC_group": SPPCSPC_group, "SimCSPSPPF": SimCSPSPPF, "CrossConv": CrossConv, "C3x": C3x}
 
 
+# the activations a yaml can name: ``nn.Name(...)`` is torch's class, a bare ``Name(...)`` the class of yolo_dual_amd.activations where
+# there is one.  AconC and FReLU need a channel count and are given through the constructor only: Conv(c1, c2, k, s, act=AconC(c2)).
+_ACT_FORM = re.compile(r"^\s*(nn\.)?([A-Za-z_]\w*)\s*\((.*)\)\s*$", re.S)
+_ACT_TORCH = {"SiLU": nn.SiLU, "ReLU": nn.ReLU, "Identity": nn.Identity, "LeakyReLU": nn.LeakyReLU, "Hardswish": nn.Hardswish,
+              "Mish": nn.Mish}
+
+
+def resolve_activation(spec):
+    """the module a yaml's ``activation:`` key (models/yolo.py:302-305) or a string in a row's argument list names.  The reference
+    evaluates the string; here it is parsed: ``nn.Name(args)`` or ``Name(args)`` for the parameter-free activations, the arguments
+    numeric literals.  Anything else raises NotImplementedError naming ``activation``."""
+    from . import activations as A
+    from .modules import _act_code
+    if isinstance(spec, nn.Module):
+        _act_code(spec)
+        return spec
+    bad = NotImplementedError(f"activation: {spec!r} is not served: write nn.Name(...) or Name(...) with Name one of "
+                              f"{', '.join(sorted(_ACT_TORCH))}, MemoryEfficientMish and numeric literal arguments "
+                              "(AconC and FReLU take a channel count: pass them to the Conv constructor)")
+    m = _ACT_FORM.match(spec) if isinstance(spec, str) else None
+    if m is None:
+        raise bad
+    name = m.group(2)
+    if name == "MetaAconC":
+        raise NotImplementedError("activation: MetaAconC is not implemented on the HIP path")
+    cls = _ACT_TORCH.get(name)
+    if m.group(1) is None and name in ("SiLU", "Hardswish", "Mish", "MemoryEfficientMish"):
+        cls = getattr(A, name)
+    if cls is None:
+        raise bad
+    args = []
+    for a in (m.group(3).split(",") if m.group(3).strip() else []):
+        try:
+            v = ast.literal_eval(a.strip())
+        except (ValueError, SyntaxError):
+            raise bad from None
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise bad
+        args.append(v)
+    try:
+        mod = cls(*args)
+    except TypeError:
+        raise bad from None
+    _act_code(mod)                # refuses what the kernels do not serve (a LeakyReLU slope outside [0, 1))
+    return mod
+
+
+@contextmanager
+def default_activation(act):
+    """``Conv.default_act`` set to ``act`` (a module or a yaml string) for the duration of one model build, then restored: the
+    reference leaves the class attribute changed for every later model (models/yolo.py:304), this path does not"""
+    mod = resolve_activation(act)
+    old = Conv.default_act
+    Conv.default_act = mod
+    try:
+        yield mod
+    finally:
+        Conv.default_act = old
+
+
 def parse_model(d: dict, ch: List[int], deformable: bool = False):
+    """``_parse_model`` under the yaml's ``activation:`` key, if it has one"""
+    act = d.get("activation")
+    if act is None:
+        return _parse_model(d, ch, deformable)
+    with default_activation(act) as mod:
+        LOGGER.info("activation: %s", mod)
+        return _parse_model(d, ch, deformable)
+
+
+def _parse_model(d: dict, ch: List[int], deformable: bool = False):
     """models/yolo.py:299-382 for the block set of this path: resolves module names, applies depth/width gains
     (``n = max(round(n*gd), 1)``, ``c2 = make_divisible(c2*gw, 8)``), inserts ``n`` for C3 and C3TR (AttentionConv / AttentionStem and the SPP pyramid rows, C3SPP included, get none:
     n > 1 is a Sequential of identical constructions, models/yolo.py:318-329,369), and tags every layer
@@ -554,7 +627,8 @@ def parse_model(d: dict, ch: List[int], deformable: bool = False):
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)
-            args = [c1, c2, *args[1:]]
+            # a string argument that has the form of a call is an activation (the reference evaluates string arguments)
+            args = [c1, c2, *(resolve_activation(a) if isinstance(a, str) and _ACT_FORM.match(a) else a for a in args[1:])]
             if cls in (C3Common, C3_DCNV3, C3_DCNCommon, C3Ghost, C3TR, C3x):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
                 args.insert(2, n)
                 n = 1

@@ -358,13 +358,38 @@ class _BNHolder(nn.BatchNorm2d):
 
 
 def _act_code(act) -> int:
-    if act is True or isinstance(act, nn.SiLU):
+    """the activation of a Conv as the code the tape carries: a YDL_ACT_* code of the streaming BatchNorm kernels (LeakyReLU as an
+    ``ActCode`` that holds its slope), or ACT_ACON / ACT_FRELU for the two layers that run behind an ACT_NONE Conv.  Matched by type."""
+    from . import activations as A
+    if act is True or isinstance(act, (nn.SiLU, A.SiLU)):
         return L.ACT_SILU
     if act is False or act is None or isinstance(act, nn.Identity):
         return L.ACT_NONE
     if isinstance(act, nn.ReLU):
         return L.ACT_RELU
+    if isinstance(act, nn.LeakyReLU):
+        slope = float(act.negative_slope)
+        if not 0.0 <= slope < 1.0:
+            raise NotImplementedError(f"activation {act!r}: the HIP path serves LeakyReLU slopes 0 <= negative_slope < 1")
+        return L.ActCode(L.ACT_LEAKY, slope)
+    if isinstance(act, (nn.Hardswish, A.Hardswish)):
+        return L.ACT_HSWISH
+    if isinstance(act, (nn.Mish, A.Mish)):
+        return L.ACT_MISH
+    if isinstance(act, A.AconC):
+        return L.ACT_ACON
+    if isinstance(act, A.FReLU):
+        return L.ACT_FRELU
+    if isinstance(act, A.MetaAconC):
+        raise NotImplementedError("activation MetaAconC is not implemented on the HIP path (AconC is: its beta is a parameter)")
     raise NotImplementedError(f"activation {act!r} is not supported by the HIP path (SiLU/ReLU/Identity)")
+
+
+def _pointwise_act_code(act, who: str) -> int:
+    code = _act_code(act)
+    if code in (L.ACT_ACON, L.ACT_FRELU):
+        raise NotImplementedError(f"{who}: the default activation {act!r} is not point-wise; {who} serves the point-wise activations only")
+    return code
 
 
 def _cross_args(c1, c2, k, s, p, g, d):
@@ -416,7 +441,9 @@ def _cross_args(c1, c2, k, s, p, g, d):
 class Conv(_GemmWeights, YdlModule):
     """``Conv(c1, c2, k=1, s=1, p=None, g=1, act=True)`` (seg scripts) and
     ``Conv(c1, c2, k=1, s=1, p=None, g=1, d=1, act=True)`` (models/common.py): the 7th positional argument is taken
-    as ``act`` when it is a bool/Module and as the dilation when it is an int > 0 that is not a bool."""
+    as ``act`` when it is a bool/Module and as the dilation when it is an int > 0 that is not a bool.  ``act=True`` takes the class
+    attribute ``default_act`` (models/common.py:49,55), which ``models.default_activation`` sets for the duration of one build."""
+    default_act = nn.SiLU()
 
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d_or_act=True, act=None):
         super().__init__()
@@ -459,7 +486,13 @@ class Conv(_GemmWeights, YdlModule):
             self.conv = nn.Conv2d(c1, c2, k, s, self.p, groups=g, dilation=d, bias=False)
         self.conv.weight.data = self.conv.weight.data.contiguous(memory_format=torch.channels_last)
         self.bn = _BNHolder(c2)
-        self.act = nn.SiLU() if act is True else (act if isinstance(act, nn.Module) else nn.Identity())
+        if act is True:
+            dflt = type(self).default_act
+            if not type(dflt) is nn.SiLU:
+                _pointwise_act_code(dflt, "Conv.default_act")       # a layer with parameters cannot be shared by every Conv
+            self.act = nn.SiLU() if type(dflt) is nn.SiLU else dflt
+        else:
+            self.act = act if isinstance(act, nn.Module) else nn.Identity()
         self.act_code = _act_code(self.act)
         self._wcache = {}
         if d > 1:                     # column form (Tape.dilated_conv): the KRSC master seen as the [c2][9*c1] weight of a 1x1 GEMM
@@ -521,6 +554,14 @@ class Conv(_GemmWeights, YdlModule):
     def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None, res: Optional[Var] = None,
              res_mode: int = L.RES_NONE, act_code: Optional[int] = None) -> Var:
         act = self.act_code if act_code is None else act_code
+        if act in (L.ACT_ACON, L.ACT_FRELU):
+            # the Conv materialises its BatchNorm output, the layer's own kernels follow; a shortcut is joined behind them
+            if res is not None and res_mode != L.RES_AFTER_ACT:
+                raise NotImplementedError(f"{type(self.act).__name__}: a residual joined before the activation is not served")
+            z = self._fwd(tape, x, act_code=L.ACT_NONE)
+            if res is None:
+                return self.act._apply_var(tape, z, out=out)
+            return tape.add(self.act._apply_var(tape, z), res, out=out)
         if self.d > 1:
             return tape.dilated_conv(x, self.conv, self._gemm, self.d, act, out=out, res=res, res_mode=res_mode)
         self.mark_step(tape)
@@ -657,7 +698,9 @@ class _FusedPair(_GemmWeights):
 
     @classmethod
     def make(cls, a: "Conv", b: "Conv") -> Optional["_FusedPair"]:
-        if (a.k, a.s, a.p, a.c1, a.act_code) != (b.k, b.s, b.p, b.c1, b.act_code) or a.k != 1:
+        if (a.k, a.s, a.p, a.c1, L.act_key(a.act_code)) != (b.k, b.s, b.p, b.c1, L.act_key(b.act_code)) or a.k != 1:
+            return None
+        if a.act_code in (L.ACT_ACON, L.ACT_FRELU):      # each half has its own activation parameters behind the BatchNorm
             return None
         if a.c2 % 8 or b.c2 % 8:
             return None
@@ -1160,7 +1203,9 @@ class DCNv2(YdlModule):
         self.conv_offset_mask = _BiasConv2d(in_channels, deformable_groups * 3 * kernel_size * kernel_size, kernel_size, stride,
                                             padding, bias=True)
         self.bn = _BNHolder(out_channels)
-        self.act = nn.SiLU()
+        dflt = Conv.default_act                  # models/common.py:1659: DCNv2 follows Conv's default activation
+        self.act = nn.SiLU() if type(dflt) is nn.SiLU else dflt
+        self.act_code = _pointwise_act_code(self.act, "DCNv2")
         self.reset_parameters()
         self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
         self.__dict__["_gemm"] = _DeformGemm(self, self.bn)
@@ -1176,7 +1221,7 @@ class DCNv2(YdlModule):
     def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None, res: Optional[Var] = None, res_mode: int = L.RES_NONE) -> Var:
         GK = self.deformable_groups * self.kernel_size[0] * self.kernel_size[1]
         om = tape.conv_bias(x, self.conv_offset_mask)
-        return tape.deform_conv(x, om.slice(0, 2 * GK), om.slice(2 * GK, 3 * GK), self, self._gemm, L.ACT_SILU, mask_sigmoid=True,
+        return tape.deform_conv(x, om.slice(0, 2 * GK), om.slice(2 * GK, 3 * GK), self, self._gemm, self.act_code, mask_sigmoid=True,
                                 out=out, res=res, res_mode=res_mode)
 
 

@@ -687,13 +687,13 @@ class Tape:
             cp = round_up(cw, 8)
             if sums is not None:
                 # statistics, coefficients (kept for the backward) and running statistics of this channel group in the apply launch
-                L.call("ydl_bn_act_fwd_sums", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(sums[co:]), Cout_p, npix,
+                L.call_act("ydl_bn_act_fwd_sums", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(sums[co:]), Cout_p, npix,
                        _p(m.bn.weight[co:]), _p(m.bn.bias[co:]), m.bn.eps, m.bn.momentum, _p(m.bn.running_mean[co:]),
                        _p(m.bn.running_var[co:]), _p(cf["mean"][co:]), _p(cf["invstd"][co:]), _p(cf["scale"][co:]), _p(cf["shift"][co:]),
                        rep, _p(res.t) if res is not None else None, res.ld if res is not None else 0, res_mode, act,
                        _p(o.t), o.ld, npix, cw, cp, st)
                 continue
-            L.call("ydl_bn_act_fwd", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld,
+            L.call_act("ydl_bn_act_fwd", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld,
                    _p(cf["scale"][co:]), _p(cf["shift"][co:]),
                    _p(res.t) if res is not None else None, res.ld if res is not None else 0, res_mode, act,
                    _p(o.t), o.ld, npix, cp, st)
@@ -738,7 +738,7 @@ class Tape:
                     dout = self._gbuf(o)
                     dres_t, dres_ld, rmode = self._res_grad(res, res_mode, o, dout)
                     sums_b = self.zeroed(L.BN_REPLICAS * 2 * cw)
-                    L.call("ydl_bn_act_bwd_reduce_sums", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(dout), o.ld,
+                    L.call_act("ydl_bn_act_bwd_reduce_sums", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(dout), o.ld,
                            _p(o.t), o.ld, _p(cf["mean"][co:]), _p(cf["invstd"][co:]), _p(cf["scale"][co:]), _p(cf["shift"][co:]),
                            rmode, act, _p(dres_t), dres_ld, _p(sums_b), npix, cw, cw, st2)
                     seg.append((dout, o.ld, sums_b))
@@ -769,14 +769,14 @@ class Tape:
                         entry, sums_b = "ydl_bn_act_bwd_apply_sums", red[0]
                     else:
                         entry, sums_b = "ydl_bn_act_bwd_sums", self.zeroed(L.BN_REPLICAS * 2 * cp)
-                    L.call(entry, self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(dout), o.ld,
+                    L.call_act(entry, self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(dout), o.ld,
                            _p(o.t), o.ld, _p(cf["mean"][co:]), _p(cf["invstd"][co:]), _p(cf["scale"][co:]), _p(cf["shift"][co:]),
                            rmode, act, _p(dyv), dy.ld, _p(dres_t), dres_ld, _p(gw[co:]), _p(gb[co:]), accw,
                            _p(sums_b), npix, cw, cp, st2)
                     continue
                 nws = L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4
                 ws2 = torch.empty(nws, dtype=torch.float32, device=self.device)
-                L.call("ydl_bn_act_bwd", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(dout), o.ld,
+                L.call_act("ydl_bn_act_bwd", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(dout), o.ld,
                        _p(o.t), o.ld, _p(m.bn.weight[co:]), _p(cf["mean"][co:]), _p(cf["invstd"][co:]),
                        _p(cf["scale"][co:]), _p(cf["shift"][co:]), rmode, act, _p(dyv), dy.ld, _p(dres_t), dres_ld,
                        _p(gw[co:]), _p(gb[co:]), accw, _p(ws2), npix, cw, cp, st2)
@@ -1054,6 +1054,87 @@ class Tape:
             self.bw.append(bw)
         return out
 
+    # ------------------------------------------------------------------ learnable activations (csrc/act.hip)
+    @staticmethod
+    def _param_grad(p: torch.nn.Parameter, device) -> torch.Tensor:
+        """gradient row of a per-channel parameter; a frozen one gets a scratch row (the launch writes all its rows)"""
+        if not p.requires_grad:
+            return torch.empty(p.numel(), dtype=torch.float32, device=device)
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+        return p.grad
+
+    def acon(self, z: Var, m, out: Optional[Var] = None) -> Var:
+        """AconC behind a materialised BatchNorm output: out = d * sigmoid(beta * d) + p2 * z, d = (p1 - p2) * z, with ``m.p1``,
+        ``m.p2``, ``m.beta`` of shape (1, C, 1, 1) (utils/activations.py).  The backward is one pass (ydl_acon_bwd): dz and the three
+        per-channel sums, added into the parameters' gradient rows."""
+        z = self._flat(z)
+        if out is not None and not out.aligned():
+            return self.copy(self.acon(z, m), out)
+        C, cp, hw = z.C, round_up(z.C, 8), z.H * z.W
+        if out is None:
+            out = self.new(z.N, C, z.H, z.W)
+        elif (out.N, out.C, out.H, out.W) != (z.N, C, z.H, z.W):
+            raise RuntimeError("acon: output slice has the wrong shape")
+        ps = (m.p1, m.p2, m.beta)
+        if any(p.numel() != C or not p.is_contiguous() or p.dtype != torch.float32 for p in ps):
+            raise RuntimeError(f"acon: p1 / p2 / beta must be contiguous f32 rows of {C} channels")
+        L.call("ydl_acon_fwd", self.dt, _p(z.t), z.ld, _p(ps[0]), _p(ps[1]), _p(ps[2]), 0, _p(out.t), out.ld, z.npix, hw, C, cp, _stream())
+        if not self.record:
+            return out
+        if z.need:
+            self._use(z)
+
+        def bw():
+            if not out.is_set():
+                return
+            st = _stream()
+            g1, g2, gb = (self._param_grad(p, self.device) for p in ps)
+            ws = torch.empty(L.lib().ydl_acon_bwd_ws_bytes(z.npix, hw, 0, cp) // 4, dtype=torch.float32, device=self.device)
+            if z.need:
+                gz, acc = self.grad_target(z)
+                ldz = z.ld
+            else:                                   # nothing upstream wants dz: the pass still forms the parameter sums
+                scratch = self.new(z.N, C, z.H, z.W)
+                gz, acc, ldz = scratch.t, 0, scratch.ld
+            L.call("ydl_acon_bwd", self.dt, _p(z.t), z.ld, _p(self._gbuf(out)), out.ld, _p(ps[0]), _p(ps[1]), _p(ps[2]), 0,
+                   _p(gz), ldz, acc, _p(g1), _p(g2), _p(gb), 1, _p(ws), z.npix, hw, C, cp, st)
+            from . import config as _cfg
+            for p in ps:
+                if p.requires_grad:
+                    _cfg.mark_touched(p)
+        self.bw.append(bw)
+        return out
+
+    def max2(self, a: Var, b: Var, out: Optional[Var] = None) -> Var:
+        """out = max(a, b) element-wise (FReLU's merge); the backward routes d(out) to the larger operand, half to each on a tie"""
+        a, b = self._flat(a), self._flat(b)
+        if (a.N, a.C, a.H, a.W) != (b.N, b.C, b.H, b.W):
+            raise RuntimeError("max2: operands differ in shape")
+        if out is not None and not out.aligned():
+            return self.copy(self.max2(a, b), out)
+        cp = round_up(a.C, 8)
+        if out is None:
+            out = self.new(a.N, a.C, a.H, a.W)
+        elif (out.N, out.C, out.H, out.W) != (a.N, a.C, a.H, a.W):
+            raise RuntimeError("max2: output slice has the wrong shape")
+        L.call("ydl_max2_fwd", self.dt, _p(a.t), a.ld, _p(b.t), b.ld, _p(out.t), out.ld, a.npix, cp, _stream())
+        if not self.record:
+            return out
+        for v in (a, b):
+            if v.need:
+                self._use(v)
+
+        def bw():
+            if not out.is_set() or not (a.need or b.need):
+                return
+            ga, acca = self.grad_target(a) if a.need else (None, 0)
+            gb, accb = self.grad_target(b) if b.need else (None, 0)
+            L.call("ydl_max2_bwd", self.dt, _p(a.t), a.ld, _p(b.t), b.ld, _p(self._gbuf(out)), out.ld, _p(ga), a.ld, acca,
+                   _p(gb), b.ld, accb, a.npix, cp, _stream())
+        self.bw.append(bw)
+        return out
+
     def concat(self, xs: Sequence[Var], align: bool = True) -> Var:
         """Concat along channels with the reference's auto-align (bilinear, align_corners=False, to the first
         input's size) — seg_diceloss_yolov5.py:484-507.
@@ -1250,7 +1331,7 @@ class Tape:
         else:
             L.call("ydl_dwconv2_fwd", self.dt, _p(x.t), x.ld, _p(wm), _p(y.t), y.ld, None, x.N, x.H, x.W, C, k, s, st)
             self._bn_coeffs(m, cf, C, st)
-        L.call("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
+        L.call_act("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
                res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
         if not self.record:
             return out
@@ -1270,7 +1351,7 @@ class Tape:
             gw, gb, accw = self._bn_grad_rows(m, cp)
             dres_t, dres_ld, rmode = self._res_grad(res, res_mode, out, dout)
             ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
-            L.call("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
+            L.call_act("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
                    _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rmode, act,
                    _p(dy.t), dy.ld, _p(dres_t), dres_ld, _p(gw), _p(gb), accw, _p(ws2), npix, C, cp, st2)
             m.touch_bn()
@@ -1326,7 +1407,7 @@ class Tape:
         else:
             L.call("ydl_gconv_fwd", gp, G, self.dt, _p(x.t), _p(w), _p(y.t), None, st)
             self._bn_coeffs(m, cf, Cout, st)
-        L.call("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
+        L.call_act("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
                res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
         if not self.record:
             return out
@@ -1347,7 +1428,7 @@ class Tape:
             gw, gb, accw = self._bn_grad_rows(m, cp)
             dres_t, dres_ld, rmode = self._res_grad(res, res_mode, out, dout)
             ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
-            L.call("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
+            L.call_act("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
                    _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rmode, act,
                    _p(dy.t), dy.ld, _p(dres_t), dres_ld, _p(gw), _p(gb), accw, _p(ws2), npix, Cout, cp, st2)
             m.touch_bn()
@@ -1405,7 +1486,7 @@ class Tape:
         else:
             L.call("ydl_xconv_fwd", gp, ax, self.dt, _p(x.t), _p(w), _p(y.t), None, st)
             self._bn_coeffs(m, cf, Cout, st)
-        L.call("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
+        L.call_act("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
                res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
         if not self.record:
             return out
@@ -1426,7 +1507,7 @@ class Tape:
             gw, gb, accw = self._bn_grad_rows(m, cp)
             dres_t, dres_ld, rmode = self._res_grad(res, res_mode, out, dout)
             ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
-            L.call("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
+            L.call_act("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
                    _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rmode, act,
                    _p(dy.t), dy.ld, _p(dres_t), dres_ld, _p(gw), _p(gb), accw, _p(ws2), npix, Cout, cp, st2)
             m.touch_bn()
@@ -1503,7 +1584,7 @@ class Tape:
         L.call("ydl_conv_fwd", gp, self.dt, _p(x.t), _p(w), _p(out.t), None, 0, st)
         if shift is not None:
             ones, bias = shift(self.device)
-            L.call("ydl_bn_act_fwd", self.dt, _p(out.t), out.ld, _p(ones), _p(bias), _p(res.t) if res is not None else None,
+            L.call_act("ydl_bn_act_fwd", self.dt, _p(out.t), out.ld, _p(ones), _p(bias), _p(res.t) if res is not None else None,
                    res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, out.npix, round_up(out.C, 8), st)
 
     def _conv_bias_bwd(self, m, gp, x: Var, dy: Var, wt: torch.Tensor, st) -> None:
