@@ -86,7 +86,12 @@ int ydl_conv_fwd_block_m(const ydl_conv_geom* g, int dtype);
  * BN; finish them with ydl_bn_finalize. */
 int ydl_conv_fwd(const ydl_conv_geom* g, int dtype, const void* x, const void* w, void* y,
                  float* stats_ws, int accumulate, void* stream);
-/* dx (+)= conv_transpose(dy, wt).  accumulate != 0 adds into dx (gradient fan-in). */
+/* dx (+)= conv_transpose(dy, wt).  accumulate != 0 adds into dx (gradient fan-in).
+ * The same three entry points run nn.ConvTranspose2d(c1, c2, k, 2, p, op) with the roles of x and dy exchanged, on the MIRRORED
+ * geometry {N, Hi = 2H, Wi = 2W, Cin = c2, Ho = H, Wo = W, Cout = c1, k, 2, p, ldx = ld of y / dy, ldy = ld of x}: the parameter
+ * [c1][c2][k][k] in channels_last storage is the KRSC master [c1][k*k][c2] of that convolution (ydl_weight_prep(master, w, wt, c1,
+ * k*k, c2)); forward y = ydl_conv_dgrad(dy := x, wt, dx := y), input gradient ydl_conv_fwd(x := dy, w, y := dx), weight gradient
+ * ydl_conv_wgrad(x := dy, dy := x).  (k, p, op) in {(2,0,0), (4,1,0), (3,1,1)} give Hi = 2H exactly. */
 int ydl_conv_dgrad(const ydl_conv_geom* g, int dtype, const void* dy, const void* wt, void* dx,
                    int accumulate, void* stream);
 /* Input gradient AND weight gradient of a 1x1 / stride-1 convolution in ONE pass over dy (both are HBM-bound on large maps: dy is
@@ -309,11 +314,21 @@ int ydl_spp_pool_bwd(int dtype, const void* dy1, const void* dy2, const void* dy
                      const uint8_t* idx2, const uint8_t* idx3, void* dx, int lddx, int accumulate,
                      int N, int H, int W, int C, int k1, int k2, int k3, void* stream);
 /* resize: mode 0 nearest (src=min(floor(dst*scale),in-1)), 1 bilinear align_corners=False, 2 bilinear
- * align_corners=True.  scale_h/w <= 0 means "derive from sizes" (in/out, or (in-1)/(out-1)). */
+ * align_corners=True.  scale_h/w <= 0 means "derive from sizes" (in/out, or (in-1)/(out-1)).  Modes 3 and 4 (the tape's
+ * RESIZE_BICUBIC / RESIZE_BICUBIC_AC) are refused here with a message: bicubic has the entry points ydl_bicubic_fwd / _bwd below. */
 int ydl_resize_fwd(int dtype, int mode, const void* x, int ldx, void* y, int ldy,
                    int N, int Hi, int Wi, int Ho, int Wo, int C, float scale_h, float scale_w, void* stream);
 int ydl_resize_bwd(int dtype, int mode, const void* dy, int lddy, void* dx, int lddx, int accumulate,
                    int N, int Hi, int Wi, int Ho, int Wo, int C, float scale_h, float scale_w, void* stream);
+/* bicubic resize, ATen's upsample_bicubic2d (A = -0.75); align != 0 is align_corners=True.  scale as above.  src = scale*(dst+0.5)-0.5
+ * NOT clamped at 0 (align: scale*dst), i = floor(src), t = src - i, taps i-1 .. i+2 each clamped to [0, in-1], coefficients
+ * c0 = ((A(t+1) - 5A)(t+1) + 8A)(t+1) - 4A, c1 = ((A+2)t - (A+3))t*t + 1, c2 = c1 at 1-t, c3 = c0's cubic at (1-t)+1, all in
+ * round-to-nearest f32 operations; the output is the separable 4 x 4 sum in f32.  The backward is the exact transpose in gather form
+ * (no atomics, bitwise reproducible); accumulate != 0 adds into dx. */
+int ydl_bicubic_fwd(int dtype, int align, const void* x, int ldx, void* y, int ldy,
+                    int N, int Hi, int Wi, int Ho, int Wo, int C, float scale_h, float scale_w, void* stream);
+int ydl_bicubic_bwd(int dtype, int align, const void* dy, int lddy, void* dx, int lddx, int accumulate,
+                    int N, int Hi, int Wi, int Ho, int Wo, int C, float scale_h, float scale_w, void* stream);
 /* y += resize(x) (same modes and index arithmetic as ydl_resize_fwd); with ``sums`` != NULL also adds the per-channel (sum, sum of
  * squares) of the result to BatchNorm replica rows sums[YDL_BN_REPLICAS][2][sums_ld], exactly like ydl_conv_fwd_sums' epilogues: the
  * last launch of a 1x1 Conv over the auto-aligned Concat [a, resize(b)] (seg_diceloss_yolov5.py:484-507 + :388-409) evaluated as
@@ -584,6 +599,21 @@ int ydl_dwconv2_dgrad(int dtype, const void* dy, int lddy, const float* w, void*
 int64_t ydl_dwconv2_wgrad_ws_bytes(int C, int k);
 int ydl_dwconv2_wgrad(int dtype, const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, int N, int H, int W, int C,
                       int k, int s, void* stream);
+/* ---- depth-wise transposed convolution, stride 2 (DWConvTranspose2d, models/common.py:73-76): the forms that double the map,
+ * (k, p, op) in {(2,0,0), (4,1,0), (3,1,1)}: Ho = (H-1)*2 - 2p + k + op = 2H.  (H, W) is always the INPUT size; w is the f32 master
+ * [C][k*k] (= nn.ConvTranspose2d(C, C, k, 2, p, op, groups=C).weight, shape [C,1,k,k]); C a multiple of 8; pixel strides as for
+ * ydl_dwconv2_* (tensors may be channel slices of wider buffers).  ydl_dwtconv_supported answers on the host, without a device.
+ *   fwd:   y[n,oh,ow,c] = b[c] + sum_{r,t} x[n,(oh+p-r)/2,(ow+p-t)/2,c] * w[c][r*k+t]  over exact quotients inside the input
+ *   dgrad: dx[n,i,j,c] (+)= sum_{r,t} dy[n,2i-p+r,2j-p+t,c] * w[c][r*k+t]              over taps inside the output
+ *   wgrad: dw[c][r*k+t] += sum_{n,i,j} x[n,i,j,c] * dy[n,2i-p+r,2j-p+t,c]; per-CTA partials in ws merged in a fixed order */
+int ydl_dwtconv_supported(int C, int k, int s, int p, int op);
+int ydl_dwtconv_fwd(int dtype, const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, int N, int H, int W, int C,
+                    int k, int p, int op, void* stream);
+int ydl_dwtconv_dgrad(int dtype, const void* dy, int lddy, const float* w, void* dx, int lddx, int accumulate, int N, int H, int W,
+                      int C, int k, int p, int op, void* stream);
+int64_t ydl_dwtconv_wgrad_ws_bytes(int C, int k);
+int ydl_dwtconv_wgrad(int dtype, const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, int N, int H, int W, int C,
+                      int k, int p, int op, void* stream);
 /* BN partial statistics of any NHWC tensor in the format ydl_bn_finalize consumes: nblocks = ceil(npix / block_m) rows of
  * (sum, M2) with block_m = ydl_bn_stats_block_m() */
 int ydl_bn_stats_block_m(void);

@@ -20,6 +20,7 @@ AXIS_W, AXIS_H = 0, 1             # YDL_AXIS_* of ydl.h
 OPT_ADAM, OPT_ADAMW, OPT_RMSPROP = 1, 2, 3      # YDL_OPT_* of ydl.h
 OPT_MAX_CLASSES, OPT_HYPER_FLOATS = 16, 76
 RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BILINEAR_AC = 0, 1, 2
+RESIZE_BICUBIC, RESIZE_BICUBIC_AC = 3, 4           # Tape.resize routes them to ydl_bicubic_fwd / ydl_bicubic_bwd
 
 
 class ConvGeom(C.Structure):
@@ -104,6 +105,8 @@ SIGNATURES = {
     "ydl_maxpool_bwd": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_resize_fwd": (_i, [_i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
     "ydl_resize_bwd": (_i, [_i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
+    "ydl_bicubic_fwd": (_i, [_i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
+    "ydl_bicubic_bwd": (_i, [_i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
     "ydl_resize_acc_sums": (_i, [_i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _vp]),
     "ydl_copy2d": (_i, [_i, _vp, _i, _vp, _i, _i64, _i, _i, _vp]),
     "ydl_nchw_to_nhwc": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -157,6 +160,11 @@ SIGNATURES = {
     "ydl_dwconv2_dgrad": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_dwconv2_wgrad_ws_bytes": (_i64, [_i, _i]),
     "ydl_dwconv2_wgrad": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ydl_dwtconv_supported": (_i, [_i, _i, _i, _i, _i]),
+    "ydl_dwtconv_fwd": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ydl_dwtconv_dgrad": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ydl_dwtconv_wgrad_ws_bytes": (_i64, [_i, _i]),
+    "ydl_dwtconv_wgrad": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_bn_stats_block_m": (_i, []),
     "ydl_bn_stats_ws_bytes": (_i64, [_i64, _i]),
     "ydl_bn_stats": (_i, [_i, _vp, _i, _vp, _i64, _i, _vp]),

@@ -1,4 +1,4 @@
-// Spatial NHWC ops: max-pool, nearest / bilinear resize (both align_corners conventions), strided slice copy,
+// Spatial NHWC ops: max-pool, nearest / bilinear / bicubic resize (both align_corners conventions), strided slice copy,
 // NCHW<->NHWC edge conversion, per-(n,c) channel gating.  HBM-bound, 16-byte channel vectors per thread.
 // Index arithmetic restates ATen's (UpSample.h area_pixel_compute_source_index / nearest_idx) with explicit
 // round-to-nearest f32 ops so the compiler cannot contract them into FMAs: indices are bit-exact vs the CPU.
@@ -613,6 +613,142 @@ __global__ __launch_bounds__(256) void resize_acc_sums_kernel(int mode, const T*
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// bicubic resize (ydl_bicubic_fwd / ydl_bicubic_bwd): ATen's upsample_bicubic2d, A = -0.75 (UpSample.h cubic_convolution1/2,
+// get_cubic_upsample_coefficients).  The source coordinate is NOT clamped at 0 (unlike bilinear); the four taps
+// floor(src)-1 .. floor(src)+2 are each clamped to [0, in-1].  Every index / coefficient operation is an explicit
+// round-to-nearest f32 op in a fixed order, so a host restatement repeats it bit for bit.
+// ------------------------------------------------------------------------------------------------------
+struct Cub { int i[4]; float c[4]; };
+
+__device__ __forceinline__ float cubic_c1(float x) {        // ((A+2) x - (A+3)) x x + 1
+    return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(1.25f, x), 2.25f), x), x), 1.f);
+}
+__device__ __forceinline__ float cubic_c2(float x) {        // ((A x - 5A) x + 8A) x - 4A
+    return __fsub_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fsub_rn(__fmul_rn(-0.75f, x), -3.75f), x), -6.f), x), -3.f);
+}
+__device__ __forceinline__ Cub cub_src(int dst, float scale, int in, bool align) {
+    Cub Q;
+    const float src = align ? __fmul_rn(scale, (float)dst) : __fsub_rn(__fmul_rn(scale, __fadd_rn((float)dst, 0.5f)), 0.5f);
+    const float fl = floorf(src);
+    const float t = __fsub_rn(src, fl);
+    const float u = __fsub_rn(1.f, t);
+    const int i0 = (int)fl;
+    Q.c[0] = cubic_c2(__fadd_rn(t, 1.f));
+    Q.c[1] = cubic_c1(t);
+    Q.c[2] = cubic_c1(u);
+    Q.c[3] = cubic_c2(__fadd_rn(u, 1.f));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int v = i0 - 1 + j;
+        v = v < 0 ? 0 : v;
+        Q.i[j] = v > in - 1 ? in - 1 : v;
+    }
+    return Q;
+}
+// the weight input index ``i`` carries in output ``dst``: clamped border taps pile onto 0 and in-1 (added in tap order)
+__device__ __forceinline__ float cub_weight(const Cub& Q, int i) {
+    float w = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w = __fadd_rn(w, Q.i[j] == i ? Q.c[j] : 0.f);
+    return w;
+}
+
+// forward: thread layout of resize_acc_sums_kernel (a thread owns one 16-byte channel chunk, a CTA walks whole output rows);
+// out = sum_a ch[a] * (sum_b cw[b] * x[ih_a][iw_b]) in f32, rows and columns in tap order
+template <typename T>
+__global__ __launch_bounds__(256) void bicubic_fwd_kernel(int align, const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
+                                                          int Hi, int Wi, int Ho, int Wo, int Cp, float sh, float sw, int nrows) {
+    constexpr int V = ET<T>::V;
+    const int cpp = Cp / V;
+    const int cpb = cpp < 256 ? cpp : 256;
+    const int R = 256 / cpb;
+    const int cq = threadIdx.x % cpb, pl = threadIdx.x / cpb;
+    const int chunk = blockIdx.y * 256 + cq;
+    if (!(pl < R && chunk < cpp)) return;
+    const int c0 = chunk * V;
+    for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
+        const int n = row / Ho, ho = row - n * Ho;
+        const T* xb = x + (size_t)n * Hi * Wi * ldx + c0;
+        T* yrow = y + (size_t)row * Wo * ldy + c0;
+        const Cub qh = cub_src(ho, sh, Hi, align != 0);
+        for (int wo = pl; wo < Wo; wo += R) {
+            const Cub qw = cub_src(wo, sw, Wi, align != 0);
+            float o[V];
+#pragma unroll
+            for (int e = 0; e < V; ++e) o[e] = 0.f;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const T* r = xb + (size_t)qh.i[a] * Wi * ldx;
+                float rs[V];
+#pragma unroll
+                for (int e = 0; e < V; ++e) rs[e] = 0.f;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    float v[V];
+                    unpack16<T>(*(const uint4*)(r + (size_t)qw.i[b] * ldx), v);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) rs[e] = fmaf(qw.c[b], v[e], rs[e]);
+                }
+#pragma unroll
+                for (int e = 0; e < V; ++e) o[e] = fmaf(qh.c[a], rs[e], o[e]);
+            }
+            *(uint4*)(yrow + (size_t)wo * ldy) = pack16<T>(o);
+        }
+    }
+}
+
+// conservative bounds on {dst : floor(src(dst)) in [i-2, i+1]}, the outputs whose unclamped taps reach i; the clamped taps of the
+// two borders come from every output below / above
+__device__ __forceinline__ void cub_cand_range(int i, int in, int out, float scale, int& lo, int& hi) {
+    const float inv = scale > 0.f ? 1.0f / scale : (float)out;
+    const float a = ((float)i - 2.5f) * inv - 2.f, b = ((float)i + 2.5f) * inv + 2.f;
+    lo = a < 0.f ? 0 : (a > (float)(out - 1) ? out - 1 : (int)a);
+    hi = b > (float)(out - 1) ? out - 1 : (int)b;
+    if (i == in - 1) hi = out - 1;
+    if (i == 0) lo = 0;
+}
+
+// gather backward (the resize_bwd_kernel pattern): an input element scans the outputs that can reference it and re-derives the
+// forward taps; candidates are added rows outer, columns inner, ascending => bitwise reproducible, no atomics
+template <typename T>
+__global__ __launch_bounds__(256) void bicubic_bwd_kernel(int align, const T* __restrict__ dy, int lddy, T* __restrict__ dx, int lddx,
+                                                          int accumulate, int N, int Hi, int Wi, int Ho, int Wo, int Cp, float sh, float sw) {
+    constexpr int V = ET<T>::V;
+    const int cpp = Cp / V;
+    const long long total = (long long)N * Hi * Wi * cpp;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int cq = (int)(i % cpp);
+        const long long pix = i / cpp;
+        const int iw = (int)(pix % Wi);
+        const long long t2 = pix / Wi;
+        const int ih = (int)(t2 % Hi);
+        const int n = (int)(t2 / Hi);
+        float g[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) g[e] = 0.f;
+        if (accumulate) unpack16<T>(*(const uint4*)(dx + (size_t)pix * lddx + cq * V), g);
+        int hlo, hhi, wlo, whi;
+        cub_cand_range(ih, Hi, Ho, sh, hlo, hhi);
+        cub_cand_range(iw, Wi, Wo, sw, wlo, whi);
+        const T* db = dy + (size_t)n * Ho * Wo * lddy + cq * V;
+        for (int ho = hlo; ho <= hhi; ++ho) {
+            const float wh = cub_weight(cub_src(ho, sh, Hi, align != 0), ih);
+            if (wh == 0.f) continue;
+            for (int wo = wlo; wo <= whi; ++wo) {
+                const float ww = cub_weight(cub_src(wo, sw, Wi, align != 0), iw);
+                if (ww == 0.f) continue;
+                float d[V];
+                unpack16<T>(*(const uint4*)(db + ((size_t)ho * Wo + wo) * lddy), d);
+                const float wgt = __fmul_rn(wh, ww);
+#pragma unroll
+                for (int e = 0; e < V; ++e) g[e] = fmaf(wgt, d[e], g[e]);
+            }
+        }
+        *(uint4*)(dx + (size_t)pix * lddx + cq * V) = pack16<T>(g);
+    }
+}
+
 int g_resize_rows = 1;         // ydl_debug_set key 11: 0 = the element-indexed forward kernel (tests)
 int g_resize_int = 1;          // ydl_debug_set key 10: 0 = the generic gather backward also for integer scale factors (tests)
 static inline float axis_scale(int mode, int in, int out, float given) {
@@ -625,6 +761,7 @@ extern "C" int ydl_resize_fwd(int dtype, int mode, const void* x, int ldx, void*
                               int N, int Hi, int Wi, int Ho, int Wo, int C, float scale_h, float scale_w, void* stream) {
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
+    YDL_CHECK(mode != 3 && mode != 4, "the bicubic modes 3 and 4 are served by ydl_bicubic_fwd");
     YDL_CHECK(x && y && mode >= 0 && mode <= 2 && ldx >= Cp && ldy >= Cp, "bad arguments");
     YDL_CHECK(aligned16(x) && aligned16(y) && ldx % V == 0 && ldy % V == 0, "16-byte alignment");
     float sh = axis_scale(mode, Hi, Ho, scale_h), sw = axis_scale(mode, Wi, Wo, scale_w);
@@ -648,6 +785,7 @@ extern "C" int ydl_resize_acc_sums(int dtype, int mode, const void* x, int ldx, 
                                    int C, float scale_h, float scale_w, float* sums, int sums_ld, void* stream) {
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
+    YDL_CHECK(mode != 3 && mode != 4, "the bicubic modes 3 and 4 are served by ydl_bicubic_fwd only (no fused accumulate / statistics form)");
     YDL_CHECK(x && y && mode >= 0 && mode <= 2 && ldx >= Cp && ldy >= Cp && N >= 1, "bad arguments");
     YDL_CHECK(aligned16(x) && aligned16(y) && ldx % V == 0 && ldy % V == 0, "16-byte alignment");
     YDL_CHECK(sums == nullptr || sums_ld >= Cp, "statistics rows shorter than the padded channel count");
@@ -666,6 +804,7 @@ extern "C" int ydl_resize_bwd(int dtype, int mode, const void* dy, int lddy, voi
                               int N, int Hi, int Wi, int Ho, int Wo, int C, float scale_h, float scale_w, void* stream) {
     const int V = dtype == YDL_F32 ? 4 : 8;
     const int Cp = round_up(C, V);
+    YDL_CHECK(mode != 3 && mode != 4, "the bicubic modes 3 and 4 are served by ydl_bicubic_bwd");
     YDL_CHECK(dy && dx && mode >= 0 && mode <= 2 && lddy >= Cp && lddx >= Cp, "bad arguments");
     YDL_CHECK(aligned16(dy) && aligned16(dx) && lddy % V == 0 && lddx % V == 0, "16-byte alignment");
     float sh = axis_scale(mode, Hi, Ho, scale_h), sw = axis_scale(mode, Wi, Wo, scale_w);
@@ -689,6 +828,42 @@ extern "C" int ydl_resize_bwd(int dtype, int mode, const void* dy, int lddy, voi
     }
     if (dtype == YDL_F32) resize_bwd_kernel<float><<<grid, 256, 0, st>>>(mode, (const float*)dy, lddy, (float*)dx, lddx, accumulate, N, Hi, Wi, Ho, Wo, Cp, sh, sw);
     else resize_bwd_kernel<bf16_t><<<grid, 256, 0, st>>>(mode, (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, accumulate, N, Hi, Wi, Ho, Wo, Cp, sh, sw);
+    YDL_LAUNCH_CHECK();
+    return 0;
+}
+
+// bicubic resize (RESIZE_BICUBIC / RESIZE_BICUBIC_AC of the tape): entry points of their own, ydl_resize_* keep their three modes.
+// align != 0: align_corners = True.  The scale is the bilinear one (axis_scale): given, in / out, or (in - 1) / (out - 1).
+extern "C" int ydl_bicubic_fwd(int dtype, int align, const void* x, int ldx, void* y, int ldy,
+                               int N, int Hi, int Wi, int Ho, int Wo, int C, float scale_h, float scale_w, void* stream) {
+    const int V = dtype == YDL_F32 ? 4 : 8;
+    const int Cp = round_up(C, V);
+    YDL_CHECK((dtype == YDL_F32 || dtype == YDL_BF16) && x && y && ldx >= Cp && ldy >= Cp, "bad arguments");
+    YDL_CHECK(aligned16(x) && aligned16(y) && ldx % V == 0 && ldy % V == 0, "16-byte alignment");
+    YDL_CHECK(N >= 1 && Hi >= 1 && Wi >= 1 && Ho >= 1 && Wo >= 1 && C >= 1 && (long long)N * Ho < (1ll << 30), "empty tensor or too many output rows");
+    const int am = align ? 2 : 1;
+    const float sh = axis_scale(am, Hi, Ho, scale_h), sw = axis_scale(am, Wi, Wo, scale_w);
+    hipStream_t st = (hipStream_t)stream;
+    const int nrows = N * Ho, cpp = Cp / V;
+    const dim3 grid((unsigned)(nrows < 4096 ? nrows : 4096), (unsigned)((cpp + 255) / 256));
+    if (dtype == YDL_F32) bicubic_fwd_kernel<float><<<grid, 256, 0, st>>>(align != 0, (const float*)x, ldx, (float*)y, ldy, Hi, Wi, Ho, Wo, Cp, sh, sw, nrows);
+    else bicubic_fwd_kernel<bf16_t><<<grid, 256, 0, st>>>(align != 0, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, Hi, Wi, Ho, Wo, Cp, sh, sw, nrows);
+    YDL_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int ydl_bicubic_bwd(int dtype, int align, const void* dy, int lddy, void* dx, int lddx, int accumulate,
+                               int N, int Hi, int Wi, int Ho, int Wo, int C, float scale_h, float scale_w, void* stream) {
+    const int V = dtype == YDL_F32 ? 4 : 8;
+    const int Cp = round_up(C, V);
+    YDL_CHECK((dtype == YDL_F32 || dtype == YDL_BF16) && dy && dx && lddy >= Cp && lddx >= Cp, "bad arguments");
+    YDL_CHECK(aligned16(dy) && aligned16(dx) && lddy % V == 0 && lddx % V == 0, "16-byte alignment");
+    YDL_CHECK(N >= 1 && Hi >= 1 && Wi >= 1 && Ho >= 1 && Wo >= 1 && C >= 1, "empty tensor");
+    const int am = align ? 2 : 1;
+    const float sh = axis_scale(am, Hi, Ho, scale_h), sw = axis_scale(am, Wi, Wo, scale_w);
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = sgrid((long long)N * Hi * Wi * (Cp / V));
+    if (dtype == YDL_F32) bicubic_bwd_kernel<float><<<grid, 256, 0, st>>>(align != 0, (const float*)dy, lddy, (float*)dx, lddx, accumulate, N, Hi, Wi, Ho, Wo, Cp, sh, sw);
+    else bicubic_bwd_kernel<bf16_t><<<grid, 256, 0, st>>>(align != 0, (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, accumulate, N, Hi, Wi, Ho, Wo, Cp, sh, sw);
     YDL_LAUNCH_CHECK();
     return 0;
 }

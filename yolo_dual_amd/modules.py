@@ -27,7 +27,7 @@ __all__ = ["autopad", "Conv", "C3", "C3Common", "Bottleneck", "C2f", "C3k2", "GA
            "BasicBlock", "BottleneckBlock", "SegmentHead", "run_region", "Linear", "DCNv3", "DCNV3_YoLo", "Bottleneck_DCNV3",
            "C3_DCNV3", "DeformConv2d", "C3_DCN", "C2f_DCN", "DCNv2",
            "Bottleneck_DCN", "C3_DCNCommon", "AttentionConv", "AttentionStem", "DWConv", "GhostConv", "GhostBottleneck", "C3Ghost",
-           "BasicConv", "RFB", "ASPP", "CrossConv", "C3x"]
+           "BasicConv", "RFB", "ASPP", "CrossConv", "C3x", "ConvTranspose2d", "DWConvTranspose2d"]
 
 
 def autopad(k, p=None, d=1):
@@ -256,7 +256,7 @@ class _GemmWeights:
 
     def bias_coeffs(self, device):
         """(ones, bias) padded to a multiple of 8 channels for ydl_bn_act_fwd (scale = 1, shift = bias)"""
-        rows = self._gemm_dims()[0]
+        rows = self._bias_len()
         cp = round_up(rows, 8)
         key = (self.bias.data_ptr(), self.bias._version, config.weight_epoch())
         c = self._wcache
@@ -268,6 +268,10 @@ class _GemmWeights:
             L.call("ydl_copy2d", L.YDL_F32, _p(self._krsc(self.bias.detach())), rows, _p(c["bpad"]), cp, 1, rows, 0, _stream())
             c["bkey"] = key
         return c["ones"], c["bpad"]
+
+    def _bias_len(self) -> int:
+        """length of the bias row: the GEMM's rows, except where the GEMM runs mirrored (ConvTranspose2d)"""
+        return self._gemm_dims()[0]
 
     def _grad_of(self, p: nn.Parameter) -> torch.Tensor:
         """(this holder's rows of) the parameter's gradient"""
@@ -1184,6 +1188,120 @@ class _BiasConv2d(_GemmWeights, nn.Conv2d):
         return self.out_channels, self.k * self.k, self.in_channels
 
 
+# the stride-2 transposed convolutions that double the map exactly: Ho = (H - 1) * 2 - 2 p + k + output_padding = 2 H
+_TCONV_FORMS = ((2, 0, 0), (4, 1, 0), (3, 1, 1))
+
+
+def _pair_int(v, who: str, what: str) -> int:
+    """a square int / (a, a) argument as an int; anything rectangular is refused by name"""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2 or v[0] != v[1]:
+            raise NotImplementedError(f"{who}: {what}={tuple(v)} must be square on the HIP path")
+        v = v[0]
+    return int(v)
+
+
+def _tconv_args(who: str, names, c1, c2, k, s, p, op, groups=1, dilation=1, padding_mode="zeros", depthwise=False):
+    """the served set of the two transposed convolutions; ``names`` = the constructor's own names for (kernel, stride, padding,
+    output padding).  Everything outside it raises NotImplementedError naming the class and the offending argument."""
+    nk, ns, np_, nop = names
+    k, s, p, op = _pair_int(k, who, nk), _pair_int(s, who, ns), _pair_int(p, who, np_), _pair_int(op, who, nop)
+    d = _pair_int(dilation, who, "dilation")
+    if padding_mode != "zeros":
+        raise NotImplementedError(f"{who}: padding_mode={padding_mode!r} is not implemented (zeros only)")
+    if d != 1:
+        raise NotImplementedError(f"{who}: dilation={d} is not implemented on the HIP path (dilation = 1 only)")
+    if depthwise:
+        if not (c1 == c2 == groups):
+            raise NotImplementedError(f"{who}: c1={c1}, c2={c2} give groups = gcd(c1, c2) = {groups}; only the depth-wise form "
+                                      f"groups == c1 == c2 is implemented on the HIP path")
+    elif groups != 1:
+        raise NotImplementedError(f"{who}: groups={groups} is not implemented on the HIP path (groups = 1; the depth-wise form is "
+                                  "DWConvTranspose2d)")
+    if s != 2:
+        raise NotImplementedError(f"{who}: {ns}={s} is not implemented on the HIP path ({ns} = 2 only)")
+    if k not in (2, 3, 4):
+        raise NotImplementedError(f"{who}: {nk}={k} is not implemented on the HIP path: ({nk}, {np_}, {nop}) must be one of "
+                                  f"{_TCONV_FORMS} at {ns} = 2")
+    want = {f[0]: f for f in _TCONV_FORMS}[k]
+    if p != want[1]:
+        raise NotImplementedError(f"{who}: {np_}={p} with {nk}={k} is not implemented on the HIP path: ({nk}, {np_}, {nop}) must be "
+                                  f"one of {_TCONV_FORMS}")
+    if op != want[2]:
+        raise NotImplementedError(f"{who}: {nop}={op} with {nk}={k} is not implemented on the HIP path: ({nk}, {np_}, {nop}) must be "
+                                  f"one of {_TCONV_FORMS}")
+    if c1 % 8 or c2 % 8:
+        bad = ("c1" if depthwise else "in_channels") if c1 % 8 else ("c2" if depthwise else "out_channels")
+        raise NotImplementedError(f"{who}: {bad}={c1 if c1 % 8 else c2} is not implemented on the HIP path (channel counts must be "
+                                  "multiples of 8)")
+    return k, s, p, op
+
+
+class _TConvBase:
+    """stand-alone call / taped call dispatch of the two transposed convolutions (YdlModule.forward for an nn.ConvTranspose2d)"""
+    takes_list = False
+
+    def forward(self, x, output_size=None):
+        if output_size is not None:
+            raise NotImplementedError(f"{self._wname}: output_size is not implemented (the served forms double the map exactly)")
+        if isinstance(x, Var):
+            return self._fwd(x.tape, x)
+        return run_region(self, [x])
+
+
+class ConvTranspose2d(_TConvBase, _GemmWeights, nn.ConvTranspose2d):
+    """``nn.ConvTranspose2d(c1, c2, k, 2, p, output_padding)`` in the three forms that double the map (``_TCONV_FORMS``), groups 1,
+    run by Tape.conv_transpose on the implicit-GEMM entry points with the roles of x and dy exchanged: the parameter [c1][c2][k][k]
+    kept channels_last is physically [c1][k*k][c2], the KRSC master of the mirrored convolution c2 -> c1."""
+    _wname = "ConvTranspose2d"
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, output_padding=0, groups=1, bias=True,
+                 dilation=1, padding_mode="zeros", device=None, dtype=None):
+        k, s, p, op = _tconv_args("ConvTranspose2d", ("kernel_size", "stride", "padding", "output_padding"), in_channels, out_channels,
+                                  kernel_size, stride, padding, output_padding, groups, dilation, padding_mode)
+        super().__init__(in_channels, out_channels, k, s, p, op, groups, bias, dilation, padding_mode, device, dtype)
+        self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
+        self.k, self.s, self.p, self.op = k, s, p, op
+        self._wcache = {}
+
+    def _gemm_dims(self):
+        return self.in_channels, self.k * self.k, self.out_channels
+
+    def _bias_len(self) -> int:
+        return self.out_channels
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        return tape.conv_transpose(x, self, out=out)
+
+
+class DWConvTranspose2d(_TConvBase, nn.ConvTranspose2d):
+    """models/common.py:73-76: ``nn.ConvTranspose2d(c1, c2, k, s, p1, p2, groups=gcd(c1, c2))``; served depth-wise (c1 == c2) at
+    s = 2 in the forms of ``_TCONV_FORMS``, by the kernels of csrc/tconv.hip (Tape.dw_conv_transpose).  The weight [C][1][k][k] is
+    the f32 master [C][k*k] the kernels read."""
+    _wname = "DWConvTranspose2d"
+
+    def __init__(self, c1, c2, k=1, s=1, p1=0, p2=0):
+        g = math.gcd(c1, c2)
+        k, s, p1, p2 = _tconv_args("DWConvTranspose2d", ("k", "s", "p1", "p2"), c1, c2, k, s, p1, p2, groups=g, depthwise=True)
+        super().__init__(c1, c2, k, s, p1, p2, groups=g)
+        self.k, self.s, self.p, self.op = k, s, p1, p2
+
+    def master_dw(self) -> torch.Tensor:
+        w = self.weight.detach().permute(0, 2, 3, 1)
+        return w if w.is_contiguous() else w.contiguous()
+
+    def grad_dw(self) -> torch.Tensor:
+        if self.weight.grad is None:
+            self.weight.grad = torch.zeros_like(self.weight)
+        g = self.weight.grad.permute(0, 2, 3, 1)
+        if not g.is_contiguous():
+            raise RuntimeError("DWConvTranspose2d weight gradient must be [C][k*k]-contiguous")
+        return g
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        return tape.dw_conv_transpose(x, self, out=out)
+
+
 class DCNv2(YdlModule):
     """models/common.py:1629-1690: ``conv_offset_mask`` (plain biased Conv2d, zero-initialised) -> offsets = channels [0, 2GK),
     mask = sigmoid(channels [2GK, 3GK)) -> deform_conv2d(x, weight, offset, mask, bias) -> BatchNorm -> SiLU.  The sigmoid runs
@@ -1595,7 +1713,8 @@ class Concat(YdlModule):
 
 
 class Upsample(YdlModule):
-    """nn.Upsample restated for the taped path (nearest, or bilinear with either align_corners convention)."""
+    """nn.Upsample restated for the taped path (nearest, or bilinear / bicubic with either align_corners convention).  Bicubic is
+    never lazy and runs outside the virtual-concat fusions: materialize + Tape.resize (ydl_bicubic_fwd / ydl_bicubic_bwd)."""
 
     def __init__(self, size=None, scale_factor=None, mode="nearest", align_corners=None):
         super().__init__()
@@ -1603,7 +1722,7 @@ class Upsample(YdlModule):
         self.scale_factor = scale_factor
         self.mode = mode
         self.align_corners = align_corners
-        if mode not in ("nearest", "bilinear"):
+        if mode not in ("nearest", "bilinear", "bicubic"):
             raise NotImplementedError(f"Upsample mode {mode}")
 
     def _out_size(self, x: Var):
@@ -1628,7 +1747,10 @@ class Upsample(YdlModule):
                 sh, sw = (sf, sf) if not isinstance(sf, (tuple, list)) else sf
                 return tape.resize(x, Ho, Wo, L.RESIZE_NEAREST, 1.0 / sh, 1.0 / sw, out=out)
             return tape.resize(x, Ho, Wo, L.RESIZE_NEAREST, out=out)
-        mode = L.RESIZE_BILINEAR_AC if self.align_corners else L.RESIZE_BILINEAR
+        if self.mode == "bicubic":
+            mode = L.RESIZE_BICUBIC_AC if self.align_corners else L.RESIZE_BICUBIC
+        else:
+            mode = L.RESIZE_BILINEAR_AC if self.align_corners else L.RESIZE_BILINEAR
         if self.size is None and not self.align_corners:
             sf = self.scale_factor
             sh, sw = (sf, sf) if not isinstance(sf, (tuple, list)) else sf

@@ -999,7 +999,8 @@ class Tape:
 
     def resize(self, x: Var, Ho: int, Wo: int, mode: int, scale_h: float = 0.0, scale_w: float = 0.0,
                out: Optional[Var] = None) -> Var:
-        """mode: L.RESIZE_NEAREST / RESIZE_BILINEAR (align_corners=False) / RESIZE_BILINEAR_AC (True)."""
+        """mode: L.RESIZE_NEAREST / RESIZE_BILINEAR (align_corners=False) / RESIZE_BILINEAR_AC (True) / RESIZE_BICUBIC (False) /
+        RESIZE_BICUBIC_AC (True)."""
         x = self.materialize(x)
         if not x.aligned():
             x = self.copy(x, self.new(x.N, x.C, x.H, x.W, need=x.need, f32=(x.dt == L.YDL_F32)))
@@ -1007,14 +1008,17 @@ class Tape:
             return self.copy(self.resize(x, Ho, Wo, mode, scale_h, scale_w), out)
         if out is None:
             out = self.new(x.N, x.C, Ho, Wo, f32=(x.dt == L.YDL_F32))
-        L.call("ydl_resize_fwd", x.dt, mode, _p(x.t), x.ld, _p(out.t), out.ld, x.N, x.H, x.W, Ho, Wo, x.C,
+        # bicubic has entry points of its own (their second argument is align_corners); ydl_resize_* serve modes 0..2
+        cubic = mode in (L.RESIZE_BICUBIC, L.RESIZE_BICUBIC_AC)
+        fwd, bwd, arg = ("ydl_bicubic_fwd", "ydl_bicubic_bwd", int(mode == L.RESIZE_BICUBIC_AC)) if cubic else ("ydl_resize_fwd", "ydl_resize_bwd", mode)
+        L.call(fwd, x.dt, arg, _p(x.t), x.ld, _p(out.t), out.ld, x.N, x.H, x.W, Ho, Wo, x.C,
                scale_h, scale_w, _stream())
         if self.record:
             def bw():
                 if not out.is_set() or not x.need:
                     return
                 gx, acc = self.grad_target(x)
-                L.call("ydl_resize_bwd", x.dt, mode, _p(self._gbuf(out)), out.ld, _p(gx), x.ld, acc,
+                L.call(bwd, x.dt, arg, _p(self._gbuf(out)), out.ld, _p(gx), x.ld, acc,
                        x.N, x.H, x.W, Ho, Wo, x.C, scale_h, scale_w, _stream())
             self.bw.append(bw)
         return out
@@ -1632,6 +1636,102 @@ class Tape:
                     return
                 self._conv_bias_bwd(m, gp, x, Var(self, self._gbuf(out), out.ld, False), wt, _stream())
                 self._keep.append(geom)
+            self.bw.append(bw)
+        return out
+
+    def _bias_grad(self, m, dy: Var, st) -> None:
+        """bias gradient of a transposed convolution: ydl_channel_sum over dy, added into ``m.bias.grad``"""
+        if m.bias is None or not m.bias.requires_grad:
+            return
+        if m.bias.grad is None:
+            m.bias.grad = torch.zeros_like(m.bias)
+        ws = torch.empty(L.lib().ydl_channel_sum_ws_bytes(dy.C) // 4, dtype=torch.float32, device=self.device)
+        L.call("ydl_channel_sum", self.dt, _p(dy.t), dy.ld, _p(m.bias.grad), _p(ws), dy.npix, dy.C, 1, st)
+        self._keep.append(ws)
+        from . import config as _cfg
+        _cfg.mark_touched(m.bias)
+
+    def _tconv_out(self, x: Var, C2: int, out: Optional[Var], who: str) -> Var:
+        if out is None:
+            return self.new(x.N, C2, 2 * x.H, 2 * x.W)
+        if (out.N, out.C, out.H, out.W) != (x.N, C2, 2 * x.H, 2 * x.W) or not out.aligned():
+            raise RuntimeError(f"{who}: the output slice has the wrong shape or is not 16-byte aligned")
+        return out
+
+    def conv_transpose(self, x: Var, m, out: Optional[Var] = None) -> Var:
+        """``nn.ConvTranspose2d(c1, c2, k, 2, p, output_padding)`` in the forms that double the map (modules._TCONV_FORMS), with no new
+        kernel: a transposed convolution is the input gradient of the MIRRORED convolution c2 -> c1 on the (2H, 2W) map, and
+        ydl_conv_dgrad already evaluates that in sub-pixel form (one dense convolution per output-parity class).  ``m`` is a
+        modules.ConvTranspose2d: its channels_last parameter [c1][c2][k][k] is the KRSC master [c1][k*k][c2] of the mirrored layer.
+          forward          ydl_conv_dgrad(g, dy := x, wt, dx := y), then the bias by ydl_bn_act_fwd in place with scale 1
+          bias gradient    ydl_channel_sum over dy
+          weight gradient  the holder's wgrad with x := dy, dy := x
+          input gradient   ydl_conv_fwd(g, x := dy, w, y := dx, accumulate)"""
+        x = self._flat(x)
+        c1, _taps, c2 = m._gemm_dims()
+        if x.C != c1:
+            raise RuntimeError(f"ConvTranspose2d input channel mismatch: got {x.C}, weight expects {c1}")
+        w, wt = m.compute_weights(self)
+        out = self._tconv_out(x, c2, out, "conv_transpose")
+        geom = L.ConvGeom(x.N, out.H, out.W, c2, x.H, x.W, c1, m.k, 2, m.p, out.ld, x.ld, 0)
+        gp = ctypes.byref(geom)
+        st = _stream()
+        L.call("ydl_conv_dgrad", gp, self.dt, _p(x.t), _p(wt), _p(out.t), 0, st)
+        if m.bias is not None:
+            ones, bias = m.bias_coeffs(self.device)
+            L.call_act("ydl_bn_act_fwd", self.dt, _p(out.t), out.ld, _p(ones), _p(bias), None, 0, L.RES_NONE, L.ACT_NONE,
+                       _p(out.t), out.ld, out.npix, round_up(out.C, 8), st)
+        if self.record:
+            if x.need:
+                self._use(x)
+
+            def bw():
+                if not out.is_set():
+                    return
+                st2 = _stream()
+                dy = Var(self, self._gbuf(out), out.ld, False)
+                self._bias_grad(m, dy, st2)
+                m.wgrad(self, gp, dy, x, st2)
+                if x.need:
+                    gx, acc = self.grad_target(x)
+                    L.call("ydl_conv_fwd", gp, self.dt, _p(dy.t), _p(w), _p(gx), None, acc, st2)
+                self._keep.append(geom)
+            self.bw.append(bw)
+        return out
+
+    def dw_conv_transpose(self, x: Var, m, out: Optional[Var] = None) -> Var:
+        """``DWConvTranspose2d`` (models/common.py:73-76), depth-wise at stride 2 in the forms that double the map: the kernels of
+        csrc/tconv.hip read the f32 master [C][k*k] directly and fuse the bias; the weight gradient is deterministic (per-CTA
+        partials merged in a fixed order), the bias gradient comes from ydl_channel_sum."""
+        x = self._flat(x)
+        C, k, p, op = m.in_channels, m.k, m.p, m.op
+        if x.C != C:
+            raise RuntimeError(f"DWConvTranspose2d input channel mismatch: got {x.C}, weight expects {C}")
+        out = self._tconv_out(x, C, out, "dw_conv_transpose")
+        wm = m.master_dw()
+        st = _stream()
+        L.call("ydl_dwtconv_fwd", self.dt, _p(x.t), x.ld, _p(wm), _p(m.bias.detach()) if m.bias is not None else None, _p(out.t), out.ld,
+               x.N, x.H, x.W, C, k, p, op, st)
+        if self.record:
+            if x.need:
+                self._use(x)
+
+            def bw():
+                if not out.is_set():
+                    return
+                st2 = _stream()
+                dy = Var(self, self._gbuf(out), out.ld, False)
+                self._bias_grad(m, dy, st2)
+                if m.weight.requires_grad:
+                    gk = m.grad_dw()
+                    ws = torch.empty(L.lib().ydl_dwtconv_wgrad_ws_bytes(C, k) // 4, dtype=torch.float32, device=self.device)
+                    L.call("ydl_dwtconv_wgrad", self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws), x.N, x.H, x.W, C, k, p, op, st2)
+                    self._keep.append(ws)
+                    from . import config as _cfg
+                    _cfg.mark_touched(m.weight)
+                if x.need:
+                    gx, acc = self.grad_target(x)
+                    L.call("ydl_dwtconv_dgrad", self.dt, _p(dy.t), dy.ld, _p(wm), _p(gx), x.ld, acc, x.N, x.H, x.W, C, k, p, op, st2)
             self.bw.append(bw)
         return out
 
