@@ -16,6 +16,7 @@ from typing import Callable, List, Optional, Sequence
 import torch
 
 from . import _lib as L
+from . import config as _cfg
 
 _DT = {"f32": (L.YDL_F32, torch.float32), "bf16": (L.YDL_BF16, torch.bfloat16)}
 
@@ -51,6 +52,16 @@ def side_stream(device) -> "torch.cuda.Stream":
 
 def _p(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _at(t: torch.Tensor, c0: int) -> ctypes.c_void_p:
+    """``t`` from channel ``c0`` on: a per-channel row, or the (N,C,H,W) view of an NHWC buffer (c fastest)"""
+    return ctypes.c_void_p(t.data_ptr() + c0 * t.element_size())
+
+
+def _bn_part(y: "Var", cf, c0: int):
+    """what the BatchNorm launches of the channel group from ``c0`` on read: y and the mean, invstd, scale and shift rows there"""
+    return [_at(t, c0) for t in (y.t, cf["mean"], cf["invstd"], cf["scale"], cf["shift"])]
 
 
 def stream_wait(waiter: "torch.cuda.Stream", on: "torch.cuda.Stream") -> None:
@@ -291,7 +302,6 @@ class Tape:
         the geometry runs on a kernel that has the fused epilogue.  The producers find (sums, write count) on their output Var and
         skip their own reduce launch if nothing wrote the buffer in between (Tape.conv_bn_act.bw); a wrong guess only wastes the
         epilogue work."""
-        from . import config as _cfg
         if not _cfg.bn_bwd_fuse() or self.dt != L.YDL_BF16:
             return False
         xr = x.root()
@@ -463,7 +473,6 @@ class Tape:
         """queue a weight-gradient launch for the side stream.  One fork (event record + stream wait) per ``wgrad_batch`` launches
         instead of one per layer: forks cost host time in eager mode and a cross-branch edge each in a captured graph.  The last
         layers of the sweep fork at once, so the tail of the backward pass does not wait for a batch to fill."""
-        from . import config as _cfg
         self._pending_wgrad.append(launch)
         self._keep.extend(keep)
         if len(self._pending_wgrad) >= _cfg.wgrad_batch() or self._bw_left <= 2:
@@ -493,7 +502,7 @@ class Tape:
             self._side_used = False
         self._keep.clear()
 
-    # ------------------------------------------------------------------ BatchNorm pieces shared by conv_bn_act and dw_bn_act
+    # ------------------------------------------------------------------ BatchNorm pieces shared by conv_bn_act, _side_bn_act and the bias-only convolutions
     def _bn_coeffs(self, m, cf, C: int, st, part=None) -> None:
         """scale / shift (and in train mode mean / invstd, the running statistics) of ``m.bn`` into ``cf``: from the partial rows
         ``part`` = (ws, rows, block_m, npix, rep) a convolution launch wrote (ydl_bn_finalize), or in eval mode (``part`` None)
@@ -528,6 +537,28 @@ class Tape:
             return None, 0, res_mode
         gbuf, racc = self.grad_target(res)
         return gbuf, res.ld, (res_mode | L.RES_GRAD_ACCUMULATE) if racc else res_mode
+
+    def _bn_apply(self, y: Var, scale: torch.Tensor, shift: torch.Tensor, act: int, out: Var, npix: int, cp: int, st,
+                  res: Optional[Var] = None, res_mode: int = L.RES_NONE, c0: int = 0) -> None:
+        """the apply pass: out = act(y * scale + shift) [+ res] over ``cp`` channels (ydl_bn_act_fwd).  ``c0``: the channel group of
+        ``y`` and of the coefficient rows that starts there (split outputs).  A bias is the scale-1 case, in place (out is y)."""
+        L.call_act("ydl_bn_act_fwd", self.dt, _at(y.t, c0), y.ld, _at(scale, c0), _at(shift, c0), _p(res.t) if res is not None else None,
+                   res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
+
+    def _bn_bwd_rows(self, m, y: Var, cf, act: int, o: Var, res: Optional[Var], res_mode: int, dy: Var, rows, npix: int, cw: int,
+                     cp: int, st, c0: int = 0, touch: bool = True) -> None:
+        """the partial-row BatchNorm backward (ydl_bn_act_bwd) of the ``cw`` channels from ``c0`` on whose activated output is ``o``:
+        fills that channel group of ``dy``, writes (or adds) the residual's gradient and dgamma / dbeta into ``rows`` =
+        _bn_grad_rows(m, .), then reports the BatchNorm parameters (``touch``: a caller with more groups to go does that itself)"""
+        gw, gb, accw = rows
+        dout = self._gbuf(o)
+        dres_t, dres_ld, rmode = self._res_grad(res, res_mode, o, dout)
+        ws = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
+        L.call_act("ydl_bn_act_bwd", self.dt, _at(y.t, c0), y.ld, _p(dout), o.ld, _p(o.t), o.ld, _at(m.bn.weight, c0),
+                   _at(cf["mean"], c0), _at(cf["invstd"], c0), _at(cf["scale"], c0), _at(cf["shift"], c0), rmode, act,
+                   _at(dy.t, c0), dy.ld, _p(dres_t), dres_ld, _at(gw, c0), _at(gb, c0), accw, _p(ws), npix, cw, cp, st)
+        if touch:
+            m.touch_bn()          # dgamma / dbeta kernels are enqueued: the DP hook may now reduce their bucket
 
     # ------------------------------------------------------------------ conv + BN + act (+ residual)
     def conv_bn_act(self, x: Var, m, s: int, p: int, act: int, out=None,
@@ -595,7 +626,6 @@ class Tape:
         w, wt = m.compute_weights(self)
         npix = x.N * Ho * Wo
         cf = m.coeffs(self.device)                   # dict of f32 [Cp] tensors: mean, invstd, scale, shift
-        es = w.element_size()
         Cin_p, Cout_p = round_up(Cin, 8), round_up(Cout, 8)
         if virt is None:
             gkey = (x.N, x.H, x.W, Cin, Cout, k, s, p, x.ld, y.ld, self.dt, L.debug_epoch())
@@ -621,55 +651,10 @@ class Tape:
             geom = subs[-1][3]                       # the launch that writes the BN partials
         gp = ctypes.byref(geom)
 
-        from . import config as _cfg
         sums_mode = self.train and _cfg.bn_sums(self.dname)      # replica sums instead of partial rows + finalize / merge launches
-        fwd_entry = "ydl_conv_fwd_sums" if sums_mode else "ydl_conv_fwd"
-
-        def conv_fwd(ws_ptr):
-            if subs is None:
-                L.call(fwd_entry if ws_ptr is not None else "ydl_conv_fwd", gp, self.dt, _p(x.t), _p(w), _p(y.t), ws_ptr, 0, st)
-                return
-            if sums_mode and ws_ptr is not None and _cfg.resize_last() and sum(1 for e in subs if e[2]) == 1 and len(subs) >= 2:
-                # replica-sums mode: the plain sub-convolutions first (the first one overwrites y, no statistics), the resized
-                # source LAST through ydl_resize_acc_sums — a streaming read-modify-write that also adds the statistics of the sum.
-                # (The other order costs a full write of the resized tensor plus the point-wise kernel's register-layout
-                # read-modify-write with statistics: 42 + 94 us against 48 + ~45 us for the 128-channel 160^2 case of config 2.)
-                first = True
-                for (v, c0_, r_, gv) in subs:
-                    if r_:
-                        continue
-                    wv = ctypes.c_void_p(w.data_ptr() + c0_ * es)
-                    L.call("ydl_conv_fwd", ctypes.byref(gv), self.dt, _p(v.t), wv, _p(y.t), None, 0 if first else 1, st)
-                    first = False
-                for (v, c0_, r_, gv) in subs:
-                    if not r_:
-                        continue
-                    wv = ctypes.c_void_p(w.data_ptr() + c0_ * es)
-                    z = self.new(v.N, Cout, v.H, v.W)
-                    gz = L.ConvGeom(v.N, v.H, v.W, v.C, v.H, v.W, Cout, 1, 1, 0, v.ld, z.ld, Cin_p)
-                    L.call("ydl_conv_fwd", ctypes.byref(gz), self.dt, _p(v.t), wv, _p(z.t), None, 0, st)
-                    L.call("ydl_resize_acc_sums", self.dt, L.RESIZE_BILINEAR, _p(z.t), z.ld, _p(y.t), y.ld, v.N, v.H, v.W, Ho, Wo,
-                           Cout, 0.0, 0.0, ws_ptr, Cout_p, st)
-                return
-            first = True
-            for i, (v, c0_, r_, gv) in enumerate(subs):
-                wv = ctypes.c_void_p(w.data_ptr() + c0_ * es)
-                last = i == len(subs) - 1
-                if r_:
-                    z = self.new(v.N, Cout, v.H, v.W)
-                    gz = L.ConvGeom(v.N, v.H, v.W, v.C, v.H, v.W, Cout, 1, 1, 0, v.ld, z.ld, Cin_p)
-                    L.call("ydl_conv_fwd", ctypes.byref(gz), self.dt, _p(v.t), wv, _p(z.t), None, 0, st)
-                    L.call("ydl_resize_fwd", self.dt, L.RESIZE_BILINEAR, _p(z.t), z.ld, _p(y.t), y.ld, v.N, v.H, v.W, Ho, Wo,
-                           Cout, 0.0, 0.0, st)
-                else:
-                    L.call(fwd_entry if (last and ws_ptr is not None) else "ydl_conv_fwd", ctypes.byref(gv), self.dt, _p(v.t), wv, _p(y.t),
-                           ws_ptr if last else None, 0 if first else 1, st)
-                first = False
-
-        sums = None
+        sums = ws = None
         if sums_mode:
             sums = self.zeroed(L.BN_REPLICAS * 2 * Cout_p)
-            conv_fwd(_p(sums))
         elif self.train:
             if subs is None:
                 nbytes, grid_m, block_m = gc[2], gc[3], gc[4]
@@ -677,26 +662,27 @@ class Tape:
                 nbytes = L.lib().ydl_conv_fwd_stats_ws_bytes(gp, self.dt)
                 grid_m, block_m = L.lib().ydl_conv_fwd_grid_m(gp, self.dt), L.lib().ydl_conv_fwd_block_m(gp, self.dt)
             ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
-            conv_fwd(_p(ws))
-            self._bn_coeffs(m, cf, Cout, st, (ws, grid_m, block_m, npix, rep))
+        ws_ptr = _p(sums if sums_mode else ws) if self.train else None
+        fwd_entry = "ydl_conv_fwd_sums" if sums_mode else "ydl_conv_fwd"
+        if subs is None:
+            L.call(fwd_entry, gp, self.dt, _p(x.t), _p(w), _p(y.t), ws_ptr, 0, st)
         else:
-            conv_fwd(None)
-            self._bn_coeffs(m, cf, Cout, st)
+            self._fwd_split(subs, w, y, Cin_p, ws_ptr, fwd_entry, sums_mode, st)
+        if not sums_mode:
+            self._bn_coeffs(m, cf, Cout, st, (ws, grid_m, block_m, npix, rep) if self.train else None)
         single = len(parts) == 1
         for (co, cw, o) in parts:
             cp = round_up(cw, 8)
-            if sums is not None:
-                # statistics, coefficients (kept for the backward) and running statistics of this channel group in the apply launch
-                L.call_act("ydl_bn_act_fwd_sums", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(sums[co:]), Cout_p, npix,
-                       _p(m.bn.weight[co:]), _p(m.bn.bias[co:]), m.bn.eps, m.bn.momentum, _p(m.bn.running_mean[co:]),
-                       _p(m.bn.running_var[co:]), _p(cf["mean"][co:]), _p(cf["invstd"][co:]), _p(cf["scale"][co:]), _p(cf["shift"][co:]),
-                       rep, _p(res.t) if res is not None else None, res.ld if res is not None else 0, res_mode, act,
-                       _p(o.t), o.ld, npix, cw, cp, st)
+            if sums is None:
+                self._bn_apply(y, cf["scale"], cf["shift"], act, o, npix, cp, st, res, res_mode, c0=co)
                 continue
-            L.call_act("ydl_bn_act_fwd", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld,
-                   _p(cf["scale"][co:]), _p(cf["shift"][co:]),
-                   _p(res.t) if res is not None else None, res.ld if res is not None else 0, res_mode, act,
-                   _p(o.t), o.ld, npix, cp, st)
+            # statistics, coefficients (kept for the backward) and running statistics of this channel group in the apply launch
+            yp, mean, invstd, scale, shift = _bn_part(y, cf, co)
+            bn = m.bn
+            L.call_act("ydl_bn_act_fwd_sums", self.dt, yp, y.ld, _at(sums, co), Cout_p, npix, _at(bn.weight, co), _at(bn.bias, co), bn.eps,
+                       bn.momentum, _at(bn.running_mean, co), _at(bn.running_var, co), mean, invstd, scale, shift, rep,
+                       _p(res.t) if res is not None else None, res.ld if res is not None else 0, res_mode, act,
+                       _p(o.t), o.ld, npix, cw, cp, st)
         ret = outs[0] if single else None
         if not self.record:
             return ret
@@ -723,67 +709,38 @@ class Tape:
                 return                                   # frozen layer on a frozen prefix: nothing upstream wants a gradient
                                                          # (a residual operand that does is served by the BN-backward pass below)
             st2 = _stream()
-            from . import config as _cfg
             if (sums_mode and subs is None and self.dt == L.YDL_BF16 and rep == 1 and act in (L.ACT_NONE, L.ACT_SILU)
                     and train_w and x.need and _cfg.fuse_bn_pw_backward() and _cfg.fuse_pw_backward() and not _cfg.bn_bwd_fuse()
                     and not _cfg.deterministic(self.dname) and all(o.is_set() for (_c, _w, o) in parts)
                     and (single or (len(parts) == 2 and all(cw == 64 for (_c, cw, _o) in parts)))
                     and L.lib().ydl_conv_bwd_pw_bn_supported(gp, self.dt) and getattr(m, "pw_bn_ready", lambda: False)()):
-                # dy has ONE reader, the one-pass 1x1 backward: only the reduce pass is launched (it also serves the residual
-                # operand), ydl_conv_bwd_pw_bn forms dy from y and dout itself and writes dgamma / dbeta; no dy buffer
-                gw, gb, accw = self._bn_grad_rows(m, Cout_p)
-                seg = []
-                for (co, cw, o) in parts:
-                    o.bnred = None
-                    dout = self._gbuf(o)
-                    dres_t, dres_ld, rmode = self._res_grad(res, res_mode, o, dout)
-                    sums_b = self.zeroed(L.BN_REPLICAS * 2 * cw)
-                    L.call_act("ydl_bn_act_bwd_reduce_sums", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(dout), o.ld,
-                           _p(o.t), o.ld, _p(cf["mean"][co:]), _p(cf["invstd"][co:]), _p(cf["scale"][co:]), _p(cf["shift"][co:]),
-                           rmode, act, _p(dres_t), dres_ld, _p(sums_b), npix, cw, cw, st2)
-                    seg.append((dout, o.ld, sums_b))
-                if single:
-                    seg.append((None, 0, None))
-                gx, acc = self.grad_target(x)
-                bn = (_p(y.t), y.ld, _p(seg[0][0]), seg[0][1], _p(seg[1][0]), seg[1][1], _p(cf["mean"]), _p(cf["invstd"]),
-                      _p(cf["scale"]), _p(cf["shift"]), _p(seg[0][2]), _p(seg[1][2]), npix, act, _p(gw), _p(gb), accw, None, 0)
-                m.wgrad(self, gp, x, None, st2, fuse=(_p(wt), _p(gx), x.ld, acc, bn))
-                m.touch_bn()          # after the launch that writes dgamma / dbeta
-                self._keep.append((geom, seg))
+                self._bw_pw_bn(m, x, y, cf, parts, res, res_mode, act, geom, wt, npix, st2)
                 return
             dy = self.new(x.N, Cout, Ho, Wo)
-            gw, gb, accw = self._bn_grad_rows(m, Cout_p)
+            rows = gw, gb, accw = self._bn_grad_rows(m, Cout_p)
             for (co, cw, o) in parts:
                 cp = round_up(cw, 8)
-                dyv = dy.t if single else dy.t[:, co:co + cw]
                 if not o.is_set():                        # this half feeds nothing that reaches the loss
-                    zero_(dyv)
+                    zero_(dy.t if single else dy.t[:, co:co + cw])
+                    continue
+                if not sums_mode:
+                    self._bn_bwd_rows(m, y, cf, act, o, res, res_mode, dy, rows, npix, cw, cp, st2, c0=co, touch=False)
                     continue
                 dout = self._gbuf(o)
                 dres_t, dres_ld, rmode = self._res_grad(res, res_mode, o, dout)
-                if sums_mode:
-                    red = o.bnred
-                    o.bnred = None
-                    if red is not None and self._unwritten_since(o, red[1]):
-                        # the reduce pass ran in the epilogue of the dgrad that wrote dout last (nothing has written since)
-                        entry, sums_b = "ydl_bn_act_bwd_apply_sums", red[0]
-                    else:
-                        entry, sums_b = "ydl_bn_act_bwd_sums", self.zeroed(L.BN_REPLICAS * 2 * cp)
-                    L.call_act(entry, self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(dout), o.ld,
-                           _p(o.t), o.ld, _p(cf["mean"][co:]), _p(cf["invstd"][co:]), _p(cf["scale"][co:]), _p(cf["shift"][co:]),
-                           rmode, act, _p(dyv), dy.ld, _p(dres_t), dres_ld, _p(gw[co:]), _p(gb[co:]), accw,
-                           _p(sums_b), npix, cw, cp, st2)
-                    continue
-                nws = L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4
-                ws2 = torch.empty(nws, dtype=torch.float32, device=self.device)
-                L.call_act("ydl_bn_act_bwd", self.dt, _p(y.t if single else y.t[:, co:co + cw]), y.ld, _p(dout), o.ld,
-                       _p(o.t), o.ld, _p(m.bn.weight[co:]), _p(cf["mean"][co:]), _p(cf["invstd"][co:]),
-                       _p(cf["scale"][co:]), _p(cf["shift"][co:]), rmode, act, _p(dyv), dy.ld, _p(dres_t), dres_ld,
-                       _p(gw[co:]), _p(gb[co:]), accw, _p(ws2), npix, cw, cp, st2)
+                red = o.bnred
+                o.bnred = None
+                if red is not None and self._unwritten_since(o, red[1]):
+                    # the reduce pass ran in the epilogue of the dgrad that wrote dout last (nothing has written since)
+                    entry, sums_b = "ydl_bn_act_bwd_apply_sums", red[0]
+                else:
+                    entry, sums_b = "ydl_bn_act_bwd_sums", self.zeroed(L.BN_REPLICAS * 2 * cp)
+                yp, mean, invstd, scale, shift = _bn_part(y, cf, co)
+                L.call_act(entry, self.dt, yp, y.ld, _p(dout), o.ld, _p(o.t), o.ld, mean, invstd, scale, shift, rmode, act,
+                           _at(dy.t, co), dy.ld, _p(dres_t), dres_ld, _at(gw, co), _at(gb, co), accw, _p(sums_b), npix, cw, cp, st2)
             m.touch_bn()          # dgamma / dbeta kernels are enqueued: the DP hook may now reduce their bucket
             # weight gradient (f32, KRSC) accumulated into the parameter's grad storage; on the side stream when the
             # input gradient is needed too, so wgrad and dgrad of a layer overlap
-            from . import config as _cfg
             if subs is not None:
                 self._bw_split(m, subs, dy, wt, Cout_p, Ho, Wo, st2)
                 return
@@ -831,10 +788,65 @@ class Tape:
         self._conv_shift_fwd(ctypes.byref(geom), x, w, out, lambda _dev: (f["ones"], f["bias"]), _stream(), act, res, res_mode)
         return out
 
+    def _fwd_split(self, subs, w: torch.Tensor, y: Var, Cin_p: int, ws_ptr, fwd_entry: str, sums_mode: bool, st) -> None:
+        """forward of the commuted conv-over-concat into ``y``: per source one 1x1 convolution on its column block of the weight matrix;
+        the resized source runs at its own size and is then resized into y.  Default order: the resize initialises y, the plain
+        sub-convolutions accumulate, the last of them with the statistics (``fwd_entry``, ``ws_ptr``).
+        ``config.resize_last`` in replica-sums mode: the plain sub-convolutions first (the first one overwrites y, no statistics), the
+        resized source LAST through ydl_resize_acc_sums — a streaming read-modify-write that also adds the statistics of the sum.
+        (The default order costs a full write of the resized tensor plus the point-wise kernel's register-layout read-modify-write with
+        statistics: 42 + 94 us against 48 + ~45 us for the 128-channel 160^2 case of config 2.)"""
+        Cout, es = y.C, w.element_size()
+        resize_last = sums_mode and ws_ptr is not None and _cfg.resize_last() and sum(1 for e in subs if e[2]) == 1 and len(subs) >= 2
+        if resize_last:
+            subs = sorted(subs, key=lambda e: e[2])
+        first = True
+        for i, (v, c0_, r_, gv) in enumerate(subs):
+            wv = ctypes.c_void_p(w.data_ptr() + c0_ * es)
+            if r_:
+                z = self.new(v.N, Cout, v.H, v.W)
+                gz = L.ConvGeom(v.N, v.H, v.W, v.C, v.H, v.W, Cout, 1, 1, 0, v.ld, z.ld, Cin_p)
+                L.call("ydl_conv_fwd", ctypes.byref(gz), self.dt, _p(v.t), wv, _p(z.t), None, 0, st)
+                if resize_last:
+                    L.call("ydl_resize_acc_sums", self.dt, L.RESIZE_BILINEAR, _p(z.t), z.ld, _p(y.t), y.ld, v.N, v.H, v.W, y.H, y.W,
+                           Cout, 0.0, 0.0, ws_ptr, round_up(Cout, 8), st)
+                else:
+                    L.call("ydl_resize_fwd", self.dt, L.RESIZE_BILINEAR, _p(z.t), z.ld, _p(y.t), y.ld, v.N, v.H, v.W, y.H, y.W,
+                           Cout, 0.0, 0.0, st)
+            else:
+                stats = ws_ptr is not None and not resize_last and i == len(subs) - 1
+                L.call(fwd_entry if stats else "ydl_conv_fwd", ctypes.byref(gv), self.dt, _p(v.t), wv, _p(y.t),
+                       ws_ptr if stats else None, 0 if first else 1, st)
+            first = False
+
+    def _bw_pw_bn(self, m, x: Var, y: Var, cf, parts, res: Optional[Var], res_mode: int, act: int, geom, wt: torch.Tensor,
+                  npix: int, st2) -> None:
+        """backward of a 1x1 layer whose dy has ONE reader, the one-pass 1x1 backward: only the reduce pass of the BatchNorm backward is
+        launched (it also serves the residual operand), ydl_conv_bwd_pw_bn forms dy from y and dout itself and writes dgamma / dbeta;
+        no dy buffer.  ``parts`` = (channel offset, width, destination) of one output or of two 64-channel halves."""
+        gw, gb, accw = self._bn_grad_rows(m, round_up(y.C, 8))
+        seg = []
+        for (co, cw, o) in parts:
+            o.bnred = None
+            dout = self._gbuf(o)
+            dres_t, dres_ld, rmode = self._res_grad(res, res_mode, o, dout)
+            sums_b = self.zeroed(L.BN_REPLICAS * 2 * cw)
+            yp, mean, invstd, scale, shift = _bn_part(y, cf, co)
+            L.call_act("ydl_bn_act_bwd_reduce_sums", self.dt, yp, y.ld, _p(dout), o.ld, _p(o.t), o.ld, mean, invstd, scale, shift,
+                       rmode, act, _p(dres_t), dres_ld, _p(sums_b), npix, cw, cw, st2)
+            seg.append((dout, o.ld, sums_b))
+        if len(parts) == 1:
+            seg.append((None, 0, None))
+        gx, acc = self.grad_target(x)
+        bn = (_p(y.t), y.ld, _p(seg[0][0]), seg[0][1], _p(seg[1][0]), seg[1][1], _p(cf["mean"]), _p(cf["invstd"]),
+              _p(cf["scale"]), _p(cf["shift"]), _p(seg[0][2]), _p(seg[1][2]), npix, act, _p(gw), _p(gb), accw, None, 0)
+        m.wgrad(self, ctypes.byref(geom), x, None, st2, fuse=(_p(wt), _p(gx), x.ld, acc, bn))
+        m.touch_bn()          # after the launch that writes dgamma / dbeta
+        self._keep.append((geom, seg))
+
     def _bw_split(self, m, subs, dy: Var, wt: torch.Tensor, Cout_p: int, Ho: int, Wo: int, st2) -> None:
         """backward of the commuted conv-over-concat: per source one wgrad into its column block of the weight gradient
         and one dgrad with its row block of wt; the resized source sees d z = bilinear_up^T (dy)."""
-        from . import config as _cfg
         es = wt.element_size()
         jobs = []
         for (v, c0_, r_, gv) in subs:
@@ -930,7 +942,6 @@ class Tape:
                x.N, x.H, x.W, x.C, k, _stream())
         if self.record:
             self._use(x)
-            from . import config as _cfg
             hook = _cfg.sppf_argmax_hook()
             if hook is not None:          # test instrument: read or replace the three arg-max planes the backward will route by
                 hook(idx)
@@ -1103,7 +1114,6 @@ class Tape:
                 gz, acc, ldz = scratch.t, 0, scratch.ld
             L.call("ydl_acon_bwd", self.dt, _p(z.t), z.ld, _p(self._gbuf(out)), out.ld, _p(ps[0]), _p(ps[1]), _p(ps[2]), 0,
                    _p(gz), ldz, acc, _p(g1), _p(g2), _p(gb), 1, _p(ws), z.npix, hw, C, cp, st)
-            from . import config as _cfg
             for p in ps:
                 if p.requires_grad:
                     _cfg.mark_touched(p)
@@ -1144,7 +1154,6 @@ class Tape:
         input's size) — seg_diceloss_yolov5.py:484-507.
         When exactly one source has to be up-sampled and everything is 16-byte aligned the result is VIRTUAL (see
         Var.cat_parts): the typical consumer is a 1x1 convolution, which then never needs the up-sampled tensor."""
-        from . import config as _cfg
         xs = [self.materialize(v) if (v.virtual and v.ext_src is not None) else v for v in xs]
         H, W = xs[0].LH, xs[0].LW
         ups = [v for v in xs if (v.LH, v.LW) != (H, W)]
@@ -1301,42 +1310,51 @@ class Tape:
             x = self.copy(x, self.new(x.N, x.C, x.H, x.W, need=x.need, f32=(x.dt == L.YDL_F32)))
         return x
 
-    def dw_bn_act(self, x: Var, m, s: int, act: int, out: Optional[Var] = None, res: Optional[Var] = None,
-                  res_mode: int = L.RES_NONE) -> Var:
-        """depth-wise Conv+BN+act: out = act(bn(dwconv(x))) [+ res], stride 1 or 2 — the Ghost blocks (models/common.py:67-70,
-        253-279) and the ``dw_conv`` branch of DCNv3 (modules/dcnv3.py:89, :35-39).  The convolution launch writes the BatchNorm
-        partial rows of its own output (ydl_dwconv2_fwd), so train mode goes conv -> ydl_bn_finalize -> ydl_bn_act_fwd with no
-        statistics pass over y.  ``out`` may be a concat slice."""
+    # ------------------------------------------------------------------ depth-wise, grouped and cross Conv + BN + act
+    def _side_bn_act(self, fam, x: Var, m, act: int, out: Optional[Var], res: Optional[Var], res_mode: int) -> Var:
+        """the body that ``dw_bn_act``, ``gconv_bn_act`` and ``xconv_bn_act`` share: out = act(bn(conv(x))) [+ res].  The convolution launch
+        writes the BatchNorm partial rows of its own output, so train mode goes conv -> ydl_bn_finalize -> ydl_bn_act_fwd; the backward
+        is ydl_bn_act_bwd, then the weight and the input gradient on the main stream.  ``fam`` says what differs between the families:
+          who, kind             the method's name and the layer's, for messages
+          Cout, k, s            output channels, taps and stride of the geometry (padding k // 2)
+          size(x) -> Ho, Wo     the output's size
+          weights() -> w, wt    the operands of the forward and of the input gradient
+          refuse(gp)            None, or: false when the kernels do not take the geometry (ydl_last_error says why)
+          stats(gp, npix)       bytes of the statistics workspace and the block height of its partial rows
+          fwd(gp, x, w, y, ws, st), wgrad(gp, x, dy, gk, st), dgrad(gp, x, dy, wt, gx, acc, st)      the three launches
+        ``gp`` is the ConvGeom of the layer by reference (the depth-wise kernels take their sizes as plain arguments instead)."""
+        who, kind, Cout, k, s, size, weights, refuse, stats, fwd, wgrad, dgrad = fam
         x = self._flat(x)
         if res is not None:
             res = self._flat(res)
         if out is not None and not out.aligned():       # the BatchNorm kernels work on 8-channel groups: stage an odd slice
-            return self.copy(self.dw_bn_act(x, m, s, act, None, res, res_mode), out)
-        C, k = m.c1, m.k
-        if x.C != C:
-            raise RuntimeError(f"depth-wise Conv input channel mismatch: got {x.C}, weight expects {C}")
-        Ho = (x.H + 2 * (k // 2) - k) // s + 1
-        Wo = (x.W + 2 * (k // 2) - k) // s + 1
-        y = self.new(x.N, C, Ho, Wo)
+            return self.copy(self._side_bn_act(fam, x, m, act, None, res, res_mode), out)
+        if x.C != m.c1:
+            raise RuntimeError(f"{kind} input channel mismatch: got {x.C}, weight expects {m.c1}")
+        Ho, Wo = size(x)
+        y = self.new(x.N, Cout, Ho, Wo)
         if out is None:
-            out = self.new(x.N, C, Ho, Wo)
-        elif (out.N, out.C, out.H, out.W) != (x.N, C, Ho, Wo):
-            raise RuntimeError("dw_bn_act: output slice has the wrong shape")
+            out = self.new(x.N, Cout, Ho, Wo)
+        elif (out.N, out.C, out.H, out.W) != (x.N, Cout, Ho, Wo):
+            raise RuntimeError(f"{who}: output slice has the wrong shape")
         st = _stream()
-        wm = m.master_dw()                                   # f32 [C][k*k]
+        w, wt = weights()
         cf = m.coeffs(self.device)
         npix = x.N * Ho * Wo
-        cp = round_up(C, 8)
+        cp = round_up(Cout, 8)
+        geom = L.ConvGeom(x.N, x.H, x.W, m.c1, Ho, Wo, Cout, k, s, k // 2, x.ld, y.ld, 0)
+        gp = ctypes.byref(geom)
+        if refuse is not None and not refuse(gp):
+            raise RuntimeError(f"{who}: " + (L.lib().ydl_last_error() or b"?").decode())
         if self.train:
-            ws = torch.empty(L.lib().ydl_bn_stats_ws_bytes(npix, C) // 4, dtype=torch.float32, device=self.device)
-            bm = L.lib().ydl_bn_stats_block_m()
-            L.call("ydl_dwconv2_fwd", self.dt, _p(x.t), x.ld, _p(wm), _p(y.t), y.ld, _p(ws), x.N, x.H, x.W, C, k, s, st)
-            self._bn_coeffs(m, cf, C, st, (ws, (npix + bm - 1) // bm, bm, npix, 1))
+            nbytes, bm = stats(gp, npix)
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+            fwd(gp, x, w, y, _p(ws), st)
+            self._bn_coeffs(m, cf, Cout, st, (ws, (npix + bm - 1) // bm, bm, npix, 1))
         else:
-            L.call("ydl_dwconv2_fwd", self.dt, _p(x.t), x.ld, _p(wm), _p(y.t), y.ld, None, x.N, x.H, x.W, C, k, s, st)
-            self._bn_coeffs(m, cf, C, st)
-        L.call_act("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
-               res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
+            fwd(gp, x, w, y, None, st)
+            self._bn_coeffs(m, cf, Cout, st)
+        self._bn_apply(y, cf["scale"], cf["shift"], act, out, npix, cp, st, res, res_mode)
         if not self.record:
             return out
         if not self.train:
@@ -1345,34 +1363,82 @@ class Tape:
             self._use(x)
         if res is not None and res.need and res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
             self._use(res)
+        self._keep.append(geom)         # the ctypes struct outlives the enqueue
 
         def bw():
             if not out.is_set():
                 return
             st2 = _stream()
-            dy = self.new(x.N, C, Ho, Wo)
-            dout = self._gbuf(out)
-            gw, gb, accw = self._bn_grad_rows(m, cp)
-            dres_t, dres_ld, rmode = self._res_grad(res, res_mode, out, dout)
-            ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
-            L.call_act("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
-                   _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rmode, act,
-                   _p(dy.t), dy.ld, _p(dres_t), dres_ld, _p(gw), _p(gb), accw, _p(ws2), npix, C, cp, st2)
-            m.touch_bn()
+            dy = self.new(x.N, Cout, Ho, Wo)
+            self._bn_bwd_rows(m, y, cf, act, out, res, res_mode, dy, self._bn_grad_rows(m, cp), npix, Cout, cp, st2)
+            gb_ = L.ConvGeom(x.N, x.H, x.W, m.c1, Ho, Wo, Cout, k, s, k // 2, x.ld, dy.ld, 0)     # the same geometry on dy's rows
+            gpb = ctypes.byref(gb_)
+            self._keep.append(gb_)
             if m.trainable()[0]:
-                gk = m.grad_dw()
-                # k = 3 at stride 1 (DCNv3's dw_conv) stays on the stride-1 entry point and its vectorised kernel until
-                # ydl_dwconv2_wgrad has been measured against it at those shapes; its last argument is the padding, 1 like s
-                wg = "ydl_dwconv_wgrad" if (k == 3 and s == 1) else "ydl_dwconv2_wgrad"
-                ws3 = torch.empty(getattr(L.lib(), wg + "_ws_bytes")(C, k) // 4, dtype=torch.float32, device=self.device)
-                L.call(wg, self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws3), x.N, x.H, x.W, C, k, s, st2)
-                from . import config as _cfg
+                wgrad(gpb, x, dy, m.grad_dw(), st2)
                 _cfg.mark_touched(m.conv.weight)
             if x.need:
                 gx, acc = self.grad_target(x)
-                L.call("ydl_dwconv2_dgrad", self.dt, _p(dy.t), dy.ld, _p(wm), _p(gx), x.ld, acc, x.N, x.H, x.W, C, k, s, st2)
+                dgrad(gpb, x, dy, wt, gx, acc, st2)
         self.bw.append(bw)
         return out
+
+    def _geom_family(self, entry: str, arg: int):
+        """refuse, stats, fwd, wgrad, dgrad of ``_side_bn_act`` for the kernels that take a ConvGeom and one more integer (``entry`` =
+        "ydl_gconv" with the group count, "ydl_xconv" with the axis).  They use no atomics: the same launches serve throughput mode and
+        deterministic mode."""
+        lib = L.lib()
+
+        def refuse(gp):
+            return getattr(lib, entry + "_supported")(gp, arg, self.dt)
+
+        def stats(gp, npix):
+            return getattr(lib, entry + "_fwd_stats_ws_bytes")(gp, arg, self.dt), getattr(lib, entry + "_fwd_block_m")(gp, arg, self.dt)
+
+        def fwd(gp, x, w, y, ws, st):
+            L.call(entry + "_fwd", gp, arg, self.dt, _p(x.t), _p(w), _p(y.t), ws, st)
+
+        def wgrad(gp, x, dy, gk, st):                        # gk: KRSC [Cout][taps][Cin / groups], the kernel's dw layout
+            nws = max(getattr(lib, entry + "_wgrad_ws_bytes")(gp, arg, self.dt) // 4, 4)
+            ws = torch.empty(nws, dtype=torch.float32, device=self.device)
+            L.call(entry + "_wgrad", gp, arg, self.dt, _p(x.t), _p(dy.t), _p(gk), _p(ws), st)
+
+        def dgrad(gp, x, dy, wt, gx, acc, st):
+            L.call(entry + "_dgrad", gp, arg, self.dt, _p(dy.t), _p(wt), _p(gx), acc, st)
+        return refuse, stats, fwd, wgrad, dgrad
+
+    def dw_bn_act(self, x: Var, m, s: int, act: int, out: Optional[Var] = None, res: Optional[Var] = None,
+                  res_mode: int = L.RES_NONE) -> Var:
+        """depth-wise Conv+BN+act: out = act(bn(dwconv(x))) [+ res], stride 1 or 2 — the Ghost blocks (models/common.py:67-70,
+        253-279) and the ``dw_conv`` branch of DCNv3 (modules/dcnv3.py:89, :35-39).  The convolution launch writes the BatchNorm
+        partial rows of its own output (ydl_dwconv2_fwd), so train mode goes conv -> ydl_bn_finalize -> ydl_bn_act_fwd with no
+        statistics pass over y.  ``out`` may be a concat slice."""
+        C, k, lib = m.c1, m.k, L.lib()
+
+        def size(x):
+            return (x.H + 2 * (k // 2) - k) // s + 1, (x.W + 2 * (k // 2) - k) // s + 1
+
+        def weights():
+            wm = m.master_dw()                                   # f32 [C][k*k]: both directions read the master
+            return wm, wm
+
+        def stats(gp, npix):
+            return lib.ydl_bn_stats_ws_bytes(npix, C), lib.ydl_bn_stats_block_m()
+
+        def fwd(gp, x, w, y, ws, st):
+            L.call("ydl_dwconv2_fwd", self.dt, _p(x.t), x.ld, _p(w), _p(y.t), y.ld, ws, x.N, x.H, x.W, C, k, s, st)
+
+        def wgrad(gp, x, dy, gk, st):
+            # k = 3 at stride 1 (DCNv3's dw_conv) stays on the stride-1 entry point and its vectorised kernel until
+            # ydl_dwconv2_wgrad has been measured against it at those shapes; its last argument is the padding, 1 like s
+            wg = "ydl_dwconv_wgrad" if (k == 3 and s == 1) else "ydl_dwconv2_wgrad"
+            ws = torch.empty(getattr(lib, wg + "_ws_bytes")(C, k) // 4, dtype=torch.float32, device=self.device)
+            L.call(wg, self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws), x.N, x.H, x.W, C, k, s, st)
+
+        def dgrad(gp, x, dy, wt, gx, acc, st):
+            L.call("ydl_dwconv2_dgrad", self.dt, _p(dy.t), dy.ld, _p(wt), _p(gx), x.ld, acc, x.N, x.H, x.W, C, k, s, st)
+        fam = ("dw_bn_act", "depth-wise Conv", C, k, s, size, weights, None, stats, fwd, wgrad, dgrad)
+        return self._side_bn_act(fam, x, m, act, out, res, res_mode)
 
     def gconv_bn_act(self, x: Var, m, act: int, out: Optional[Var] = None, res: Optional[Var] = None,
                      res_mode: int = L.RES_NONE) -> Var:
@@ -1380,76 +1446,8 @@ class Tape:
         every Conv / Bottleneck / C3 / C2f with g > 1.  One ydl_gconv_fwd launch serves all groups and writes the BatchNorm partial rows
         of its output, so train mode goes conv -> ydl_bn_finalize -> ydl_bn_act_fwd.  The kernels use no atomics: the same launches
         serve throughput mode and deterministic mode.  ``out`` may be a concat slice."""
-        x = self._flat(x)
-        if res is not None:
-            res = self._flat(res)
-        if out is not None and not out.aligned():       # the BatchNorm kernels work on 8-channel groups: stage an odd slice
-            return self.copy(self.gconv_bn_act(x, m, act, None, res, res_mode), out)
-        Cin, Cout, k, G = m.c1, m.c2, m.k, m.groups
-        if x.C != Cin:
-            raise RuntimeError(f"grouped Conv input channel mismatch: got {x.C}, weight expects {Cin}")
-        N, H, W = x.N, x.H, x.W
-        y = self.new(N, Cout, H, W)
-        if out is None:
-            out = self.new(N, Cout, H, W)
-        elif (out.N, out.C, out.H, out.W) != (N, Cout, H, W):
-            raise RuntimeError("gconv_bn_act: output slice has the wrong shape")
-        st = _stream()
-        w, wt = m.gconv_weights(self)
-        cf = m.coeffs(self.device)
-        npix = N * H * W
-        cp = round_up(Cout, 8)
-        geom = L.ConvGeom(N, H, W, Cin, H, W, Cout, k, 1, k // 2, x.ld, y.ld, 0)
-        gp = ctypes.byref(geom)
-        if not L.lib().ydl_gconv_supported(gp, G, self.dt):
-            raise RuntimeError("gconv_bn_act: " + (L.lib().ydl_last_error() or b"?").decode())
-        if self.train:
-            ws = torch.empty(L.lib().ydl_gconv_fwd_stats_ws_bytes(gp, G, self.dt) // 4, dtype=torch.float32, device=self.device)
-            bm = L.lib().ydl_gconv_fwd_block_m(gp, G, self.dt)
-            L.call("ydl_gconv_fwd", gp, G, self.dt, _p(x.t), _p(w), _p(y.t), _p(ws), st)
-            self._bn_coeffs(m, cf, Cout, st, (ws, (npix + bm - 1) // bm, bm, npix, 1))
-        else:
-            L.call("ydl_gconv_fwd", gp, G, self.dt, _p(x.t), _p(w), _p(y.t), None, st)
-            self._bn_coeffs(m, cf, Cout, st)
-        L.call_act("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
-               res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
-        if not self.record:
-            return out
-        if not self.train:
-            raise RuntimeError("backward through eval-mode BatchNorm is not supported")
-        if x.need:
-            self._use(x)
-        if res is not None and res.need and res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
-            self._use(res)
-        self._keep.append(geom)
-
-        def bw():
-            if not out.is_set():
-                return
-            st2 = _stream()
-            dy = self.new(N, Cout, H, W)
-            dout = self._gbuf(out)
-            gw, gb, accw = self._bn_grad_rows(m, cp)
-            dres_t, dres_ld, rmode = self._res_grad(res, res_mode, out, dout)
-            ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
-            L.call_act("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
-                   _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rmode, act,
-                   _p(dy.t), dy.ld, _p(dres_t), dres_ld, _p(gw), _p(gb), accw, _p(ws2), npix, Cout, cp, st2)
-            m.touch_bn()
-            gb_ = L.ConvGeom(N, H, W, Cin, H, W, Cout, k, 1, k // 2, x.ld, dy.ld, 0)
-            gpb = ctypes.byref(gb_)
-            self._keep.append(gb_)
-            if m.trainable()[0]:
-                gk = m.grad_dw()                                 # KRSC [Cout][k*k][Cin/groups]: the kernel's dw layout
-                ws3 = torch.empty(max(L.lib().ydl_gconv_wgrad_ws_bytes(gpb, G, self.dt) // 4, 4), dtype=torch.float32, device=self.device)
-                L.call("ydl_gconv_wgrad", gpb, G, self.dt, _p(x.t), _p(dy.t), _p(gk), _p(ws3), st2)
-                from . import config as _cfg
-                _cfg.mark_touched(m.conv.weight)
-            if x.need:
-                gx, acc = self.grad_target(x)
-                L.call("ydl_gconv_dgrad", gpb, G, self.dt, _p(dy.t), _p(wt), _p(gx), acc, st2)
-        self.bw.append(bw)
-        return out
+        fam = ("gconv_bn_act", "grouped Conv", m.c2, m.k, 1, lambda x: (x.H, x.W), lambda: m.gconv_weights(self))
+        return self._side_bn_act(fam + self._geom_family("ydl_gconv", m.groups), x, m, act, out, res, res_mode)
 
     def xconv_bn_act(self, x: Var, m, act: int, out: Optional[Var] = None, res: Optional[Var] = None,
                      res_mode: int = L.RES_NONE) -> Var:
@@ -1457,78 +1455,14 @@ class Tape:
         two convolutions of CrossConv (models/common.py:147-158).  ydl_xconv_fwd writes the BatchNorm partial rows of its output, so
         train mode goes conv -> ydl_bn_finalize -> ydl_bn_act_fwd.  The kernels use no atomics: the same launches serve throughput
         mode and deterministic mode.  ``out`` may be a concat slice."""
-        x = self._flat(x)
-        if res is not None:
-            res = self._flat(res)
-        if out is not None and not out.aligned():       # the BatchNorm kernels work on 8-channel groups: stage an odd slice
-            return self.copy(self.xconv_bn_act(x, m, act, None, res, res_mode), out)
-        Cin, Cout, k, s, ax = m.c1, m.c2, m.k, m.s, m.axis
-        if x.C != Cin:
-            raise RuntimeError(f"cross Conv input channel mismatch: got {x.C}, weight expects {Cin}")
-        N, H, W = x.N, x.H, x.W
-        Ho = (H + 2 * (k // 2) - k) // s + 1 if ax == L.AXIS_H else H
-        Wo = (W + 2 * (k // 2) - k) // s + 1 if ax == L.AXIS_W else W
-        y = self.new(N, Cout, Ho, Wo)
-        if out is None:
-            out = self.new(N, Cout, Ho, Wo)
-        elif (out.N, out.C, out.H, out.W) != (N, Cout, Ho, Wo):
-            raise RuntimeError("xconv_bn_act: output slice has the wrong shape")
-        st = _stream()
-        w, wt = m.compute_weights(self)                 # [Cout][k][Cin] and [Cin][k][Cout]: ydl_weight_prep with kk = k
-        cf = m.coeffs(self.device)
-        npix = N * Ho * Wo
-        cp = round_up(Cout, 8)
-        geom = L.ConvGeom(N, H, W, Cin, Ho, Wo, Cout, k, s, k // 2, x.ld, y.ld, 0)
-        gp = ctypes.byref(geom)
-        if not L.lib().ydl_xconv_supported(gp, ax, self.dt):
-            raise RuntimeError("xconv_bn_act: " + (L.lib().ydl_last_error() or b"?").decode())
-        if self.train:
-            ws = torch.empty(L.lib().ydl_xconv_fwd_stats_ws_bytes(gp, ax, self.dt) // 4, dtype=torch.float32, device=self.device)
-            bm = L.lib().ydl_xconv_fwd_block_m(gp, ax, self.dt)
-            L.call("ydl_xconv_fwd", gp, ax, self.dt, _p(x.t), _p(w), _p(y.t), _p(ws), st)
-            self._bn_coeffs(m, cf, Cout, st, (ws, (npix + bm - 1) // bm, bm, npix, 1))
-        else:
-            L.call("ydl_xconv_fwd", gp, ax, self.dt, _p(x.t), _p(w), _p(y.t), None, st)
-            self._bn_coeffs(m, cf, Cout, st)
-        L.call_act("ydl_bn_act_fwd", self.dt, _p(y.t), y.ld, _p(cf["scale"]), _p(cf["shift"]), _p(res.t) if res is not None else None,
-               res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, npix, cp, st)
-        if not self.record:
-            return out
-        if not self.train:
-            raise RuntimeError("backward through eval-mode BatchNorm is not supported")
-        if x.need:
-            self._use(x)
-        if res is not None and res.need and res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
-            self._use(res)
-        self._keep.append(geom)
+        k, s, ax = m.k, m.s, m.axis
 
-        def bw():
-            if not out.is_set():
-                return
-            st2 = _stream()
-            dy = self.new(N, Cout, Ho, Wo)
-            dout = self._gbuf(out)
-            gw, gb, accw = self._bn_grad_rows(m, cp)
-            dres_t, dres_ld, rmode = self._res_grad(res, res_mode, out, dout)
-            ws2 = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
-            L.call_act("ydl_bn_act_bwd", self.dt, _p(y.t), y.ld, _p(dout), out.ld, _p(out.t), out.ld,
-                   _p(m.bn.weight), _p(cf["mean"]), _p(cf["invstd"]), _p(cf["scale"]), _p(cf["shift"]), rmode, act,
-                   _p(dy.t), dy.ld, _p(dres_t), dres_ld, _p(gw), _p(gb), accw, _p(ws2), npix, Cout, cp, st2)
-            m.touch_bn()
-            gb_ = L.ConvGeom(N, H, W, Cin, Ho, Wo, Cout, k, s, k // 2, x.ld, dy.ld, 0)
-            gpb = ctypes.byref(gb_)
-            self._keep.append(gb_)
-            if m.trainable()[0]:
-                gk = m.grad_dw()                                 # KRSC [Cout][k][Cin]: the kernel's dw layout
-                ws3 = torch.empty(max(L.lib().ydl_xconv_wgrad_ws_bytes(gpb, ax, self.dt) // 4, 4), dtype=torch.float32, device=self.device)
-                L.call("ydl_xconv_wgrad", gpb, ax, self.dt, _p(x.t), _p(dy.t), _p(gk), _p(ws3), st2)
-                from . import config as _cfg
-                _cfg.mark_touched(m.conv.weight)
-            if x.need:
-                gx, acc = self.grad_target(x)
-                L.call("ydl_xconv_dgrad", gpb, ax, self.dt, _p(dy.t), _p(wt), _p(gx), acc, st2)
-        self.bw.append(bw)
-        return out
+        def size(x):
+            Ho, Wo = ((n + 2 * (k // 2) - k) // s + 1 for n in (x.H, x.W))
+            return (Ho if ax == L.AXIS_H else x.H), (Wo if ax == L.AXIS_W else x.W)
+        # weights: [Cout][k][Cin] and [Cin][k][Cout], ydl_weight_prep with kk = k
+        fam = ("xconv_bn_act", "cross Conv", m.c2, k, s, size, lambda: m.compute_weights(self))
+        return self._side_bn_act(fam + self._geom_family("ydl_xconv", ax), x, m, act, out, res, res_mode)
 
     def group_softmax(self, x: Var, G: int, P: int) -> Var:
         """softmax over the P sampling points of each group (modules/dcnv3.py:122-123)"""
@@ -1588,18 +1522,14 @@ class Tape:
         L.call("ydl_conv_fwd", gp, self.dt, _p(x.t), _p(w), _p(out.t), None, 0, st)
         if shift is not None:
             ones, bias = shift(self.device)
-            L.call_act("ydl_bn_act_fwd", self.dt, _p(out.t), out.ld, _p(ones), _p(bias), _p(res.t) if res is not None else None,
-                   res.ld if res is not None else 0, res_mode, act, _p(out.t), out.ld, out.npix, round_up(out.C, 8), st)
+            self._bn_apply(out, ones, bias, act, out, out.npix, round_up(out.C, 8), st, res, res_mode)
 
     def _conv_bias_bwd(self, m, gp, x: Var, dy: Var, wt: torch.Tensor, st) -> None:
         """backward of out = conv(x, m.weight) + m.bias from dy = d out: the bias gradient (ydl_channel_sum), the weight gradient,
         and the input gradient added into d x"""
         if m.bias is not None and m.bias.requires_grad:
-            ws = torch.empty(L.lib().ydl_channel_sum_ws_bytes(dy.C) // 4, dtype=torch.float32, device=self.device)
-            L.call("ydl_channel_sum", self.dt, _p(dy.t), dy.ld, _p(m._grad_of(m.bias)), _p(ws), dy.npix, dy.C, 1, st)
-            if m.final:                  # a row block of a shared parameter reports it once, after its last writer
-                from . import config as _cfg
-                _cfg.mark_touched(m.bias)
+            # a row block of a shared parameter reports it once, after its last writer
+            self._channel_sum_grad(dy, m._grad_of(m.bias), m.bias if m.final else None, st)
         m.wgrad(self, gp, x, dy, st)
         if x.need:
             gx, acc = self.grad_target(x)
@@ -1645,11 +1575,15 @@ class Tape:
             return
         if m.bias.grad is None:
             m.bias.grad = torch.zeros_like(m.bias)
+        self._channel_sum_grad(dy, m.bias.grad, m.bias, st)
+
+    def _channel_sum_grad(self, dy: Var, grad: torch.Tensor, param, st) -> None:
+        """grad += the per-channel sums of dy (ydl_channel_sum); ``param``: the parameter to report as written, or None"""
         ws = torch.empty(L.lib().ydl_channel_sum_ws_bytes(dy.C) // 4, dtype=torch.float32, device=self.device)
-        L.call("ydl_channel_sum", self.dt, _p(dy.t), dy.ld, _p(m.bias.grad), _p(ws), dy.npix, dy.C, 1, st)
+        L.call("ydl_channel_sum", self.dt, _p(dy.t), dy.ld, _p(grad), _p(ws), dy.npix, dy.C, 1, st)
         self._keep.append(ws)
-        from . import config as _cfg
-        _cfg.mark_touched(m.bias)
+        if param is not None:
+            _cfg.mark_touched(param)
 
     def _tconv_out(self, x: Var, C2: int, out: Optional[Var], who: str) -> Var:
         if out is None:
@@ -1679,8 +1613,7 @@ class Tape:
         L.call("ydl_conv_dgrad", gp, self.dt, _p(x.t), _p(wt), _p(out.t), 0, st)
         if m.bias is not None:
             ones, bias = m.bias_coeffs(self.device)
-            L.call_act("ydl_bn_act_fwd", self.dt, _p(out.t), out.ld, _p(ones), _p(bias), None, 0, L.RES_NONE, L.ACT_NONE,
-                       _p(out.t), out.ld, out.npix, round_up(out.C, 8), st)
+            self._bn_apply(out, ones, bias, L.ACT_NONE, out, out.npix, round_up(out.C, 8), st)
         if self.record:
             if x.need:
                 self._use(x)
@@ -1727,7 +1660,6 @@ class Tape:
                     ws = torch.empty(L.lib().ydl_dwtconv_wgrad_ws_bytes(C, k) // 4, dtype=torch.float32, device=self.device)
                     L.call("ydl_dwtconv_wgrad", self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws), x.N, x.H, x.W, C, k, p, op, st2)
                     self._keep.append(ws)
-                    from . import config as _cfg
                     _cfg.mark_touched(m.weight)
                 if x.need:
                     gx, acc = self.grad_target(x)
@@ -1887,7 +1819,6 @@ class Tape:
             def bw():
                 if not out.is_set():
                     return
-                from . import config as _cfg
                 st2 = _stream()
                 dqkv = self.new(N, len(projs) * Cp, H, W, need=False, zero=(Cp != C))
                 dbase = dqkv.t.data_ptr()
