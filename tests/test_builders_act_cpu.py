@@ -14,6 +14,8 @@ import re
 import numpy as np
 import pytest
 
+from tests.block_harness import check_state_dict_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "act_*.npz")))
@@ -56,12 +58,7 @@ def test_the_fixtures_are_present_small_and_carry_the_floors():
 
 @pytest.mark.parametrize("path", FILES, ids=lambda p: os.path.basename(p)[:-4])
 def test_state_dict_matches_the_reference_modules(path):
-    import torch
-    z = np.load(path)
-    mod = build(z)
-    want = [(str(k), tuple(z["p." + str(k)].shape)) for k in z["keys"]]
-    assert [(k, tuple(v.shape)) for k, v in mod.state_dict().items()] == want
-    mod.load_state_dict({k: torch.from_numpy(z["p." + k]).to(mod.state_dict()[k].dtype) for k, _ in want})
+    check_state_dict_layout(path, build)
 
 
 def test_activation_classes_have_the_reference_surface():

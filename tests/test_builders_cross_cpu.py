@@ -6,11 +6,12 @@ library's host-side queries ``ydl_xconv_supported`` / ``_fwd_block_m`` / ``_fwd_
 line as the constructor."""
 import ctypes
 import glob
-import json
 import os
 
 import numpy as np
 import pytest
+
+from tests.block_harness import build_from_json as build, check_state_dict_layout
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "cross_*.npz")))
@@ -29,12 +30,6 @@ CASES = [((16, 24, (1, 3), (1, 1), None), True), ((16, 16, (5, 1), (2, 1), None)
          ((16, 16, (3, 1), (1, 1), (0, 0)), False)]
 
 
-def build(z):
-    """the module a fixture describes (weights not loaded); JSON turned the kernel and stride pairs into lists"""
-    import yolo_dual_amd as ydl
-    return getattr(ydl, str(z["cls"]))(*json.loads(str(z["args"])))
-
-
 def test_the_five_fixtures_are_present_small_and_carry_the_floors():
     assert [os.path.basename(f)[:-4] for f in FILES] == NAMES
     assert all(os.path.getsize(f) < (1 << 20) for f in FILES)
@@ -49,11 +44,7 @@ def test_the_five_fixtures_are_present_small_and_carry_the_floors():
 @pytest.mark.parametrize("path", FILES, ids=lambda p: os.path.basename(p)[:-4])
 def test_state_dict_matches_the_reference_modules(path):
     import torch
-    z = np.load(path)
-    mod = build(z)
-    want = [(str(k), tuple(z["p." + str(k)].shape)) for k in z["keys"]]
-    assert [(k, tuple(v.shape)) for k, v in mod.state_dict().items()] == want
-    mod.load_state_dict({k: torch.from_numpy(z["p." + k]).to(mod.state_dict()[k].dtype) for k, _ in want})
+    _z, mod, _want = check_state_dict_layout(path, build)
     for m in mod.modules():                                 # loading leaves the KRSC master in place
         if isinstance(m, torch.nn.Conv2d):
             assert m.weight.permute(0, 2, 3, 1).is_contiguous()

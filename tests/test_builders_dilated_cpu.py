@@ -3,11 +3,11 @@ reference's constructor signatures and state_dict layout (key lists and shapes r
 tools/make_dilated_golden.py), ``parse_model`` resolves the ASPP and RFB rows (models/yolo.py:317-326: width gain on c2), and the
 constructors refuse what the HIP path does not implement."""
 import glob
-import json
 import os
 
-import numpy as np
 import pytest
+
+from tests.block_harness import build_from_json as build, check_state_dict_layout
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "dil_*.npz")))
@@ -20,12 +20,6 @@ YAML = {"nc": 12, "width_multiple": 0.5, "depth_multiple": 0.33,
         "head": [[-1, 1, "ASPP", [12]]]}
 
 
-def build(z):
-    """the module a fixture describes (weights not loaded)"""
-    import yolo_dual_amd as ydl
-    return getattr(ydl, str(z["cls"]))(*json.loads(str(z["args"])))
-
-
 def test_the_four_fixtures_are_present():
     assert [os.path.basename(f) for f in FILES] == ["dil_aspp_16_8.npz", "dil_basic_12_16_d3.npz", "dil_conv_16_24_d2.npz",
                                                     "dil_rfb_64_32.npz"]
@@ -34,11 +28,7 @@ def test_the_four_fixtures_are_present():
 @pytest.mark.parametrize("path", FILES, ids=lambda p: os.path.basename(p)[:-4])
 def test_state_dict_matches_the_reference_modules(path):
     import torch
-    z = np.load(path)
-    mod = build(z)
-    want = [(str(k), tuple(z["p." + str(k)].shape)) for k in z["keys"]]
-    assert [(k, tuple(v.shape)) for k, v in mod.state_dict().items()] == want
-    mod.load_state_dict({k: torch.from_numpy(z["p." + k]).to(mod.state_dict()[k].dtype) for k, _ in want})
+    _z, mod, _want = check_state_dict_layout(path, build)
     dil = [m for m in mod.modules() if isinstance(m, torch.nn.Conv2d) and m.dilation[0] > 1]
     assert dil and all(m.padding == m.dilation and m.weight.shape[2:] == (3, 3) for m in dil)
     for m in dil:                                   # KRSC master: the weight of the 1x1 GEMM over the column buffer as it is

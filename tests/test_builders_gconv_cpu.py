@@ -5,11 +5,12 @@ resolves the row, Bottleneck / C3 hand their ``g`` through, everything outside t
 query ``ydl_gconv_supported`` draws the same line as the constructor."""
 import ctypes
 import glob
-import json
 import os
 
 import numpy as np
 import pytest
+
+from tests.block_harness import build_from_json as build, check_state_dict_layout
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "gconv_*.npz")))
@@ -26,12 +27,6 @@ CASES = [((32, 96, 3, 1, None, 2), True), ((64, 64, 1, 1, None, 4), True), ((256
          ((8, 16, 3, 1, None, 4), False), ((32, 32, 3, 1, 0, 2), False)]
 
 
-def build(z):
-    """the module a fixture describes (weights not loaded)"""
-    import yolo_dual_amd as ydl
-    return getattr(ydl, str(z["cls"]))(*json.loads(str(z["args"])))
-
-
 def test_the_two_fixtures_are_present_and_small():
     assert [os.path.basename(f) for f in FILES] == ["gconv_conv_32_96_g2_k3.npz", "gconv_sppcspc_group_64_64.npz"]
     assert all(os.path.getsize(f) < (1 << 20) for f in FILES)
@@ -40,12 +35,7 @@ def test_the_two_fixtures_are_present_and_small():
 
 @pytest.mark.parametrize("path", FILES, ids=lambda p: os.path.basename(p)[:-4])
 def test_state_dict_matches_the_reference_modules(path):
-    import torch
-    z = np.load(path)
-    mod = build(z)
-    want = [(str(k), tuple(z["p." + str(k)].shape)) for k in z["keys"]]
-    assert [(k, tuple(v.shape)) for k, v in mod.state_dict().items()] == want
-    mod.load_state_dict({k: torch.from_numpy(z["p." + k]).to(mod.state_dict()[k].dtype) for k, _ in want})
+    check_state_dict_layout(path, build)
 
 
 def test_constructor_forms():

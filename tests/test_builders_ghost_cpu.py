@@ -6,8 +6,9 @@ reference's does (utils/torch_utils.py:318-333)."""
 import glob
 import os
 
-import numpy as np
 import pytest
+
+from tests.block_harness import check_state_dict_layout
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "ghost_*.npz")))
@@ -33,12 +34,7 @@ def test_the_six_fixtures_are_present():
 
 @pytest.mark.parametrize("path", FILES, ids=lambda p: os.path.basename(p)[:-4])
 def test_state_dict_matches_the_reference_modules(path):
-    import torch
-    z = np.load(path)
-    mod = build(z)
-    want = [(str(k), tuple(z["p." + str(k)].shape)) for k in z["keys"]]
-    assert [(k, tuple(v.shape)) for k, v in mod.state_dict().items()] == want
-    mod.load_state_dict({k: torch.from_numpy(z["p." + k]).to(mod.state_dict()[k].dtype) for k, _ in want})
+    _z, _mod, want = check_state_dict_layout(path, build)
     dw = [k for k, s in want if k.endswith("conv.weight") and len(s) == 4 and s[1] == 1 and s[0] > 1]
     assert dw, "every Ghost fixture holds at least one depth-wise weight [C,1,k,k]"
 

@@ -3,11 +3,12 @@
 reference's own classes by tools/make_spp_golden.py), ``parse_model`` resolves the rows (models/yolo.py:317-326: width gain on c2, no
 ``n`` inserted, a yaml list passed through as ``k``), and the constructors refuse what the HIP path does not implement."""
 import glob
-import json
 import os
 
 import numpy as np
 import pytest
+
+from tests.block_harness import build_from_json as build, check_state_dict_layout
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "spp_*.npz")))
@@ -17,12 +18,6 @@ YAML = {"nc": 12, "width_multiple": 0.5, "depth_multiple": 0.33,
         "backbone": [[-1, 1, "Conv", [32, 6, 2, 2]], [-1, 1, "Conv", [64, 3, 2]], [-1, 1, "SPP", [64]], [-1, 1, "SPPCSPC", [64]],
                      [-1, 1, "SimSPPF", [64, 5]], [-1, 1, "SimCSPSPPF", [64]], [-1, 1, "C3SPP", [64, [3, 5]]]],
         "head": [[-1, 1, "Conv", [12, 1, 1]]]}
-
-
-def build(z):
-    """the module a fixture describes (weights not loaded)"""
-    import yolo_dual_amd as ydl
-    return getattr(ydl, str(z["cls"]))(*json.loads(str(z["args"])))
 
 
 def test_the_five_fixtures_are_present_and_small():
@@ -38,12 +33,7 @@ def test_the_five_fixtures_are_present_and_small():
 
 @pytest.mark.parametrize("path", FILES, ids=lambda p: os.path.basename(p)[:-4])
 def test_state_dict_matches_the_reference_modules(path):
-    import torch
-    z = np.load(path)
-    mod = build(z)
-    want = [(str(k), tuple(z["p." + str(k)].shape)) for k in z["keys"]]
-    assert [(k, tuple(v.shape)) for k, v in mod.state_dict().items()] == want
-    mod.load_state_dict({k: torch.from_numpy(z["p." + k]).to(mod.state_dict()[k].dtype) for k, _ in want})
+    check_state_dict_layout(path, build)
 
 
 def test_constructor_forms():

@@ -9,13 +9,13 @@
 * the small yaml model of tests/test_builders_cross_cpu.py (a CrossConv down-sampler, then a C3x with two CrossConvs and shortcuts)
   takes a full eager training step in bf16 and in f32 at a 32^2 input, every parameter touched and moved;
 * in deterministic f32 mode five steps replayed from the launch list leave the same losses and state as the eager steps, bit for
-  bit (the pattern of tests/test_gpu_gconv_blocks.py): the new entry points are in the replay table."""
+  bit (tests/block_harness.py): the new entry points are in the replay table."""
 import os
 
-import numpy as np
 import pytest
 import torch
 
+from tests.block_harness import check_bf16_against_floor, check_f32_fixture, check_replay_equals_eager, eager_step_checks, train_setup
 from tests.test_builders_cross_cpu import FILES, YAML, build
 
 pytestmark = pytest.mark.gpu
@@ -23,99 +23,18 @@ pytestmark = pytest.mark.gpu
 FLOOR_FACTOR = 4.0
 
 
-def _err(got, want):
-    want = torch.as_tensor(want).double()
-    scale = float(want.abs().max())
-    return float((got.detach().double().cpu() - want).abs().max()) / (scale if scale > 0 else 1.0)
-
-
-def _module(z):
-    mod = build(z)
-    sd = mod.state_dict()
-    mod.load_state_dict({str(k): torch.from_numpy(z["p." + str(k)]).to(sd[str(k)].dtype) for k in z["keys"]})
-    return mod.cuda().train()
-
-
-def _step(z):
-    """one train-mode forward + backward of the fixture's module -> (module, x, out, errors by tensor)"""
-    mod = _module(z)
-    x = torch.from_numpy(z["x"]).float().cuda().requires_grad_(True)
-    out = mod(x)
-    assert tuple(out.shape) == tuple(z["out"].shape)
-    out.backward(torch.from_numpy(z["grad_out"]).float().cuda())
-    torch.cuda.synchronize()
-    errs = {"out": _err(out, z["out"]), "grad_x": _err(x.grad, z["grad_x"])}
-    for k, p in mod.named_parameters():
-        assert p.grad is not None, k
-        errs["g." + k] = _err(p.grad, z["g." + k])
-    sd = mod.state_dict()
-    for k in z.files:
-        if k.startswith("rm.") or k.startswith("rv."):
-            errs[k] = _err(sd[k[3:]], z[k])
-    return mod, x, out, errs
-
-
 @pytest.mark.parametrize("path", FILES, ids=[os.path.basename(f)[:-4] for f in FILES])
 def test_modules_match_the_reference_fixtures(path):
-    import yolo_dual_amd as ydl
-    ydl.set_compute_dtype("f32")
-    try:
-        z = np.load(path)
-        mod, x, out, errs = _step(z)
-        print(os.path.basename(path), {k: f"{v:.1e}" for k, v in errs.items()})
-        assert any(k.startswith("rv.") for k in errs)
-        assert all(v < 1e-4 for v in errs.values()), {k: v for k, v in errs.items() if not v < 1e-4}
-        # eval mode: the forward runs on the running statistics and records nothing
-        before = {k: v.detach().clone() for k, v in mod.state_dict().items()}
-        mod.eval()
-        with torch.no_grad():
-            out_eval = mod(x.detach())
-        torch.cuda.synchronize()
-        assert out_eval.shape == out.shape and bool(torch.isfinite(out_eval).all()) and out_eval.grad_fn is None
-        for k, v in mod.state_dict().items():
-            assert torch.equal(v, before[k]), k
-    finally:
-        ydl.set_compute_dtype("bf16")
-
-
-def _kind(k):
-    return "out" if k == "out" else "run" if k[:3] in ("rm.", "rv.") else "grad"
+    check_f32_fixture(path, build)
 
 
 @pytest.mark.parametrize("path", FILES, ids=[os.path.basename(f)[:-4] for f in FILES])
 def test_bf16_mode_against_the_fixtures(path):
-    import yolo_dual_amd as ydl
-    ydl.set_compute_dtype("bf16")
-    z = np.load(path)
-    name = os.path.basename(path)[:-4]
-    floor = {k: float(z["floor." + k]) for k in ("out", "grad", "run")}
-    _mod, _x, _out, errs = _step(z)
-    worst = {"out": (0.0, ""), "grad": (0.0, ""), "run": (0.0, "")}
-    for k, v in errs.items():
-        worst[_kind(k)] = max(worst[_kind(k)], (v, k))
-    print("[cross bf16]", name, {k: f"{v:.2e} ({w}) floor {floor[k]:.2e} ratio {v / floor[k]:.2f}" for k, (v, w) in worst.items()})
-    bad = {k: (v, FLOOR_FACTOR * floor[_kind(k)]) for k, v in errs.items() if not v < FLOOR_FACTOR * floor[_kind(k)]}
-    assert not bad, bad
+    check_bf16_against_floor(path, build, FLOOR_FACTOR, ("out", "grad", "run"), "cross")
 
 
 def _setup(mode):
-    import yolo_dual_amd as ydl
-    ydl.set_compute_dtype(mode)
-    torch.manual_seed(11)
-    m = ydl.SegYoloModel(YAML).cuda().train()
-    opt = ydl.smart_optimizer(m, "SGD", lr=0.01, momentum=0.937, decay=5e-4)
-    crit = ydl.SegmentationLoss(12, 0.0, torch.ones(12), "dice", sync=False)
-    gen = torch.Generator("cuda").manual_seed(3)
-    xs = [torch.rand(2, 3, 32, 32, device="cuda", generator=gen) for _ in range(2)]
-    ts = [torch.randint(0, 12, (2, 8, 8), device="cuda", generator=gen) for _ in range(2)]
-    return m, opt, crit, xs, ts
-
-
-def _state(m, opt):
-    out = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    out["__momentum"] = opt.mom_arena.detach().clone()
-    out["__ema"] = opt.ema_arena.detach().clone()
-    return out
+    return train_setup(YAML, mode, 8)
 
 
 @pytest.mark.parametrize("mode", ["bf16", "f32"])
@@ -123,18 +42,7 @@ def test_yaml_model_takes_a_full_eager_step(mode):
     import yolo_dual_amd as ydl
     try:
         m, opt, crit, xs, ts = _setup(mode)
-        before = _state(m, opt)
-        opt.zero_grad()
-        out = m(xs[0])
-        assert out.shape == (2, 12, 8, 8)
-        total, items = crit(out, ts[0])
-        total.backward()
-        params = dict(m.named_parameters())
-        assert all(getattr(p, "_ydl_touched", False) for p in params.values()), [k for k, p in params.items() if not p._ydl_touched]
-        opt.step()
-        torch.cuda.synchronize()
-        assert bool(torch.isfinite(total)) and bool(torch.isfinite(opt.params_arena).all())
-        after = _state(m, opt)
+        params, before, after = eager_step_checks(m, opt, crit, xs, ts, (2, 12, 8, 8))
         for k in params:                                   # the fused optimizer step moved every parameter
             assert not torch.equal(before[k], after[k]), k
         for w in (m.model[1].cv1.conv.weight, m.model[2].m[1].cv2.conv.weight):
@@ -145,49 +53,4 @@ def test_yaml_model_takes_a_full_eager_step(mode):
 
 
 def test_replayed_step_equals_the_eager_step_bit_for_bit():
-    import yolo_dual_amd as ydl
-    from yolo_dual_amd import config
-    from yolo_dual_amd.replay import ReplayedTrainStep
-    config.set_deterministic(True)
-    try:
-        res = {}
-        for how in ("eager", "replay"):
-            m, opt, crit, xs, ts = _setup("f32")
-            x, t = xs[0].clone(), ts[0].clone()
-            losses = []
-            if how == "eager":
-                for st in range(5):
-                    x.copy_(xs[st % 2]); t.copy_(ts[st % 2])
-                    opt.zero_grad()
-                    total, items = crit(m(x), t)
-                    total.backward()
-                    opt.step()
-                    losses.append(float(items[0]))
-            else:
-                step_no = [0]
-
-                def pre(_mod, _inp):
-                    i = step_no[0]
-                    x.copy_(xs[i % 2]); t.copy_(ts[i % 2])
-                    step_no[0] += 1
-                h = m.register_forward_pre_hook(pre)
-                r = ReplayedTrainStep(m, crit, opt, x, t, warmup=2)
-                h.remove()
-                assert step_no[0] == 3
-                for fn in ("ydl_xconv_fwd", "ydl_xconv_dgrad", "ydl_xconv_wgrad"):
-                    assert r.rec.fn.get(fn) is not None, fn
-                losses = [None, None, float(r.loss_items[0])]
-                r.poison()
-                for st in range(3, 5):
-                    x.copy_(xs[st % 2]); t.copy_(ts[st % 2])
-                    losses.append(float(r.step()[0]))
-            torch.cuda.synchronize()
-            res[how] = (losses, _state(m, opt))
-        le, lr_ = res["eager"][0], res["replay"][0]
-        print("[cross replay] losses", le, lr_)
-        assert le[2:] == lr_[2:], (le, lr_)
-        for k, v in res["eager"][1].items():
-            assert torch.equal(v, res["replay"][1][k]), k
-    finally:
-        config.set_deterministic(None)
-        ydl.set_compute_dtype("bf16")
+    check_replay_equals_eager(_setup, "cross", ("ydl_xconv_fwd", "ydl_xconv_dgrad", "ydl_xconv_wgrad"))

@@ -16,7 +16,8 @@ import functools
 import pytest
 import torch
 
-from tests.test_gpu_ghost_blocks import BF16_TOL, _err, _kind
+from tests.block_harness import kind as _kind, rel_max_err as _err
+from tests.test_gpu_ghost_blocks import BF16_TOL
 
 pytestmark = pytest.mark.gpu
 

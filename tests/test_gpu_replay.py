@@ -9,6 +9,7 @@ import torch
 import yaml
 
 from oracle.fill import fill_state_dict
+from tests.block_harness import train_state as _state
 
 pytestmark = pytest.mark.gpu
 CW = torch.tensor([1, 2, 25, 2, 10, 3, 25, 10, 5, 15, 25, 1], dtype=torch.float32)
@@ -38,13 +39,6 @@ def _setup(mode, cfg_name="yolov5_seg.yaml", cls="YOLOv5Seg", size=128, bs=4, ki
     xs = [torch.rand(bs, 3, size, size, device="cuda", generator=gen) for _ in range(3)]
     ts = [torch.randint(0, 12, (bs, size, size), device="cuda", generator=gen) for _ in range(3)]
     return m, opt, crit, xs, ts
-
-
-def _state(m, opt):
-    out = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    out["__momentum"] = opt.mom_arena.detach().clone()
-    out["__ema"] = opt.ema_arena.detach().clone()
-    return out
 
 
 @pytest.mark.parametrize("mode,cfg_name,cls,kind", [("bf16", "yolov5_seg.yaml", "YOLOv5Seg", "dice"), ("f32", "yolov5_seg.yaml", "YOLOv5Seg", "dice"),

@@ -2,7 +2,7 @@
 """Dev-time generator of tests/golden/attn_conv_*.npz and attn_stem_*.npz: the reference's OWN AttentionConv / AttentionStem
 classes, run on the CPU in float64.
 
-    python tools/make_attn_golden.py --reference <checkout of the reference project>
+    python tools/make_attn_golden.py --reference <checkout of the reference project> [--out DIR]
 
 Nothing of the reference is copied: the line range of models/common.py that holds the two classes (:1509-1627) is exec'd in a
 namespace that provides torch, nn and F.  Only arrays are written, per case:
@@ -12,16 +12,15 @@ namespace that provides torch, nn and F.  Only arrays are written, per case:
   x, out, grad_out, grad_x
 
 Inputs keep |logit| below about 4: x, rel_* and emb_* ~ N(0, 1), projection weights ~ N(0, 1/c1)."""
-import argparse
 import os
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "tests", "golden")
+import golden_blocks as G
+
+RANGES = ((1509, 1627),)
 
 # name -> (class, constructor arguments, (N, H, W))
 CASES = {
@@ -35,40 +34,23 @@ CASES = {
 
 
 def load_reference(ref):
-    path = os.path.join(ref, "models", "common.py")
-    lines = open(path, encoding="utf-8").read().split("\n")
-    ns = dict(torch=torch, nn=nn, F=F)
-    exec(compile("\n" * (1509 - 1) + "\n".join(lines[1509 - 1:1627]), path, "exec"), ns)
-    return ns
+    return G.load_ranges(os.path.join(ref, "models", "common.py"), RANGES, dict(torch=torch, nn=nn, F=F))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reference", required=True)
-    opt = ap.parse_args()
-    ns = load_reference(opt.reference)
-    os.makedirs(OUT, exist_ok=True)
-    for seed, (name, (cls, kw, (N, H, W))) in enumerate(CASES.items()):
-        gen = torch.Generator().manual_seed(100 + seed)
-        mod = ns[cls](**kw).double()
-        c1 = kw["in_channels"]
-        with torch.no_grad():
-            for key, p in mod.named_parameters():
-                p.copy_(torch.randn(p.shape, generator=gen, dtype=torch.float64) * (c1 ** -0.5 if key.endswith(".weight") else 1.0))
-        x = torch.randn(N, c1, H, W, generator=gen, dtype=torch.float64, requires_grad=True)
-        out = mod(x)
-        gout = torch.randn(out.shape, generator=gen, dtype=torch.float64)
-        out.backward(gout)
-        keys = list(mod.state_dict().keys())
-        arrs = dict(args=np.array([c1, kw["out_channels"], kw["kernel_size"], kw["stride"], kw["padding"], kw["groups"], kw.get("m", 0)]),
-                    keys=np.array(keys), x=x.detach().numpy(), out=out.detach().numpy(), grad_out=gout.numpy(), grad_x=x.grad.numpy())
+def record(ns, seed, case, path):
+    cls, kw, (N, H, W) = case
+    gen = torch.Generator().manual_seed(100 + seed)
+    mod = ns[cls](**kw).double()
+    c1 = kw["in_channels"]
+    with torch.no_grad():                               # this family's own draw, in float64 throughout
         for key, p in mod.named_parameters():
-            arrs["p." + key] = p.detach().numpy()
-            arrs["g." + key] = p.grad.numpy()
-        path = os.path.join(OUT, name + ".npz")
-        np.savez_compressed(path, **arrs)
-        print(f"{path}: {os.path.getsize(path)} bytes, out {tuple(out.shape)}, |logit| proxy max|x| {float(x.detach().abs().max()):.2f}")
+            p.copy_(torch.randn(p.shape, generator=gen, dtype=torch.float64) * (c1 ** -0.5 if key.endswith(".weight") else 1.0))
+    x = torch.randn(N, c1, H, W, generator=gen, dtype=torch.float64)
+    gout = torch.randn(G.out_shape(mod, x), generator=gen, dtype=torch.float64)
+    args = [c1, kw["out_channels"], kw["kernel_size"], kw["stride"], kw["padding"], kw["groups"], kw.get("m", 0)]
+    G.write_fixture(path, dict(args=args), G.snapshot(mod), x, gout, G.run(mod, x, gout), as_f32=lambda k: False)
+    print(f"  |logit| proxy max|x| {float(x.abs().max()):.2f}")
 
 
 if __name__ == "__main__":
-    main()
+    G.main(CASES, load_reference, record)

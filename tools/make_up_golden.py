@@ -2,10 +2,10 @@
 """Dev-time generator of tests/golden/up_*.npz: the decoder up-samplers run on the CPU in float64 — ``nn.ConvTranspose2d`` and
 ``nn.Upsample(mode='bicubic')`` from torch, ``DWConvTranspose2d`` from the reference's OWN class.
 
-    python tools/make_up_golden.py --reference <checkout of the reference project>
+    python tools/make_up_golden.py --reference <checkout of the reference project> [--out DIR]
 
 Nothing of the reference is copied: the lines of models/common.py that hold DWConvTranspose2d (:73-76) are exec'd in a namespace that
-provides math, torch and nn.  Only arrays are written, per case, in the layout of tools/make_cross_golden.py:
+provides math, torch and nn.  Only arrays are written, per case, in the layout of tools/golden_blocks.py (write_fixture):
 
   cls, args, kwargs   class name, the positional constructor arguments and the keyword arguments as JSON
   keys                the state_dict keys, in order;  p.<key> the parameter BEFORE the step,  g.<key> its gradient
@@ -19,17 +19,15 @@ The bf16 floor is the module's own error when its tensors pass through bf16 wher
 with the same parameters run a second time in float64, with the input, the weight, the output and its incoming gradient rounded to
 bf16.  floor.out / floor.grad are the worst error of that run against the float64 run, relative to each tensor's max, over the output /
 the gradients of x and of every parameter."""
-import argparse
 import json
 import math
 import os
 
-import numpy as np
 import torch
 import torch.nn as nn
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "tests", "golden")
+import golden_blocks as G
+
 RANGES = ((73, 76),)
 
 # name -> (class, positional arguments, keyword arguments, input shape)
@@ -45,98 +43,39 @@ CASES = {
 
 
 def load_reference(ref):
-    path = os.path.join(ref, "models", "common.py")
-    lines = open(path, encoding="utf-8").read().split("\n")
-    ns = dict(math=math, torch=torch, nn=nn)
-    for a, b in RANGES:
-        exec(compile("\n" * (a - 1) + "\n".join(lines[a - 1:b]), path, "exec"), ns)
+    ns = G.load_ranges(os.path.join(ref, "models", "common.py"), RANGES, dict(math=math, torch=torch, nn=nn))
     ns["ConvTranspose2d"], ns["Upsample"] = nn.ConvTranspose2d, nn.Upsample
     return ns
 
 
-def bf16(t):
-    return t.to(torch.bfloat16).to(torch.float64)
-
-
-class RoundBoth(torch.autograd.Function):
-    """the value on the way forward and its gradient on the way back, both through bf16"""
-
-    @staticmethod
-    def forward(ctx, t):
-        return bf16(t)
-
-    @staticmethod
-    def backward(ctx, g):
-        return bf16(g)
-
-
-def run(mod, x, gout):
-    x = x.clone().requires_grad_(True)
-    out = mod(x)
-    out.backward(gout)
-    res = {"out": out.detach(), "grad_x": x.grad}
-    for key, p in mod.named_parameters():
-        res["g." + key] = p.grad
-    return res
-
-
-def bf16_floor(make, before, x, gout, exact):
-    mod = make()
-    mod.load_state_dict(before)
+def draw(mod, gen):
     with torch.no_grad():
-        if getattr(mod, "weight", None) is not None:
-            mod.weight.copy_(bf16(mod.weight))
-    mod.register_forward_hook(lambda _m, _i, o: RoundBoth.apply(o))
-    got = run(mod, bf16(x), gout)
-    floor = {"out": 0.0, "grad": 0.0}
-    for k, want in exact.items():
-        kind = "out" if k == "out" else "grad"
-        scale = float(want.abs().max())
-        floor[kind] = max(floor[kind], float((got[k] - want).abs().max()) / (scale if scale > 0 else 1.0))
-    return floor
+        for key, p in mod.named_parameters():
+            if key == "weight":
+                k = p.shape[-1]
+                terms = ((k + 1) // 2) ** 2 * (p.shape[0] if mod.groups == 1 else 1)
+                p.copy_(G.f32(torch.randn(p.shape, generator=gen, dtype=torch.float64) * terms ** -0.5))
+            else:
+                p.copy_(G.f32(torch.rand(p.shape, generator=gen, dtype=torch.float64) * 0.6 - 0.3))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reference", required=True)
-    opt = ap.parse_args()
-    ns = load_reference(opt.reference)
-    os.makedirs(OUT, exist_ok=True)
-    for seed, (name, (cls, args, kwargs, shape)) in enumerate(CASES.items()):
-        gen = torch.Generator().manual_seed(1500 + seed)
+def record(ns, seed, case, path):
+    cls, args, kwargs, shape = case
 
-        def make():
-            return ns[cls](*args, **kwargs).double().train()
+    def make():
+        return ns[cls](*args, **kwargs).double().train()
+
+    def rounded(before):
         mod = make()
+        mod.load_state_dict(before)
         with torch.no_grad():
-            for key, p in mod.named_parameters():
-                if key == "weight":
-                    k = p.shape[-1]
-                    terms = ((k + 1) // 2) ** 2 * (p.shape[0] if mod.groups == 1 else 1)
-                    p.copy_((torch.randn(p.shape, generator=gen, dtype=torch.float64) * terms ** -0.5).float().double())
-                else:
-                    p.copy_((torch.rand(p.shape, generator=gen, dtype=torch.float64) * 0.6 - 0.3).float().double())
-        before = {k: v.detach().clone() for k, v in mod.state_dict().items()}
-        x = torch.randn(*shape, generator=gen, dtype=torch.float64).float().double()
-        out_shape = mod(x).shape
-        gout = torch.randn(out_shape, generator=gen, dtype=torch.float64).float().double()
-        exact = run(mod, x, gout)
-        floor = bf16_floor(make, before, x, gout, exact)
-        keys = list(before.keys())
-        arrs = dict(cls=np.array(cls), args=np.array(json.dumps(list(args))), kwargs=np.array(json.dumps(kwargs)), keys=np.array(keys, dtype=str),
-                    x=x.numpy(), grad_out=gout.numpy())
-        for key in keys:
-            arrs["p." + key] = before[key].numpy()
-        for k, v in exact.items():
-            arrs[k] = v.numpy()
-        for k, v in floor.items():
-            arrs["floor." + k] = np.array(v, dtype=np.float64)
-        arrs = {k: v.astype(np.float32) if v.dtype == np.float64 and not k.startswith("floor.") else v for k, v in arrs.items()}
-        path = os.path.join(OUT, name + ".npz")
-        np.savez_compressed(path, **arrs)
-        print(f"{path}: {os.path.getsize(path)} bytes, out {tuple(out_shape)}, {len(keys)} keys, floor "
-              + ", ".join(f"{k} {v:.2e}" for k, v in floor.items()))
+            if getattr(mod, "weight", None) is not None:
+                mod.weight.copy_(G.bf16(mod.weight))
+        G.round_output(mod)
+        return mod
+    G.record_module(path, torch.Generator().manual_seed(1500 + seed), make, shape,
+                    dict(cls=cls, args=json.dumps(list(args)), kwargs=json.dumps(kwargs)), draw=draw, rounded=rounded)
 
 
 if __name__ == "__main__":
-    main()
+    G.main(CASES, load_reference, record)
