@@ -399,6 +399,23 @@ int ydl_seg_loss_rep_bwd(const float* plow, int64_t sn, int64_t sc, int64_t sh, 
                          int N, int C, int H, int W, int rep_h, int rep_w, const float* ws,
                          const float* dloss /* device scalar, NULL = 1 */, float* dlow, void* stream);
 
+/* The replicated tail in one pass each way, from the stored LOGITS x (NHWC compute dtype, rows of stride ldx, C <= 32):
+ * forward = ydl_softmax_fwd at the stored resolution + ydl_seg_loss_rep_fwd without the probabilities in memory; backward =
+ * ydl_seg_loss_rep_bwd + ydl_softmax_bwd without dlow in memory.  Same ws layout, same `losses`, same arithmetic per pixel
+ * (the per-CTA partial sums are associated differently: several pixels per thread, fewer CTAs).
+ * counts: ydl_seg_tail_count_bytes(...) bytes, 16-byte aligned: the forward leaves the per-pixel label counts there, one byte
+ * per class and 16 (C <= 16) or 32 bytes per stored pixel, and the backward reads them instead of the labels.  Where
+ * rep_h * rep_w > 255 a count does not fit a byte: the size is 0, counts may be NULL and the backward counts the labels again.
+ * dx: rows of stride lddx in x's dtype; channels [C, round_up(C, 8)) are written as zeros where they fit into lddx, as
+ * ydl_softmax_bwd writes them, and nothing beyond. */
+int64_t ydl_seg_tail_count_bytes(int N, int C, int H, int W, int rep_h, int rep_w);
+int ydl_seg_tail_fwd(int dtype, const void* x, int ldx, const int64_t* target, const float* class_weights /* NULL = ones */,
+                     int kind, float label_smoothing, float eps, int N, int C, int H, int W, int rep_h, int rep_w,
+                     float* ws, float* losses, uint8_t* counts, void* stream);
+int ydl_seg_tail_bwd(int dtype, const void* x, int ldx, const uint8_t* counts, const int64_t* target,
+                     const float* class_weights, float label_smoothing, int N, int C, int H, int W, int rep_h, int rep_w,
+                     const float* ws, const float* dloss /* device scalar, NULL = 1 */, void* dx, int lddx, void* stream);
+
 /* ---- optimizer: SGD(nesterov) + EMA on flat arenas --------------------------------------------------- */
 /* params/grads/momentum are flat f32 arenas laid out [decay group | no-decay group]; ema spans
  * n_params + n_buffers (BN running stats follow the params in both `params` and `ema`).

@@ -127,6 +127,9 @@ SIGNATURES = {
     "ydl_seg_loss_bwd": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i, _vp, _i, _f, _f, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ydl_seg_loss_rep_fwd": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i, _f, _f, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ydl_seg_loss_rep_bwd": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i, _f, _f, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ydl_seg_tail_count_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
+    "ydl_seg_tail_fwd": (_i, [_i, _vp, _i, _vp, _vp, _i, _f, _f, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ydl_seg_tail_bwd": (_i, [_i, _vp, _i, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "ydl_sgd_ema_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f, _f, _f, _f, _f, _i, _f, _vp]),
     "ydl_sgd_ema_step_dev": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _vp]),
     "ydl_sgd_ema_step_multi": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _i, _vp]),

@@ -6,6 +6,8 @@ import os
 _STATE = {"dtype": "bf16", "weight_epoch": 0, "lazy_upsample": True, "fuse_siblings": True, "overlap_wgrad": os.environ.get("YDL_OVERLAP_WGRAD", "1") != "0",
           "commute_concat": os.environ.get("YDL_COMMUTE_CONCAT", "1") != "0",
           "replicated_loss": os.environ.get("YDL_REPLICATED_LOSS", "1") != "0",
+          # the replicated tail as ydl_seg_tail_fwd / ydl_seg_tail_bwd: None = from SEG_TAIL_MIN_PIXELS stored pixels on, True / False force
+          "fused_seg_tail": {"1": True, "0": False}.get(os.environ.get("YDL_SEG_TAIL", ""), None),
           "stem_s2d": os.environ.get("YDL_STEM_S2D", "1") != "0",
           # weight gradients: None = deterministic split-K (partial slabs + fixed-order sum) in f32 parity mode, f32 atomics in
           # bf16 throughput mode; True / False force one form for both
@@ -177,6 +179,31 @@ def dcnv3_border_rule() -> str:
 def replicated_loss() -> bool:
     """SegmentationLoss evaluates a nearest-replicated prediction per stored pixel (ydl_seg_loss_rep_*)"""
     return _STATE["replicated_loss"]
+
+
+SEG_TAIL_MIN_PIXELS = 1 << 18
+
+
+def fused_seg_tail():
+    """the switch of the fused replicated tail: None (default) = by size, True / False = forced (see use_fused_seg_tail)"""
+    return _STATE["fused_seg_tail"]
+
+
+def set_fused_seg_tail(on) -> None:
+    """True / False, or None for the by-size default"""
+    _STATE["fused_seg_tail"] = None if on is None else bool(on)
+
+
+def use_fused_seg_tail(stored_pixels: int) -> bool:
+    """whether a replicated prediction tail of ``stored_pixels`` (N * H * W at the stored resolution) runs in one pass each way from the
+    stored logits (ydl_seg_tail_fwd / ydl_seg_tail_bwd; the stored-resolution probabilities are then computed only where something
+    still asks for them) or in the five-launch form (ydl_softmax_fwd at the stored resolution, ydl_seg_loss_rep_fwd,
+    ydl_seg_loss_rep_bwd, ydl_softmax_bwd).  Read when the model's forward builds its output.  By default the fused pair is taken from
+    SEG_TAIL_MIN_PIXELS = 262144 stored pixels on (the flagship step has 409600): the recorded launch traces of the small traced
+    steps (tests/golden/launch_trace.json.gz, up to 131072 stored pixels) keep the five-launch form they were recorded with.
+    set_fused_seg_tail(True) / YDL_SEG_TAIL=1 takes the pair at every size, False / 0 never"""
+    on = _STATE["fused_seg_tail"]
+    return stored_pixels >= SEG_TAIL_MIN_PIXELS if on is None else on
 
 
 def weight_epoch() -> int:

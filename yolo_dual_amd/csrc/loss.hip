@@ -635,6 +635,346 @@ extern "C" int ydl_seg_loss_rep_bwd(const float* plow, int64_t sn, int64_t sc, i
 }
 
 // ------------------------------------------------------------------------------------------------------
+// The replicated tail in one pass each way, from the stored logits.  Unfused, the step runs softmax_fwd_kernel (plow),
+// seg_loss_rep_fwd_kernel, seg_loss_rep_bwd_kernel (dlow) and softmax_bwd_kernel: the soft-max of a stored pixel is formed three
+// times from memory copies of itself, the labels are read and counted twice, and dlow exists only to be read by the next launch.
+// Here each direction reads the logits once and keeps everything else of a pixel in registers:
+//   forward : p = softmax(x) as softmax_fwd_kernel forms it, the label counts as count_labels forms them, the sums of
+//             seg_loss_rep_fwd_kernel (which applies log-softmax to the probabilities, as the reference does); the counts are left
+//             as one byte per class, so the backward never reads the labels (rh*rw <= 255; beyond that it counts them again).
+//             A thread takes several stored pixels and the grid is sized to the device: the 3C+3 cross-lane reductions of a CTA are
+//             paid a few hundred times per launch, not 128 x N times.  Per-CTA partial rows and the fixed-order merge stay.
+//   backward: p again, dlow with the expressions of seg_loss_rep_bwd_kernel, then dx = p (dlow - sum_c p dlow) as softmax_bwd_kernel
+//             has it, stored in the logits' dtype; pad channels [C, Cp) are written as zeros.
+// ------------------------------------------------------------------------------------------------------
+#define TAIL_MAX_COUNT 255
+#define TAIL_TARGET_CTAS 768        // 3 CTAs of 4 waves per CU of a 256-CU device
+// Both kernels are bound by their arithmetic, not by their bytes ("The replicated tail in one pass each way"), and with the
+// class count a run-time value every per-class statement sits behind a scalar branch.  The project's own class count (12: the
+// SegmentationLoss default, every yaml model) gets an instantiation with the count as a constant: no branches, no dead channels.
+#define TAIL_EXACT_C 12
+
+// CTAs per image: whole pixels-per-thread (a CTA-stride turn that only a few threads take costs a full turn), about
+// TAIL_TARGET_CTAS CTAs over the N images, at most the LOSS_BLOCKS_PER_IMAGE partial rows the workspace holds
+static inline int tail_blocks_per_image(int N, long long HW) {
+    long long ppt = ((long long)N * HW + 128LL * TAIL_TARGET_CTAS) / (256LL * TAIL_TARGET_CTAS);      // rounded to nearest
+    if (ppt < 1) ppt = 1;
+    long long b = (HW + 256 * ppt - 1) / (256 * ppt);
+    if (b > LOSS_BLOCKS_PER_IMAGE) b = LOSS_BLOCKS_PER_IMAGE;
+    return (int)b;
+}
+
+// the logits of one stored pixel; `vec`: rows start on 16-byte boundaries and hold whole 16-byte chunks up to channel C
+template <typename T, int MC>
+__device__ __forceinline__ void load_logits(const T* __restrict__ xp, int C, bool vec, float (&v)[MC]) {
+    constexpr int V = ET<T>::V;
+    if (vec) {
+#pragma unroll
+        for (int q = 0; q < MC / V; ++q)
+            if (q * V < C) unpack16<T>(*(const uint4*)(xp + q * V), &v[q * V]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+            if (c < C) v[c] = ET<T>::ld(xp + c);
+    }
+}
+
+// v <- softmax(v) over the first C entries, with the arithmetic of softmax_fwd_kernel
+template <int MC>
+__device__ __forceinline__ void softmax_inplace(float (&v)[MC], int C) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+        if (c < C) mx = fmaxf(mx, v[c]);
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+        if (c < C) { v[c] = expf(v[c] - mx); s += v[c]; }
+    float inv = 1.f / s;
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+        if (c < C) v[c] = v[c] * inv;
+}
+
+// the counts of count_labels as bytes: byte c of the MC-byte row q = how many of the pixel's rh x rw labels equal c (rh*rw <= 255, so
+// no byte carries into its neighbour).  A label adds one shifted 1 to the 8-byte word that holds its class, instead of being compared
+// with every class; a label outside [0, MC) selects no word.
+template <int MC>
+__device__ __forceinline__ void count_labels_bytes(const int64_t* __restrict__ target, int n, int h, int w, int Ht, int Wt, int rh, int rw,
+                                                   uint32_t (&q)[MC / 4]) {
+    unsigned long long acc[MC / 8];
+#pragma unroll
+    for (int k = 0; k < MC / 8; ++k) acc[k] = 0ull;
+    auto add = [&](int t) {
+        const unsigned u = (unsigned)t;
+        const unsigned long long one = 1ull << ((u & 7u) * 8u);
+#pragma unroll
+        for (int k = 0; k < MC / 8; ++k) acc[k] += (u >> 3) == (unsigned)k ? one : 0ull;
+    };
+    const int64_t* tp = target + ((size_t)n * Ht + (size_t)h * rh) * Wt + (size_t)w * rw;
+    if (rw == 4 && (Wt & 1) == 0) {
+        for (int a = 0; a < rh; ++a) {
+            const longlong2* r = (const longlong2*)(tp + (size_t)a * Wt);
+            longlong2 u0 = r[0], u1 = r[1];
+            add((int)u0.x); add((int)u0.y); add((int)u1.x); add((int)u1.y);
+        }
+    } else {
+        for (int a = 0; a < rh; ++a)
+            for (int b = 0; b < rw; ++b) add((int)tp[(size_t)a * Wt + b]);
+    }
+#pragma unroll
+    for (int k = 0; k < MC / 8; ++k) { q[2 * k] = (uint32_t)acc[k]; q[2 * k + 1] = (uint32_t)(acc[k] >> 32); }
+}
+
+template <int MC>
+__device__ __forceinline__ void unpack_counts(const uint32_t (&q)[MC / 4], float (&cnt)[MC]) {
+#pragma unroll
+    for (int c = 0; c < MC; ++c) cnt[c] = (float)((q[c >> 2] >> (8 * (c & 3))) & 0xffu);
+}
+
+template <typename T, int MC, int CE>
+__global__ __launch_bounds__(256) void seg_tail_fwd_kernel(const T* __restrict__ x, int ldx, bool vec,
+                                                           const int64_t* __restrict__ target, const float* __restrict__ cw,
+                                                           int Crt, int H, int W, int rh, int rw, uint8_t* __restrict__ counts,
+                                                           float* __restrict__ part) {
+    const int C = CE > 0 ? CE : Crt;
+    const int n = blockIdx.y;
+    const long long HW = (long long)H * W;
+    const int Ht = H * rh, Wt = W * rw;
+    const float rr = (float)(rh * rw);
+    float accI[MC], accP[MC], accT[MC];
+#pragma unroll
+    for (int c = 0; c < MC; ++c) { accI[c] = 0.f; accP[c] = 0.f; accT[c] = 0.f; }
+    float ce_num = 0.f, ce_den = 0.f, sm_num = 0.f;
+    float wv[MC];
+#pragma unroll
+    for (int c = 0; c < MC; ++c) wv[c] = (c < C) ? (cw ? cw[c] : 1.f) : 0.f;
+
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += (long long)gridDim.x * blockDim.x) {
+        int w = (int)(i % W), h = (int)(i / W);
+        const size_t pix = (size_t)n * HW + i;
+        float cnt[MC];
+        if (counts) {
+            uint32_t q[MC / 4];
+            count_labels_bytes<MC>(target, n, h, w, Ht, Wt, rh, rw, q);
+            uint4* cq = (uint4*)(counts + pix * MC);
+#pragma unroll
+            for (int k = 0; k < MC / 16; ++k) cq[k] = make_uint4(q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]);
+            unpack_counts<MC>(q, cnt);
+        } else {
+            count_labels<MC>(target, n, h, w, Ht, Wt, rh, rw, cnt);
+        }
+        float v[MC];
+        load_logits<T, MC>(x + pix * ldx, C, vec, v);
+        softmax_inplace<MC>(v, C);                                  // the stored-resolution probabilities (plow)
+        // from here on: seg_loss_rep_fwd_kernel on v
+        float mx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+            if (c < C) mx = fmaxf(mx, v[c]);
+        float s = 0.f;
+        float ex[MC];
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+            if (c < C) { ex[c] = expf(v[c] - mx); s += ex[c]; }
+        float lse = mx + logf(s);
+        float inv = 1.f / s;
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+            if (c < C) {
+                float pc = ex[c] * inv;
+                float wp = wv[c] * pc;
+                accP[c] += rr * wp;
+                accI[c] += cnt[c] * wp;
+                accT[c] += cnt[c];
+                float wn = wv[c] * (lse - v[c]);     // w_c * (-log p_c)
+                sm_num += rr * wn;
+                ce_num += cnt[c] * wn;
+                ce_den += cnt[c] * wv[c];
+            }
+    }
+    __shared__ float red[4][3 * MC + 3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+        if (c < C) {
+            float a = wave_total63(accI[c]), b = wave_total63(accP[c]), d = wave_total63(accT[c]);      // (DPP: totals in lane 63)
+            if (lane == 63) { red[wave][c] = a; red[wave][MC + c] = b; red[wave][2 * MC + c] = d; }
+        }
+    {
+        float a = wave_total63(ce_num), b = wave_total63(ce_den), d = wave_total63(sm_num);
+        if (lane == 63) { red[wave][3 * MC] = a; red[wave][3 * MC + 1] = b; red[wave][3 * MC + 2] = d; }
+    }
+    __syncthreads();
+    float* dst = part + ((size_t)n * gridDim.x + blockIdx.x) * (3 * C + 3);
+    if (threadIdx.x < 3 * C + 3) {
+        int k = threadIdx.x;
+        int src = k < 3 * C ? (k / C) * MC + (k % C) : 3 * MC + (k - 3 * C);
+        dst[k] = red[0][src] + red[1][src] + red[2][src] + red[3][src];
+    }
+}
+
+template <typename T, int MC, int CE>
+__global__ __launch_bounds__(256) void seg_tail_bwd_kernel(const T* __restrict__ x, int ldx, bool vec,
+                                                           const uint8_t* __restrict__ counts, const int64_t* __restrict__ target,
+                                                           const float* __restrict__ cw, int Crt, int Cprt, int H, int W, int rh, int rw,
+                                                           float ls, const float* __restrict__ ws, int N,
+                                                           const float* __restrict__ dloss, T* __restrict__ dx, int lddx, bool vec_out) {
+    const int C = CE > 0 ? CE : Crt;
+    const int Cp = CE > 0 && vec_out ? (CE + 7) / 8 * 8 : Cprt;        // (a chunked store implies the padded width)
+    const int n = blockIdx.y;
+    const int NC = N * C;
+    const long long HW = (long long)H * W;
+    const int Ht = H * rh, Wt = W * rw;
+    const float rr = (float)(rh * rw);
+    const float g0 = dloss ? dloss[0] : 1.f;
+    const float ce_den = ws[5 * NC + 1], Wsum = ws[5 * NC + 3];
+    float wv[MC], aI[MC], aP[MC];
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        wv[c] = (c < C) ? (cw ? cw[c] : 1.f) : 0.f;
+        aI[c] = (c < C) ? ws[3 * NC + n * C + c] : 0.f;
+        aP[c] = (c < C) ? ws[4 * NC + n * C + c] : 0.f;
+    }
+    const float k_nll = (1.f - ls) / ce_den;
+    const float k_sm = ls > 0.f ? ls / ((float)C * ce_den) : 0.f;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += (long long)gridDim.x * blockDim.x) {
+        const size_t pix = (size_t)n * HW + i;
+        float cnt[MC];
+        if (counts) {
+            const uint4* cq = (const uint4*)(counts + pix * MC);
+            uint32_t q[MC / 4];
+#pragma unroll
+            for (int k = 0; k < MC / 16; ++k) {
+                const uint4 u = cq[k];
+                q[4 * k] = u.x; q[4 * k + 1] = u.y; q[4 * k + 2] = u.z; q[4 * k + 3] = u.w;
+            }
+            unpack_counts<MC>(q, cnt);
+        } else {
+            count_labels<MC>(target, n, (int)(i / W), (int)(i % W), Ht, Wt, rh, rw, cnt);
+        }
+        float pv[MC];
+        load_logits<T, MC>(x + pix * ldx, C, vec, pv);
+        softmax_inplace<MC>(pv, C);                                 // plow
+        // seg_loss_rep_bwd_kernel on pv -> dlow (kept in gv)
+        float v[MC];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+            if (c < C) { v[c] = pv[c]; mx = fmaxf(mx, v[c]); }
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+            if (c < C) { v[c] = expf(v[c] - mx); s += v[c]; }
+        float inv = 1.f / s;
+        float S = 0.f, A = 0.f, G0 = 0.f;
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+            if (c < C) {
+                v[c] *= inv;
+                float cwc = cnt[c] * wv[c];
+                S += cwc;
+                A += cwc * aI[c] * v[c];
+                G0 += wv[c] * aP[c] * v[c];
+            }
+        float gv[MC];
+        float dot = 0.f;
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+            if (c < C) {
+                float cwc = cnt[c] * wv[c];
+                float d_ce = k_nll * (v[c] * S - cwc) + k_sm * rr * (v[c] * Wsum - wv[c]);
+                float d_ov = v[c] * (rr * wv[c] * aP[c] + cwc * aI[c] - rr * G0 - A);
+                gv[c] = g0 * (d_ce + 0.5f * d_ov);
+                dot += pv[c] * gv[c];                               // softmax_bwd_kernel from here
+            }
+        T* d = dx + pix * lddx;
+        if (vec_out) {
+            constexpr int V = ET<T>::V;
+#pragma unroll
+            for (int q = 0; q < MC / V; ++q)
+                if (q * V < Cp) {
+                    float o[V];
+#pragma unroll
+                    for (int e = 0; e < V; ++e) { const int c = q * V + e; o[e] = c < C ? pv[c] * (gv[c] - dot) : 0.f; }
+                    *(uint4*)(d + q * V) = pack16<T>(o);
+                }
+        } else {
+#pragma unroll
+            for (int c = 0; c < MC; ++c)
+                if (c < Cp) ET<T>::st(d + c, c < C ? pv[c] * (gv[c] - dot) : 0.f);
+        }
+    }
+}
+
+extern "C" int64_t ydl_seg_tail_count_bytes(int N, int C, int H, int W, int rep_h, int rep_w) {
+    if ((long long)rep_h * rep_w > TAIL_MAX_COUNT) return 0;
+    return (int64_t)N * H * W * (C <= 16 ? 16 : 32);
+}
+
+// rows of `ld` elements from `p`: 16-byte aligned and holding whole 16-byte chunks up to channel `upto`
+static inline bool rows_vectorise(int dtype, const void* p, int ld, int upto) {
+    const int V = dtype == YDL_F32 ? 4 : 8;
+    return ((uintptr_t)p & 15) == 0 && ld % V == 0 && round_up(upto, V) <= ld;
+}
+
+extern "C" int ydl_seg_tail_fwd(int dtype, const void* x, int ldx, const int64_t* target, const float* class_weights,
+                                int kind, float label_smoothing, float eps, int N, int C, int H, int W, int rep_h, int rep_w,
+                                float* ws, float* losses, uint8_t* counts, void* stream) {
+    YDL_CHECK(x && target && ws && losses, "null pointer");
+    YDL_CHECK(dtype == YDL_F32 || dtype == YDL_BF16, "bad dtype");
+    YDL_CHECK(C >= 1 && C <= MAXC && ldx >= C && N >= 1 && H >= 1 && W >= 1 && rep_h >= 1 && rep_w >= 1, "bad sizes (C <= 32)");
+    YDL_CHECK(kind == YDL_LOSS_DICE || kind == YDL_LOSS_JACCARD, "bad loss kind");
+    const bool bytes = (long long)rep_h * rep_w <= TAIL_MAX_COUNT;
+    YDL_CHECK(!bytes || (counts && ((uintptr_t)counts & 15) == 0), "counts: 16-byte aligned buffer of ydl_seg_tail_count_bytes");
+    if (!bytes) counts = nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = tail_blocks_per_image(N, (long long)H * W);
+    dim3 grid(nblk, N);
+    float* part = ws + (size_t)5 * N * C + 4;
+    const bool vec = rows_vectorise(dtype, x, ldx, C);
+#define TAIL_FWD(T, MC, CE) seg_tail_fwd_kernel<T, MC, CE><<<grid, 256, 0, st>>>((const T*)x, ldx, vec, target, class_weights, C, H, W, \
+                                                                               rep_h, rep_w, counts, part)
+    if (dtype == YDL_F32) { if (C == TAIL_EXACT_C) TAIL_FWD(float, 16, TAIL_EXACT_C); else if (C <= 16) TAIL_FWD(float, 16, 0); else TAIL_FWD(float, 32, 0); }
+    else { if (C == TAIL_EXACT_C) TAIL_FWD(bf16_t, 16, TAIL_EXACT_C); else if (C <= 16) TAIL_FWD(bf16_t, 16, 0); else TAIL_FWD(bf16_t, 32, 0); }
+#undef TAIL_FWD
+    float* img_part = part + (size_t)N * nblk * (3 * C + 3);
+    seg_loss_merge1_kernel<<<N, 256, 0, st>>>(ws, N, C, nblk, kind, eps, img_part);
+    seg_loss_merge2_kernel<<<1, 64, 0, st>>>(ws, N, C, label_smoothing, class_weights, img_part, losses);
+    YDL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ydl_seg_tail_bwd(int dtype, const void* x, int ldx, const uint8_t* counts, const int64_t* target,
+                                const float* class_weights, float label_smoothing, int N, int C, int H, int W, int rep_h, int rep_w,
+                                const float* ws, const float* dloss, void* dx, int lddx, void* stream) {
+    YDL_CHECK(x && ws && dx, "null pointer");
+    YDL_CHECK(dtype == YDL_F32 || dtype == YDL_BF16, "bad dtype");
+    YDL_CHECK(C >= 1 && C <= MAXC && ldx >= C && lddx >= C && N >= 1 && H >= 1 && W >= 1 && rep_h >= 1 && rep_w >= 1,
+              "bad sizes (C <= 32)");
+    const bool bytes = (long long)rep_h * rep_w <= TAIL_MAX_COUNT;
+    YDL_CHECK(bytes ? (counts && ((uintptr_t)counts & 15) == 0) : target != nullptr,
+              "counts of ydl_seg_tail_fwd (16-byte aligned), or the labels where rep_h * rep_w > 255");
+    if (!bytes) counts = nullptr;
+    const int Cp = round_up(C, 8) <= lddx ? round_up(C, 8) : C;
+    hipStream_t st = (hipStream_t)stream;
+    const long long HW = (long long)H * W;
+    int bx = (int)((HW + 255) / 256);
+    if (bx > 1024) bx = 1024;
+    dim3 grid(bx, N);
+    const bool vec = rows_vectorise(dtype, x, ldx, C);
+    const bool vec_out = Cp % 8 == 0 && rows_vectorise(dtype, dx, lddx, Cp);
+#define TAIL_BWD(T, MC, CE) seg_tail_bwd_kernel<T, MC, CE><<<grid, 256, 0, st>>>((const T*)x, ldx, vec, counts, target, class_weights, C, Cp, \
+                                                                               H, W, rep_h, rep_w, label_smoothing, ws, N, dloss,  \
+                                                                               (T*)dx, lddx, vec_out)
+    if (dtype == YDL_F32) { if (C == TAIL_EXACT_C) TAIL_BWD(float, 16, TAIL_EXACT_C); else if (C <= 16) TAIL_BWD(float, 16, 0); else TAIL_BWD(float, 32, 0); }
+    else { if (C == TAIL_EXACT_C) TAIL_BWD(bf16_t, 16, TAIL_EXACT_C); else if (C <= 16) TAIL_BWD(bf16_t, 16, 0); else TAIL_BWD(bf16_t, 32, 0); }
+#undef TAIL_BWD
+    YDL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------
 // argmax + confusion matrix (rows = target, cols = prediction; pixels whose target == ignore_index dropped)
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict__ pred, long long sn, long long sc, long long sh,

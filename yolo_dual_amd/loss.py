@@ -34,7 +34,17 @@ class _SegLossFn(torch.autograd.Function):
         if lazy is not None and (Ht, Wt) != (H, W):
             lazy = None
         ctx.lazy = lazy
-        if lazy is not None:
+        ctx.fused = lazy is not None and lazy.x is not None
+        if ctx.fused:
+            # the region handed over the stored logits: soft-max, label counts and the loss sums in one pass (ydl_seg_tail_fwd)
+            x, (rh, rw) = lazy.x, lazy.rep
+            counts = torch.empty(max(L.lib().ydl_seg_tail_count_bytes(N, C, x.H, x.W, rh, rw), 16), dtype=torch.uint8,
+                                 device=pred.device)
+            L.call("ydl_seg_tail_fwd", x.dt, _p(x.t), x.ld, _p(target), _p(cw), kind, ls, eps, N, C, x.H, x.W, rh, rw,
+                   _p(ws), _p(losses), _p(counts), _stream())
+            ctx.save_for_backward(target, ws, counts)
+            ctx.shape = tuple(pred.shape)
+        elif lazy is not None:
             low, (rh, rw) = lazy.low, lazy.rep
             sn, sc, sh, sw = low.stride()
             L.call("ydl_seg_loss_rep_fwd", _p(low), sn, sc, sh, sw, _p(target), _p(cw), kind, ls, eps,
@@ -54,6 +64,14 @@ class _SegLossFn(torch.autograd.Function):
     def backward(ctx, gtotal, _glosses):
         g = gtotal.contiguous().float()
         lazy = ctx.lazy
+        if ctx.fused:
+            # nothing is launched here: the region's backward issues ydl_seg_tail_bwd straight into the gradient of the logits
+            target, ws, counts = ctx.saved_tensors
+            if lazy.tail is not None:
+                g = lazy.tail[-1] + g                                    # (a repeated backward of this loss adds up)
+            lazy.tail = [target, ctx.cw, ctx.kind, ctx.ls, ctx.eps, ws, counts, g]
+            lazy.dummy = g.new_zeros(1).expand(ctx.shape)
+            return lazy.dummy, None, None, None, None, None, None
         if lazy is not None:
             target, ws = ctx.saved_tensors
             low, (rh, rw) = lazy.low, lazy.rep

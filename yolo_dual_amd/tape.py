@@ -208,11 +208,39 @@ class LazyOutput:
     """side channel between a region whose output is a nearest-replicated tensor and SegmentationLoss:
     ``low`` = the (N, C, H, W) tensor the (N, C, H*rh, W*rw) output replicates, ``version`` = the output's version
     counter when it was produced (an in-place edit by the caller invalidates the shortcut), ``dlow`` = replica-summed
-    gradient handed back by the loss backward, ``dummy`` = the zero-stride placeholder gradient it returned."""
-    __slots__ = ("low", "rep", "version", "dlow", "dummy", "claimed")
+    gradient handed back by the loss backward, ``dummy`` = the zero-stride placeholder gradient it returned.
 
-    def __init__(self, low: torch.Tensor, rep):
-        self.low, self.rep, self.version, self.dlow, self.dummy, self.claimed = low, tuple(rep), -1, None, None, False
+    Fused tail (config.use_fused_seg_tail): the region hands over the stored LOGITS ``x`` instead (a Var: NHWC rows in the compute
+    dtype); ``low`` is then computed from them only when something reads it (a second loss on the prediction, the fold into a
+    dense gradient).  The loss evaluates ydl_seg_tail_fwd on ``x`` and its backward leaves ``tail`` = [labels, class weights,
+    label smoothing, workspace, label counts, loss gradient] for the region, which issues ydl_seg_tail_bwd straight into the
+    gradient of ``x`` (or, where the prediction had other consumers, recovers ``dlow`` from it)."""
+    __slots__ = ("_low", "x", "rep", "version", "dlow", "dummy", "claimed", "tail")
+
+    def __init__(self, low: Optional[torch.Tensor], rep, x=None):
+        self._low, self.x, self.rep, self.version, self.dlow, self.dummy, self.claimed = low, x, tuple(rep), -1, None, None, False
+        self.tail = None
+
+    @property
+    def low(self) -> torch.Tensor:
+        if self._low is None:
+            x = self.x
+            self._low = torch.empty((x.N, x.C, x.H, x.W), dtype=torch.float32, device=x.t.device)
+            sn, sc, sh, sw = self._low.stride()
+            L.call("ydl_softmax_fwd", x.dt, _p(x.t), x.ld, _p(self._low), sn, sc, sh, sw, x.N, x.H, x.W, x.C, 1, 1, _stream())
+        return self._low
+
+    def tail_dlow(self) -> torch.Tensor:
+        """the replica-summed loss gradient of the fused tail as a tensor (``tail`` is consumed)"""
+        target, cw, kind, ls, eps, ws, _counts, g = self.tail
+        self.tail = None
+        low = self.low
+        dlow = torch.empty_like(low)
+        sn, sc, sh, sw = low.stride()
+        N, C, h, w = low.shape
+        L.call("ydl_seg_loss_rep_bwd", _p(low), sn, sc, sh, sw, _p(target), _p(cw), kind, ls, eps, N, C, h, w, self.rep[0], self.rep[1],
+               _p(ws), _p(g), _p(dlow), _stream())
+        return dlow
 
 
 class Tape:
@@ -1212,7 +1240,9 @@ class Tape:
         """nn.Softmax(1) producing the region's external output directly: f32 NCHW contiguous (no extra pass).
         The region owner must call softmax_nchw_backward with the incoming gradient.
         When x is a lazily up-sampled tensor the stored-resolution probabilities are kept as well (``self.lazy_out``):
-        SegmentationLoss uses them to evaluate the loss and its gradient per stored pixel (ydl_seg_loss_rep_*)."""
+        SegmentationLoss uses them to evaluate the loss and its gradient per stored pixel (ydl_seg_loss_rep_*).  With
+        config.use_fused_seg_tail the stored logits are handed over instead and the probabilities are computed on demand only
+        (LazyOutput)."""
         assert not x.virtual
         p = torch.empty((x.N, x.C, x.LH, x.LW), dtype=torch.float32, device=self.device)
         sn, sc, sh, sw = p.stride()
@@ -1220,10 +1250,13 @@ class Tape:
                _stream())
         self.lazy_out = None
         if x.rep != (1, 1) and self.record:
-            plow = torch.empty((x.N, x.C, x.H, x.W), dtype=torch.float32, device=self.device)
-            sn, sc, sh, sw = plow.stride()
-            L.call("ydl_softmax_fwd", x.dt, _p(x.t), x.ld, _p(plow), sn, sc, sh, sw, x.N, x.H, x.W, x.C, 1, 1, _stream())
-            self.lazy_out = LazyOutput(plow, x.rep)
+            if _cfg.use_fused_seg_tail(x.N * x.H * x.W):
+                self.lazy_out = LazyOutput(None, x.rep, x)
+            else:
+                plow = torch.empty((x.N, x.C, x.H, x.W), dtype=torch.float32, device=self.device)
+                sn, sc, sh, sw = plow.stride()
+                L.call("ydl_softmax_fwd", x.dt, _p(x.t), x.ld, _p(plow), sn, sc, sh, sw, x.N, x.H, x.W, x.C, 1, 1, _stream())
+                self.lazy_out = LazyOutput(plow, x.rep)
         return p
 
     def softmax_nchw_backward(self, x: Var, p: torch.Tensor, dp: torch.Tensor) -> None:
@@ -1234,6 +1267,16 @@ class Tape:
         dlow = None
         if lazy is not None:
             dlow, lazy.dlow = lazy.dlow, None
+            if lazy.tail is not None:
+                if all(s == 0 for s in dp.stride()) and getattr(lazy, "dummy", None) is not None:
+                    # the loss is the prediction's only consumer: its backward and the soft-max backward in one pass from the logits
+                    lazy.dummy = None
+                    target, cw, _kind, ls, _eps, ws, counts, g = lazy.tail
+                    lazy.tail = None
+                    L.call("ydl_seg_tail_bwd", x.dt, _p(x.t), x.ld, _p(counts), _p(target), _p(cw), ls, x.N, x.C, x.H, x.W,
+                           x.rep[0], x.rep[1], _p(ws), _p(g), _p(gx), x.ld, _stream())
+                    return
+                dlow = lazy.tail_dlow()
         if dlow is not None:
             if all(s == 0 for s in dp.stride()) and getattr(lazy, "dummy", None) is not None:
                 # the loss already summed its gradient over the replicas: soft-max backward at the stored resolution
