@@ -344,6 +344,18 @@ int ydl_nchw_to_nhwc(int dtype, const float* src, void* dst, int ldd, int N, int
  * Conv(3, 64, 6, 2, 2)):  conv(k,s,p) on (H,W,C) == conv(k/s,1,p/s) on (H/s, W/s, s*s*C), channel (dy*s+dx)*C + c.
  * ydl_weight_prep_s2d / ydl_wgrad_unpack_s2d apply the same index map to the KRSC weight and its gradient. */
 int ydl_nchw_to_s2d(int dtype, const float* src, void* dst, int ldd, int N, int C, int H, int W, int s, void* stream);
+/* space-to-depth / depth-to-space on interior NHWC tensors (Focus, Contract, Expand: models/common.py:241-250, :282-307); each is the
+ * other's backward.  Rows are NHWC with strides ldx / ldy in elements.
+ *   ydl_space_to_depth: x (N, H, W, C)     -> y (N, H/s, W/s, s*s*C):  y[n, ho, wo, blk(sy,sx)*C + c] (+)= x[n, ho*s+sy, wo*s+sx, c]
+ *   ydl_depth_to_space: x (N, H, W, s*s*C) -> y (N, H*s, W*s, C):      y[n, h*s+sy, w*s+sx, c] (+)= x[n, h, w, blk(sy,sx)*C + c]
+ * order 0: blk = sy*s + sx (Contract, Expand, ydl_nchw_to_s2d); order 1: blk = sx*s + sy (Focus's concat order).  Only the channels
+ * [0, s*s*C) / [0, C) of each output row are written.  accumulate != 0 adds in f32 with one rounding.  No atomics.  16-byte chunks move
+ * when C, both strides and both pointers are whole chunks; an element-granular kernel serves every other alignment.  Refused: H or W
+ * not a multiple of s (space-to-depth), a stride shorter than its row, s < 1, order outside {0, 1}. */
+int ydl_space_to_depth(int dtype, const void* x, int ldx, void* y, int ldy, int N, int H, int W, int C, int s, int order,
+                       int accumulate, void* stream);
+int ydl_depth_to_space(int dtype, const void* x, int ldx, void* y, int ldy, int N, int H, int W, int C, int s, int order,
+                       int accumulate, void* stream);
 int ydl_weight_prep_s2d(int dtype, const float* master, void* w2, int Cout, int k, int s, int C, void* stream);
 int ydl_wgrad_unpack_s2d(const float* dw2, float* grad, int Cout, int k, int s, int C, int accumulate, void* stream);
 int ydl_nhwc_to_nchw(int dtype, const void* src, int lds, float* dst, int N, int C, int H, int W, int accumulate,

@@ -15,7 +15,8 @@ from .models import (ResNet18, ResNet18Seg, ResNet50, ResNet50Seg, ResNet50SegYa
 from .modules import (GAM, AttentionConv, AttentionStem, C2f, C3, C3k2, C3_DCNV3, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C3Common, Concat,
                       Conv, C2f_DCN, C3_DCN, C3_DCNCommon, Bottleneck_DCN, DCNv2, DCNv3, DCNV3_YoLo, DeformConv2d, Linear, MaxPool2d, SegmentHead, SPPF, Upsample, autopad,
                       C3Ghost, DWConv, GhostBottleneck, GhostConv, C3TR, TransformerBlock, TransformerLayer, ASPP, RFB, BasicConv,
-                      SPP, C3SPP, SimConv, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF, CrossConv, C3x, ConvTranspose2d, DWConvTranspose2d)
+                      SPP, C3SPP, SimConv, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF, CrossConv, C3x, ConvTranspose2d, DWConvTranspose2d,
+                      Focus, Contract, Expand, BottleneckCSP, BatchNorm2d)
 from .deform import deform_conv2d
 from . import activations
 from .activations import AconC, FReLU, Hardswish, MemoryEfficientMish, MetaAconC, Mish, SiLU

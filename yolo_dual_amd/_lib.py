@@ -111,6 +111,8 @@ SIGNATURES = {
     "ydl_copy2d": (_i, [_i, _vp, _i, _vp, _i, _i64, _i, _i, _vp]),
     "ydl_nchw_to_nhwc": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ydl_nchw_to_s2d": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ydl_space_to_depth": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ydl_depth_to_space": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ydl_weight_prep_s2d": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ydl_wgrad_unpack_s2d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ydl_nhwc_to_nchw": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -30,7 +30,8 @@ from . import _lib as L
 from .modules import (ASPP, RFB, GAM, AttentionConv, AttentionStem, BasicBlock, Bottleneck, Bottleneck_DCNV3, BottleneckBlock, C2f, C2f_DCN, C3, C3_DCN, C3_DCNCommon, C3_DCNV3,
                       C3Common, C3Ghost, C3k2, C3TR, Concat, DWConv, GhostBottleneck, GhostConv, TransformerBlock,
                       Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region,
-                      SPP, C3SPP, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF, CrossConv, C3x, ConvTranspose2d, DWConvTranspose2d)
+                      SPP, C3SPP, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF, CrossConv, C3x, ConvTranspose2d, DWConvTranspose2d,
+                      Focus, Contract, Expand, BottleneckCSP, BatchNorm2d)
 from .tape import Tape, Var
 
 LOGGER = logging.getLogger("yolo_dual_amd")
@@ -533,7 +534,8 @@ _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": 
                 "GhostBottleneck": GhostBottleneck, "C3Ghost": C3Ghost, "C3TR": C3TR, "TransformerBlock": TransformerBlock,
                 "ASPP": ASPP, "RFB": RFB, "SPP": SPP, "C3SPP": C3SPP, "SimSPPF": SimSPPF, "SPPCSPC": SPPCSPC,
                 "SPPCSPC_group": SPPCSPC_group, "SimCSPSPPF": SimCSPSPPF, "CrossConv": CrossConv, "C3x": C3x,
-                "nn.ConvTranspose2d": ConvTranspose2d, "DWConvTranspose2d": DWConvTranspose2d}
+                "nn.ConvTranspose2d": ConvTranspose2d, "DWConvTranspose2d": DWConvTranspose2d, "Focus": Focus,
+                "BottleneckCSP": BottleneckCSP, "Contract": Contract, "Expand": Expand, "nn.BatchNorm2d": BatchNorm2d}
 
 
 # the activations a yaml can name: ``nn.Name(...)`` is torch's class, a bare ``Name(...)`` the class of yolo_dual_amd.activations where
@@ -624,15 +626,22 @@ def _parse_model(d: dict, ch: List[int], deformable: bool = False):
         n = n_ = max(round(n * gd), 1) if n > 1 else n
         if cls in (Conv, Bottleneck, C3Common, SPPF, C3_DCNV3, Bottleneck_DCNV3, C3_DCNCommon, AttentionConv, AttentionStem,
                    DWConv, GhostConv, GhostBottleneck, C3Ghost, C3TR, ASPP, RFB, SPP, C3SPP, SimSPPF, SPPCSPC, SPPCSPC_group,
-                   SimCSPSPPF, CrossConv, C3x, ConvTranspose2d, DWConvTranspose2d):
+                   SimCSPSPPF, CrossConv, C3x, ConvTranspose2d, DWConvTranspose2d, Focus, BottleneckCSP):
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)
             # a string argument that has the form of a call is an activation (the reference evaluates string arguments)
             args = [c1, c2, *(resolve_activation(a) if isinstance(a, str) and _ACT_FORM.match(a) else a for a in args[1:])]
-            if cls in (C3Common, C3_DCNV3, C3_DCNCommon, C3Ghost, C3TR, C3x):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
+            if cls in (C3Common, C3_DCNV3, C3_DCNCommon, C3Ghost, C3TR, C3x, BottleneckCSP):          # models/yolo.py:327-329 + the C3_DCNV3 wiring note ("common and yolo.py")
                 args.insert(2, n)
                 n = 1
+        elif cls is BatchNorm2d:                         # models/yolo.py:330-331
+            args = [ch[f]]
+            c2 = ch[f]
+        elif cls is Contract:                            # models/yolo.py:341-342
+            c2 = ch[f] * args[0] ** 2
+        elif cls is Expand:                              # models/yolo.py:343-344
+            c2 = ch[f] // args[0] ** 2
         elif cls is Concat:
             c2 = sum(ch[x] for x in f)
         elif cls is TransformerBlock:                    # not in the reference's channel-scaling set: args as written, c2 = ch[f]

@@ -27,7 +27,8 @@ __all__ = ["autopad", "Conv", "C3", "C3Common", "Bottleneck", "C2f", "C3k2", "GA
            "BasicBlock", "BottleneckBlock", "SegmentHead", "run_region", "Linear", "DCNv3", "DCNV3_YoLo", "Bottleneck_DCNV3",
            "C3_DCNV3", "DeformConv2d", "C3_DCN", "C2f_DCN", "DCNv2",
            "Bottleneck_DCN", "C3_DCNCommon", "AttentionConv", "AttentionStem", "DWConv", "GhostConv", "GhostBottleneck", "C3Ghost",
-           "BasicConv", "RFB", "ASPP", "CrossConv", "C3x", "ConvTranspose2d", "DWConvTranspose2d"]
+           "BasicConv", "RFB", "ASPP", "CrossConv", "C3x", "ConvTranspose2d", "DWConvTranspose2d",
+           "Focus", "Contract", "Expand", "BottleneckCSP", "BatchNorm2d"]
 
 
 def autopad(k, p=None, d=1):
@@ -918,6 +919,201 @@ class C2f(YdlModule):
         if self.add:
             return self.cv2._fwd(tape, cat, res=x, res_mode=L.RES_AFTER_ACT)
         return self.cv2._fwd(tape, cat)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# space / depth layers, the bare BatchNorm2d row and BottleneckCSP (models/common.py:128-144, 241-250, 282-307; models/yolo.py:330-343)
+# ----------------------------------------------------------------------------------------------------------
+class Focus(YdlModule):
+    """models/common.py:241-250: the four pixel phases of x concatenated on the channels, (::2, ::2), (1::2, ::2), (::2, 1::2),
+    (1::2, 1::2), then ``Conv(4 * c1, c2, k, s, p, g, act)``.  The concat is one ydl_space_to_depth launch in ``order`` 1; on the raw
+    image it follows the NHWC edge conversion (``Conv``'s own space-to-depth stem, ``_S2DStem``, is a different layer)."""
+
+    def __init__(self, c1, c2, k=1, s=1, p=None, g=1, act=True):
+        super().__init__()
+        self.conv = Conv(c1 * 4, c2, k, s, p, g, act=act)
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        if x.LH % 2 or x.LW % 2:
+            raise ValueError(f"Focus: the {x.LH} x {x.LW} map is not a multiple of 2")
+        return self.conv._fwd(tape, tape.space_to_depth(x, 2, order=1), out=out)
+
+
+def _gain(who: str, gain) -> int:
+    if isinstance(gain, bool) or not isinstance(gain, int) or gain < 1:
+        raise ValueError(f"{who}: gain={gain!r} must be an int >= 1")
+    return gain
+
+
+class Contract(YdlModule):
+    """models/common.py:282-293: (N, C, H, W) -> (N, C * gain^2, H / gain, W / gain), channel (sy * gain + sx) * C + c.  No parameters."""
+
+    def __init__(self, gain=2):
+        super().__init__()
+        self.gain = _gain("Contract", gain)
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        for what, v in (("height", x.LH), ("width", x.LW)):
+            if v % self.gain:
+                raise ValueError(f"Contract: the map's {what} {v} is not a multiple of gain={self.gain}")
+        return tape.space_to_depth(x, self.gain, order=0, out=out)
+
+    def extra_repr(self):
+        return f"gain={self.gain}"
+
+
+class Expand(YdlModule):
+    """models/common.py:296-307: (N, C, H, W) -> (N, C / gain^2, H * gain, W * gain), the inverse of ``Contract``.  No parameters."""
+
+    def __init__(self, gain=2):
+        super().__init__()
+        self.gain = _gain("Expand", gain)
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        if x.C % self.gain ** 2:
+            raise ValueError(f"Expand: {x.C} channels are not a multiple of gain^2={self.gain ** 2}")
+        return tape.depth_to_space(x, self.gain, order=0, out=out)
+
+    def extra_repr(self):
+        return f"gain={self.gain}"
+
+
+class BatchNorm2d(_GemmWeights, _BNHolder):
+    """The bare ``nn.BatchNorm2d`` row of a yaml (models/yolo.py:330-331): torch's signature and state_dict keys, run by Tape.bn_act with
+    no activation.  It is its own ``bn`` and uses the BatchNorm half of ``_GemmWeights`` only (coefficient and gradient rows): there is
+    no GEMM in front of it."""
+    takes_list = False
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, device=None, dtype=None):
+        if not affine or not track_running_stats or momentum is None:
+            raise NotImplementedError("BatchNorm2d: the HIP path serves affine=True, track_running_stats=True and a numeric momentum "
+                                      f"(got affine={affine}, track_running_stats={track_running_stats}, momentum={momentum})")
+        _BNHolder.__init__(self, num_features)
+        self.eps, self.momentum = eps, momentum
+
+    @property
+    def bn(self):
+        return self
+
+    def _gemm_dims(self):
+        return self.num_features, 0, 0
+
+    def trainable(self):
+        return (False, self.weight.requires_grad, self.bias.requires_grad)
+
+    def forward(self, x):
+        if isinstance(x, Var):
+            return self._fwd(x.tape, x)
+        return run_region(self, [x])
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        self.mark_step(tape)
+        return tape.bn_act(x, self, L.ACT_NONE, out=out)
+
+
+class _BNSlice:
+    """channels [c0, c0 + c) of a BatchNorm2d as the tape's launches read them.  The tensors are views taken at the call: the optimizer
+    re-homes parameters into its arenas, so a view kept from construction would go stale."""
+
+    def __init__(self, bn: nn.BatchNorm2d, c0: int, c: int):
+        self._bn, self._c0, self._c1, self.num_features = bn, c0, c0 + c, c
+
+    eps = property(lambda self: self._bn.eps)
+    momentum = property(lambda self: self._bn.momentum)
+    weight = property(lambda self: self._bn.weight.detach()[self._c0:self._c1])
+    bias = property(lambda self: self._bn.bias.detach()[self._c0:self._c1])
+    running_mean = property(lambda self: self._bn.running_mean[self._c0:self._c1])
+    running_var = property(lambda self: self._bn.running_var[self._c0:self._c1])
+
+
+class _CSPConv2d(_GemmWeights, nn.Conv2d):
+    """``nn.Conv2d(c1, c2, 1, 1, bias=False)`` of BottleneckCSP (``cv2`` / ``cv3``; state_dict key ``weight``) as Tape.conv_bn_act's
+    holder: the launch writes the BatchNorm partial rows of its own output, and its ``bn`` is the view of the block's BatchNorm over the
+    half of the concat this convolution fills (BatchNorm is per channel: bn(cat(y1, y2)) = cat(bn[:c_](y1), bn[c_:](y2))).  ``host`` =
+    (the block's BatchNorm, first channel, the counter the two halves share)."""
+    _wname = "BottleneckCSP.cv2 / cv3"
+
+    def __init__(self, c1, c2):
+        super().__init__(c1, c2, 1, 1, bias=False)
+        self.c1, self.c2 = c1, c2
+        self._wcache = {}
+
+    def attach(self, bn: nn.BatchNorm2d, c0: int, shared: dict) -> None:
+        # kept out of the module tree (the BatchNorm belongs to the block, once)
+        self.__dict__["_host"] = (bn, c0, shared)
+
+    @property
+    def bn(self):
+        bn, c0, _shared = self._host
+        return _BNSlice(bn, c0, self.c2)
+
+    def _gemm_dims(self):
+        return self.c2, 1, self.c1
+
+    def mark_step(self, tape: Tape) -> None:
+        pass                     # num_batches_tracked advances once per forward of the block, not once per half
+
+    def trainable(self):
+        bn = self._host[0]
+        return (self.weight.requires_grad, bn.weight.requires_grad, bn.bias.requires_grad)
+
+    def splittable(self) -> bool:
+        return self.c1 % 8 == 0
+
+    def grad_slot(self, tape: Tape, which: str):
+        bn, c0, _shared = self._host
+        return self._grad_of(bn.weight if which == "gamma" else bn.bias)[c0:c0 + self.c2], 1
+
+    def touch_bn(self) -> None:
+        """the block's dgamma / dbeta are complete when BOTH halves have enqueued their backward: only then may the data-parallel hook
+        see them"""
+        bn, _c0, shared = self._host
+        shared["pending"] -= 1
+        if shared["pending"] <= 0:
+            for p in (bn.weight, bn.bias):
+                if p.requires_grad:
+                    config.mark_touched(p)
+
+
+class BottleneckCSP(YdlModule):
+    """models/common.py:128-144: cv4(act(bn(cat(cv3(m(cv1 x)), cv2 x)))), ``cv2`` / ``cv3`` bias-free 1x1 convolutions, ``bn`` over the
+    2 * c_ concatenated channels, ``act`` the block's own SiLU, m = n Bottlenecks (e = 1.0).  Each of cv3 and cv2 runs as a convolution
+    whose launch writes the BatchNorm partial rows of its own output, with a holder that views its half of ``bn``; both activate
+    straight into their halves of the one buffer cv4 reads, so the concat and the BatchNorm cost no pass of their own.  ``c_`` must be a
+    multiple of 8 (the halves are 16-byte channel groups); other widths are refused."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        if c_ % 8 or c_ < 8:
+            raise NotImplementedError(f"BottleneckCSP: c_ = int(c2 * e) = {c_} is not implemented on the HIP path (the two halves of "
+                                      "the concat must be multiples of 8 channels)")
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = _CSPConv2d(c1, c_)
+        self.cv3 = _CSPConv2d(c_, c_)
+        self.cv4 = Conv(2 * c_, c2, 1, 1)
+        self.bn = _BNHolder(2 * c_)
+        self.act = nn.SiLU()
+        self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, e=1.0) for _ in range(n)))
+        self.c_ = c_
+        self._shared = {"pending": 0}
+        self.cv3.attach(self.bn, 0, self._shared)
+        self.cv2.attach(self.bn, c_, self._shared)
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        c_ = self.c_
+        act = _act_code(self.act)
+        if tape.train:
+            self.bn._nbt_pending += 1
+        if tape.record:
+            self._shared["pending"] = 2
+        cat = tape.new(x.N, 2 * c_, x.H, x.W)
+        a = self.cv1._fwd(tape, x)
+        for mm in self.m:
+            a = mm._fwd(tape, a)
+        tape.conv_bn_act(a, self.cv3, 1, 0, act, out=cat.slice(0, c_))
+        tape.conv_bn_act(x, self.cv2, 1, 0, act, out=cat.slice(c_, 2 * c_))
+        return self.cv4._fwd(tape, cat, out=out)
 
 
 # ----------------------------------------------------------------------------------------------------------

@@ -1097,6 +1097,98 @@ class Tape:
             self.bw.append(bw)
         return out
 
+    # ------------------------------------------------------------------ space-to-depth / depth-to-space (csrc/s2d.hip)
+    def _block_permute(self, x: Var, s: int, order: int, out: Optional[Var], down: bool) -> Var:
+        """the body of ``space_to_depth`` (``down``) and ``depth_to_space``: one launch each way, the backward is the opposite entry
+        point into x's gradient with its accumulate flag.  The launcher picks the 16-byte or the element-granular kernel from the raw
+        pointers and strides, so an odd channel slice on either side needs no staging copy."""
+        who = "space_to_depth" if down else "depth_to_space"
+        x = self.materialize(x)
+        s, ss = int(s), int(s) * int(s)
+        if s < 1 or order not in (0, 1):
+            raise RuntimeError(f"{who}: s={s} must be >= 1 and order={order} 0 or 1")
+        if down:
+            if x.H % s or x.W % s:
+                raise RuntimeError(f"{who}: the {x.H} x {x.W} map is not a multiple of s={s}")
+            C, shape = x.C, (x.N, x.C * ss, x.H // s, x.W // s)
+        else:
+            if x.C % ss:
+                raise RuntimeError(f"{who}: {x.C} channels are not a multiple of s*s={ss}")
+            C, shape = x.C // ss, (x.N, x.C // ss, x.H * s, x.W * s)
+        if out is None:
+            out = self.new(*shape, need=x.need, f32=(x.dt == L.YDL_F32))
+        elif (out.N, out.C, out.H, out.W) != shape or out.dt != x.dt:
+            raise RuntimeError(f"{who}: output slice has the wrong shape")
+        fwd, bwd = ("ydl_space_to_depth", "ydl_depth_to_space") if down else ("ydl_depth_to_space", "ydl_space_to_depth")
+        L.call(fwd, x.dt, _p(x.t), x.ld, _p(out.t), out.ld, x.N, x.H, x.W, C, s, order, 0, _stream())
+        if not self.record or not x.need:             # the external image: nothing upstream wants a gradient
+            return out
+        self._use(x)
+
+        def bw():
+            if not out.is_set():
+                return
+            gx, acc = self.grad_target(x)
+            L.call(bwd, x.dt, _p(self._gbuf(out)), out.ld, _p(gx), x.ld, out.N, out.H, out.W, C, s, order, acc, _stream())
+        self.bw.append(bw)
+        return out
+
+    def space_to_depth(self, x: Var, s: int, order: int = 0, out: Optional[Var] = None) -> Var:
+        """(N, C, H, W) -> (N, s*s*C, H/s, W/s): out channel blk*C + c of pixel (ho, wo) is x's channel c at (ho*s + sy, wo*s + sx), with
+        blk = sy*s + sx (``order`` 0: Contract, models/common.py:282-293) or sx*s + sy (``order`` 1: Focus's concat, :241-250).  ``out`` may
+        be a concat slice."""
+        return self._block_permute(x, s, order, out, True)
+
+    def depth_to_space(self, x: Var, s: int, order: int = 0, out: Optional[Var] = None) -> Var:
+        """(N, s*s*C, H, W) -> (N, C, H*s, W*s), the inverse of ``space_to_depth`` (``order`` 0: Expand, models/common.py:296-307)"""
+        return self._block_permute(x, s, order, out, False)
+
+    def bn_act(self, x: Var, m, act: int, out: Optional[Var] = None) -> Var:
+        """out = act(bn(x)) of an existing tensor: BatchNorm that is not the epilogue of its own convolution (a bare nn.BatchNorm2d
+        row).  ``m`` holds ``m.bn`` like a Conv.  Train mode: ydl_bn_stats -> ydl_bn_finalize -> ydl_bn_act_fwd; eval mode:
+        ydl_bn_eval_coeffs -> ydl_bn_act_fwd.  The backward is ydl_bn_act_bwd straight into x's gradient, or through a buffer that is
+        added to it when x has other consumers."""
+        x = self._flat(x)
+        if out is not None and not out.aligned():        # the BatchNorm kernels work on 8-channel groups: stage an odd slice
+            return self.copy(self.bn_act(x, m, act), out)
+        C, cp, npix = x.C, round_up(x.C, 8), x.npix
+        if C != m.bn.num_features:
+            raise RuntimeError(f"BatchNorm2d input channel mismatch: got {C}, the layer has {m.bn.num_features}")
+        if out is None:
+            out = self.new(x.N, C, x.H, x.W)
+        elif (out.N, out.C, out.H, out.W) != (x.N, C, x.H, x.W):
+            raise RuntimeError("bn_act: output slice has the wrong shape")
+        st = _stream()
+        cf = m.coeffs(self.device)
+        if self.train:
+            lib = L.lib()
+            bm = lib.ydl_bn_stats_block_m()
+            ws = torch.empty(lib.ydl_bn_stats_ws_bytes(npix, C) // 4, dtype=torch.float32, device=self.device)
+            L.call("ydl_bn_stats", self.dt, _p(x.t), x.ld, _p(ws), npix, C, st)
+            self._bn_coeffs(m, cf, C, st, (ws, (npix + bm - 1) // bm, bm, npix, 1))
+        else:
+            self._bn_coeffs(m, cf, C, st)
+        self._bn_apply(x, cf["scale"], cf["shift"], act, out, npix, cp, st)
+        if not self.record:
+            return out
+        if not self.train:
+            raise RuntimeError("backward through eval-mode BatchNorm is not supported")
+        if x.need:
+            self._use(x)
+
+        def bw():
+            if not out.is_set() or not (x.need or any(m.trainable()[1:])):
+                return
+            st2 = _stream()
+            gx, acc = self.grad_target(x) if x.need else (None, 1)
+            # first writer of d/dx: the pass writes it in place; otherwise (or when nobody wants it) into a buffer of its own
+            dy = Var(self, gx, x.ld, False) if not acc else self.new(x.N, C, x.H, x.W)
+            self._bn_bwd_rows(m, x, cf, act, out, None, L.RES_NONE, dy, self._bn_grad_rows(m, cp), npix, C, cp, st2)
+            if x.need and acc:
+                L.call("ydl_copy2d", x.dt, _p(dy.t), dy.ld, _p(gx), x.ld, npix, C, 1, st2)
+        self.bw.append(bw)
+        return out
+
     # ------------------------------------------------------------------ learnable activations (csrc/act.hip)
     @staticmethod
     def _param_grad(p: torch.nn.Parameter, device) -> torch.Tensor:
