@@ -716,6 +716,49 @@ int ydl_aug_crop_mask(const void* src, int h, int w, int x1, int y1, int cw, int
 int ydl_fill_zero(void* dst, int64_t bytes, void* stream);
 int ydl_zero2d(int dtype, void* dst, int ldd, int64_t npix, int C, void* stream);
 
+/* ---- prediction path (csrc/predict.hip): label maps, their metrics and pictures ----------------------------------------------
+ * What the reference does with a trained model besides mIoU: unet-lite/Resnet50/test.py:410-464 (SegmentationMetrics),
+ * yolo5-seg/val_diceloss.py:103-119 (overlay), seg_diceloss_yolov5.py:810-830 (mask_to_rgb, visualize_prediction_difference) and
+ * :753-771 (seg_labels_to_class_weights).  Label maps are uint8 with an image stride and a row stride in bytes.  Every entry point
+ * checks its arguments on the host and launches nothing when it refuses them.
+ *
+ * ydl_argmax_labels: labels[n][h*rep_h + i][w*rep_w + j] = argmax_c x[n*sn + c*sc + h*sh + w*sw] for i < rep_h, j < rep_w (the lazy
+ * nearest replication of the tape folded into the store).  x: f32 or bf16 scores with four ELEMENT strides: the tape's NHWC rows
+ * (sc = 1, sw = ld) or an NCHW tensor.  torch.argmax's rule: the first maximum wins, a NaN counts as the maximum and the first NaN
+ * wins.  1 <= C <= 32.  With sc == 1, 16-byte aligned rows and sw >= C rounded up to a 16-byte chunk a thread reads its pixel as
+ * 16-byte vectors, otherwise element by element.  Nothing outside the N * (H*rep_h) rows of W*rep_w bytes is written. */
+int ydl_argmax_labels(int dtype, const void* x, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int N, int C, int H, int W,
+                      int rep_h, int rep_w, uint8_t* labels, int64_t ldl_n, int64_t ldl_h, void* stream);
+/* labels[n][ho][wo] = argmax_c bilinear_resize(softmax_c(x))[n][c][ho][wo], align_corners = False, (Hi, Wi) -> (Ho, Wo): the exit of
+ * a model whose last Softmax is followed by the resize to its output size, without writing the probabilities or their resized copy.
+ * x: NHWC rows of ldx elements, f32 or bf16.  The f32 arithmetic is ydl_softmax_fwd's followed by ydl_resize_fwd's (mode 1),
+ * expression for expression: the labels are the argmax of the very values those two launches would have produced. */
+int ydl_softmax_resize_labels(int dtype, const void* x, int ldx, int N, int C, int Hi, int Wi, int Ho, int Wo,
+                              uint8_t* labels, int64_t ldl_n, int64_t ldl_h, void* stream);
+/* dst[n][i][j] = src[n][y0 + si][x0 + sj]: the crop box (y0, x0, hc, wc) of every image resized to Ho x Wo by ATen's nearest rule,
+ * si = min((int)floorf(i * ((float)hc / Ho)), hc - 1) in f32, sj likewise (F.interpolate(mode='nearest') of the box).  With the box
+ * = letterbox_geometry's interior and (Ho, Wo) = the source image's size this undoes the letterbox.  (test.py:419-424 is NOT this:
+ * its unsqueeze(0) makes the call a 1-D resize along the width, and it raises for int64 predictions.) */
+int ydl_labels_resize(const uint8_t* src, int64_t lds_n, int64_t lds_h, int N, int y0, int x0, int hc, int wc,
+                      uint8_t* dst, int64_t ldd_n, int64_t ldd_h, int Ho, int Wo, void* stream);
+/* matrix[t][p] += 1 over the pixels of two label maps (int64 [C][C], rows = target).  target: uint8, or int64 with
+ * target_is_i64 != 0, strides in elements.  A pixel is dropped when t < 0, t >= C, t == ignore_index or p >= C
+ * (val_diceloss.py:50-58, test.py:431); ignore_index = -1 ignores nothing.  1 <= C <= 32. */
+int ydl_confusion_labels(const uint8_t* pred, int64_t ldp_n, int64_t ldp_h, const void* target, int target_is_i64,
+                         int64_t ldt_n, int64_t ldt_h, int N, int H, int W, int C, int ignore_index, int64_t* matrix, void* stream);
+/* counts[v] += 1 for each of the n labels (uint8, or int64 with is_i64 != 0); counts holds nbins + 1 int64, the last entry collects
+ * the labels outside [0, nbins).  1 <= nbins <= 4096. */
+int ydl_label_bincount(const void* labels, int is_i64, int64_t n, int nbins, int64_t* counts, void* stream);
+/* out: uint8 [N][H][W][3]; pred / target: dense uint8 [N][H][W]; palette: uint8 [npal][3], npal <= 256.
+ *   mode 0, colour (mask_to_rgb):  palette[pred], (0,0,0) where pred >= npal
+ *   mode 1, difference (visualize_prediction_difference):  (255,0,255) where pred != target, else as mode 0
+ *   mode 2, overlay (val_diceloss.py:103-119): base = uint8(img * 255) by truncation (img: f32 [N][3][H][W], the product in f32,
+ *           values outside [0, 255] saturate); out = rint(0.5 * base + 0.5 * colour), half to even.  With bgr != 0 the base's
+ *           channels are swapped and the palette triple is written unswapped, as the reference does.  The rounding is OpenCV's
+ *           documented saturate_cast<uchar>(float); it has not been pinned against a cv2 build. */
+int ydl_labels_render(int mode, const uint8_t* pred, const uint8_t* target, const float* img, const uint8_t* palette, int npal,
+                      uint8_t* out, int N, int H, int W, int bgr, void* stream);
+
 /* ---- activations with a run-time parameter ----------------------------------------------------------------------------
  * The six streaming BatchNorm entry points above, each with one more argument after `act`: act_param, the parameter of the
  * activation (the negative slope of YDL_ACT_LEAKY; ignored by every other code).  The entry points without it are these with

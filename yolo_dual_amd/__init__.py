@@ -20,6 +20,9 @@ from .modules import (GAM, AttentionConv, AttentionStem, C2f, C3, C3k2, C3_DCNV3
 from .deform import deform_conv2d
 from . import activations
 from .activations import AconC, FReLU, Hardswish, MemoryEfficientMish, MetaAconC, Mish, SiLU
+from . import predict
+from .predict import (SegmentationMetrics, argmax_labels, colorize, default_palette, difference, label_class_weights, overlay,
+                      predict_labels, unletterbox_labels)
 from .optim import FlatAdamEMA, FlatAdamWEMA, FlatArenaOptimizer, FlatRMSPropEMA, FlatSGDEMA, smart_optimizer
 
 __all__ = [n for n in dir() if not n.startswith("_")]

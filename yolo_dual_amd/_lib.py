@@ -197,6 +197,12 @@ SIGNATURES = {
     "ydl_acon_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i64, _i64, _i, _i, _vp]),
     "ydl_max2_fwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp]),
     "ydl_max2_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i64, _i, _vp]),
+    "ydl_argmax_labels": (_i, [_i, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _vp]),
+    "ydl_softmax_resize_labels": (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _vp]),
+    "ydl_labels_resize": (_i, [_vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _i64, _i64, _i, _i, _vp]),
+    "ydl_confusion_labels": (_i, [_vp, _i64, _i64, _vp, _i, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ydl_label_bincount": (_i, [_vp, _i, _i64, _i, _vp, _vp]),
+    "ydl_labels_render": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "ydl_replay_create": (_vp, []),
     "ydl_replay_destroy": (None, [_vp]),
     "ydl_replay_fn_count": (_i, []),

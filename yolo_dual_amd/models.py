@@ -206,10 +206,20 @@ class _YamlSegModel(YdlModule):
             if isinstance(layer, Softmax):
                 H, W = self.img_size
                 if i == n_head - 1 and (inp.LH, inp.LW) == (H, W):
-                    p = tape.softmax_nchw(inp)          # final layer, already at img_size: write NCHW f32 directly
-                    tape.ext = (inp, p)
+                    if tape.labels_out:                 # argmax commutes with the softmax: labels straight from the stored scores
+                        p = tape.export_labels(inp)
+                    else:
+                        p = tape.softmax_nchw(inp)      # final layer, already at img_size: write NCHW f32 directly
+                        tape.ext = (inp, p)
                     if use_side:
                         stream_wait(main, side)          # the dead branch has finished before the region returns
+                    return p
+                if i == n_head - 1 and tape.labels_out:
+                    # final layer at another size (the v8 family's fixed 256 x 256): the bilinear resize to img_size below does not
+                    # commute with the argmax, so softmax, resize and argmax run as one launch that writes the labels only
+                    p = tape.export_labels_softmax_resized(inp, H, W)
+                    if use_side:
+                        stream_wait(main, side)
                     return p
                 x = tape.softmax(inp)
             else:

@@ -258,6 +258,7 @@ class Tape:
         self._pending_wgrad: List[Callable] = []   # weight-gradient launches waiting for the next fork of the side stream
         self._bw_left = 0
         self.ext = None      # (Var, tensor) of a region whose external output was written directly (softmax head)
+        self.labels_out = False   # the caller wants the label map of the output only (yolo_dual_amd.predict): see export_labels
         self._slab = None    # zero-initialised f32 scratch of the region: accumulator rows the kernels add into (BN replica sums)
         self._slab_off = 0
         self._slab_total = 0         # floats handed out so far (the owner module remembers it as next step's slab size)
@@ -480,6 +481,26 @@ class Tape:
         v = self.materialize(v)
         out = torch.empty((v.N, v.C, v.H, v.W), dtype=torch.float32, device=self.device)
         L.call("ydl_nhwc_to_nchw", v.dt, _p(v.t), v.ld, _p(out), v.N, v.C, v.H, v.W, 0, _stream())
+        return out
+
+    def export_labels(self, v: Var) -> torch.Tensor:
+        """argmax over the channels of ``v`` as a uint8 (N, LH, LW) label map (ydl_argmax_labels).  The scores are read where they
+        are stored, NHWC in the compute dtype and at the resolution before a lazy nearest up-sampling; the replication is folded
+        into the store, so neither ydl_nhwc_to_nchw nor the replication kernel runs."""
+        if v.virtual:
+            v = self.materialize(v)
+        out = torch.empty((v.N, v.LH, v.LW), dtype=torch.uint8, device=self.device)
+        sn, sc, sh, sw = v.t.stride()
+        L.call("ydl_argmax_labels", v.dt, _p(v.t), sn, sc, sh, sw, v.N, v.C, v.H, v.W, v.rep[0], v.rep[1], _p(out), v.LH * v.LW, v.LW,
+               _stream())
+        return out
+
+    def export_labels_softmax_resized(self, v: Var, Ho: int, Wo: int) -> torch.Tensor:
+        """argmax of ``resize(softmax(v), Ho, Wo, bilinear)`` as a uint8 (N, Ho, Wo) label map, in one launch that writes neither
+        the probabilities nor their resized copy (ydl_softmax_resize_labels): the labels of softmax + Tape.resize + export_nchw"""
+        v = self.materialize(v)           # (a channel slice is fine: the kernel reads a row element by element from its first channel)
+        out = torch.empty((v.N, Ho, Wo), dtype=torch.uint8, device=self.device)
+        L.call("ydl_softmax_resize_labels", v.dt, _p(v.t), v.ld, v.N, v.C, v.H, v.W, Ho, Wo, _p(out), Ho * Wo, Wo, _stream())
         return out
 
     def seed_grad_nchw(self, v: Var, g: torch.Tensor) -> None:
