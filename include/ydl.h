@@ -445,7 +445,9 @@ int ydl_sgd_ema_step_dev(float* params, const float* grads, float* momentum, flo
 
 /* every run of one step in one launch: runs_dev = device int64[nruns][6] rows {offset (elements into all four arenas), n_decay,
  * n_params, n_total, lr_index, flags: bit 0 weight decay, bit 1 first step}, each row with the meaning of the arguments of
- * ydl_sgd_ema_step_dev applied at `offset`; max_run = the largest n_total (grid sizing). */
+ * ydl_sgd_ema_step_dev applied at `offset`; max_run = the largest n_total (grid sizing).  The arenas are 16-byte aligned
+ * (refused otherwise: the walk reads them in 16-byte groups); the rows are read on the device unchecked: the caller keeps them
+ * inside the arenas. */
 int ydl_sgd_ema_step_multi(float* params, const float* grads, float* momentum, float* ema, const int64_t* runs_dev,
                            int nruns, int64_t max_run, const float* hyper_dev, int use_ema, void* stream);
 

@@ -1,6 +1,7 @@
 """GPU: the fused Adam / AdamW / RMSProp + EMA steps (csrc/optim.hip, yolo_dual_amd/optim.py) against ``torch.optim`` itself — the
 single-tensor CPU path the reference's ``smart_optimizer`` runs — and through every consumer of the optimizer protocol: the
-one-launch run table, the launch-list replay, checkpoints, data parallelism and the CLI.
+one-launch run table, the launch-list replay, checkpoints, data parallelism and the CLI.  The three entry forms of every rule of
+the family, SGD among them, are held to each other bit for bit.
 
 Tolerance of the trajectory tests: the error is measured against float64 torch.optim on the same f32 inputs, relative to the distance
 the parameters moved, and the HIP error may be at most 4x the error of torch's OWN f32 run measured in the same test (room for FMA
@@ -195,55 +196,152 @@ def test_skipped_and_late_parameters(name):
     assert eerr_hip <= 4.0 * eerr_f32, (eerr_hip, eerr_f32)
 
 
+def _hyper_vector(name):
+    """device hyper vector of a rule (ydl.h) with three bias-correction classes, and the same f32 values as Python floats"""
+    from yolo_dual_amd import _lib as L
+    lrs, b1, b2, wd = (0.01, 0.02, 0.03), 0.9, 0.999, 5e-4
+    vals = [*lrs, b1, wd, 0.5, 0.999]
+    if name != "SGD":
+        vals += [b2, 1e-8, 1.0 - b1, 1.0 - b2, 1.0 - lrs[0] * wd] + [0.0] * (L.OPT_HYPER_FLOATS - 12)
+        for c, t in enumerate((1, 5, 12)):
+            for i in range(3):
+                vals[12 + 4 * c + i] = lrs[i] / (1.0 - b1 ** t)
+            vals[12 + 4 * c + 3] = (1.0 - b2 ** t) ** 0.5
+    hyper_cpu = torch.tensor(vals, dtype=torch.float64).float()
+    return hyper_cpu.cuda(), [float(v) for v in hyper_cpu]
+
+
+def _entry(name):
+    return ("ydl_sgd_ema_step", ()) if name == "SGD" else ("ydl_optim_ema_step", (RULES[name],))
+
+
+def _step_multi(name, arrs, rows, hyper, use_ema):
+    """all rows in one launch; ``arrs`` = [params, grads, state arena(s), ema]"""
+    from yolo_dual_amd import _lib as L
+    from yolo_dual_amd.tape import _p, _stream
+    entry, rule = _entry(name)
+    tab = torch.tensor(rows, dtype=torch.int64).cuda()
+    L.call(entry + "_multi", *rule, *[_p(x) for x in arrs[:-1]], _p(arrs[-1]) if use_ema else None, _p(tab), len(rows),
+           max(r[3] for r in rows), _p(hyper), use_ema, _stream())
+    torch.cuda.synchronize()                               # the table is a local
+
+
+def _step_runs(name, form, arrs, rows, hyper, h, use_ema):
+    """the same rows one launch each, through the device-hyper (``dev``) or the host-scalar (``host``) entry point"""
+    from yolo_dual_amd import _lib as L
+    from yolo_dual_amd.tape import _p, _stream
+    entry, rule = _entry(name)
+    for row in rows:
+        off, nd, npar, n, gi, fl = row[:6]
+        if npar == 0 and not use_ema:
+            continue
+        ptrs = [_p(x[off:]) for x in arrs[:-1]] + [_p(arrs[-1][off:]) if use_ema else None]
+        d = h[6] if use_ema else -1.0
+        if form == "dev":
+            tail = (gi, fl & 1, (fl >> 1) & 1) if name == "SGD" else (gi, row[6], fl & 1)
+            L.call(entry + "_dev", *rule, *ptrs, nd, npar, n, _p(hyper), *tail, use_ema, _stream())
+        elif name == "SGD":
+            L.call(entry, *ptrs, nd, npar, n, h[gi], h[gi], h[3], h[4] if fl & 1 else 0.0, h[5], (fl >> 1) & 1, d, _stream())
+        else:
+            c = row[6]
+            step_size = h[gi] if name == "RMSProp" else h[12 + 4 * c + gi]
+            L.call(entry, *rule, *ptrs, nd, npar, n, step_size, h[12 + 4 * c + 3], h[11], h[4] if fl & 1 else 0.0, h[3], h[7], h[9], h[10],
+                   h[8], h[5], d, _stream())
+
+
+def _check_three_forms(name, base, rows):
+    """multi == dev run by run == host scalars run by run, bit for bit on every array, with and without EMA"""
+    hyper, h = _hyper_vector(name)
+    assert rows[-1][0] + rows[-1][3] == base[0].numel() and all(a[0] + a[3] == b[0] for a, b in zip(rows, rows[1:]))
+    for use_ema in (1, 0):
+        a, b, c = ([t.clone() for t in base] for _ in range(3))
+        _step_multi(name, a, rows, hyper, use_ema)
+        _step_runs(name, "dev", b, rows, hyper, h, use_ema)
+        _step_runs(name, "host", c, rows, hyper, h, use_ema)
+        torch.cuda.synchronize()
+        for x, y, z in zip(a, b, c):
+            assert torch.equal(x, y) and torch.equal(x, z)
+        assert torch.equal(a[1], base[1]) and all(not torch.equal(x, y) for x, y in zip(a[:-1], base[:-1]) if x is not a[1])
+        assert torch.equal(a[-1], base[-1]) != bool(use_ema)
+        assert bool(torch.isfinite(a[0]).all())
+
+
+def _arrays(n, count, seed=3):
+    gen = torch.Generator("cuda").manual_seed(seed)
+    return [torch.randn(n, device="cuda", generator=gen) for _ in range(count)]
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_multi_run_launch_equals_the_per_run_launches(name):
     """ydl_optim_ema_step_multi (one launch, float4 groups aligned to the arena, element form at the run ends) against
     ydl_optim_ema_step_dev run by run and against the host-scalar ydl_optim_ema_step, bit for bit — runs at offsets that are not
     multiples of four, of lengths 1..5 and large, with and without weight decay, EMA-only rows, three bias-correction classes"""
-    from yolo_dual_amd import _lib as L
-    from yolo_dual_amd.tape import _p, _stream
-    rule = RULES[name]
-    n_tot = 70001
-    gen = torch.Generator("cuda").manual_seed(3)
-    base = [torch.randn(n_tot, device="cuda", generator=gen) for _ in range(5)]
+    base = _arrays(70001, 5)
     base[3] = base[3].abs()                                # exp_avg_sq / square_avg are sums of squares
-    lrs, b1, b2, wd = (0.01, 0.02, 0.03), 0.9, 0.999, 5e-4
-    vals = [0.0] * L.OPT_HYPER_FLOATS
-    vals[:12] = [*lrs, b1, wd, 0.5, 0.999, b2, 1e-8, 1.0 - b1, 1.0 - b2, 1.0 - lrs[0] * wd]
-    for c, t in enumerate((1, 5, 12)):
-        for i in range(3):
-            vals[12 + 4 * c + i] = lrs[i] / (1.0 - b1 ** t)
-        vals[12 + 4 * c + 3] = (1.0 - b2 ** t) ** 0.5
-    hyper_cpu = torch.tensor(vals, dtype=torch.float64).float()
-    hyper = hyper_cpu.cuda()
     # (offset, n_decay, n_params, n_total, lr index, flags, class, 0)
     rows = [(0, 3, 3, 3, 0, 1, 0, 0), (3, 0, 5, 5, 1, 0, 1, 0), (8, 0, 0, 1, 0, 0, 0, 0), (9, 30001, 30001, 30001, 0, 1, 2, 0),
             (30010, 0, 20002, 20002, 2, 0, 1, 0), (50012, 2, 2, 2, 0, 1, 1, 0), (50014, 0, 4, 4, 2, 0, 0, 0), (50018, 0, 0, 19983, 0, 0, 0, 0)]
-    assert rows[-1][0] + rows[-1][3] == n_tot and all(a[0] + a[3] == b[0] for a, b in zip(rows, rows[1:]))
-    tab = torch.tensor(rows, dtype=torch.int64).cuda()
-    st = _stream()
-    h = [float(v) for v in hyper_cpu]
-    for use_ema in (1, 0):
-        pa, ga, sa, va, ea = [t.clone() for t in base]
-        L.call("ydl_optim_ema_step_multi", rule, _p(pa), _p(ga), _p(sa), _p(va), _p(ea) if use_ema else None, _p(tab), len(rows),
-               max(r[3] for r in rows), _p(hyper), use_ema, st)
-        pb, gb, sb, vb, eb = [t.clone() for t in base]
-        pc, gc, sc, vc, ec = [t.clone() for t in base]
-        for off, nd, npar, n, gi, fl, c, _z in rows:
-            if npar == 0 and not use_ema:
-                continue
-            L.call("ydl_optim_ema_step_dev", rule, _p(pb[off:]), _p(gb[off:]), _p(sb[off:]), _p(vb[off:]), _p(eb[off:]) if use_ema else None,
-                   nd, npar, n, _p(hyper), gi, c, fl & 1, use_ema, st)
-            step_size = h[gi] if name == "RMSProp" else h[12 + 4 * c + gi]
-            L.call("ydl_optim_ema_step", rule, _p(pc[off:]), _p(gc[off:]), _p(sc[off:]), _p(vc[off:]), _p(ec[off:]) if use_ema else None,
-                   nd, npar, n, step_size, h[12 + 4 * c + 3], h[11], h[4] if fl & 1 else 0.0, h[3], h[7], h[9], h[10], h[8], h[5],
-                   h[6] if use_ema else -1.0, st)
+    _check_three_forms(name, base, rows)
+
+
+def test_multi_run_optimizer_launch_equals_the_per_run_launches():
+    """the same for SGD: ydl_sgd_ema_step_multi against ydl_sgd_ema_step_dev and the host-scalar ydl_sgd_ema_step run by run, bit
+    for bit on parameters, momentum, EMA and the untouched gradients — rows of lengths 1..5 at offsets 1, 2 and 3 mod 4 and large,
+    with and without weight decay / first step (also a first-step row without decay), EMA-only rows between them"""
+    base = _arrays(70001, 4)
+    # (offset, n_decay, n_params, n_total, lr index, flags: 1 weight decay | 2 first step)
+    rows = [(0, 3, 3, 3, 0, 1), (3, 0, 5, 5, 1, 0), (8, 0, 0, 1, 0, 0), (9, 30001, 30001, 30001, 0, 1 | 2), (30010, 0, 20002, 20002, 2, 0),
+            (50012, 0, 1, 1, 1, 2), (50013, 5, 5, 5, 0, 1), (50018, 0, 4, 4, 2, 2), (50022, 0, 0, 1, 0, 0), (50023, 2, 2, 2, 0, 1 | 2),
+            (50025, 0, 3, 3, 1, 0), (50028, 0, 2, 2, 2, 0), (50030, 1, 1, 1, 0, 1), (50031, 0, 0, 19970, 0, 0)]
+    assert {(r[0] % 4, r[3]) for r in rows} >= {(1, 5), (2, 4), (3, 2), (1, 3), (2, 1)}
+    _check_three_forms("SGD", base, rows)
+
+
+def test_sgd_host_scalar_step_keeps_two_learning_rates():
+    """one ydl_sgd_ema_step over [decay | no decay | buffers] (n_decay 3 < n_params 7 < n_total 9) with a learning rate per part
+    equals, bit for bit, the three ranges stepped one uniform call each — at an arena offset that is not a multiple of four, on a
+    first and on a later step"""
+    from yolo_dual_amd import _lib as L
+    from yolo_dual_amd.tape import _p, _stream
+    base = _arrays(16, 4, seed=4)
+    lr0, lr1, mom, wd, gs, d, off = 0.01, 0.07, 0.9, 5e-4, 0.5, 0.999, 5
+    for first in (1, 0):
+        a, b = ([t.clone() for t in base] for _ in range(2))
+        L.call("ydl_sgd_ema_step", *[_p(x[off:]) for x in a], 3, 7, 9, lr0, lr1, mom, wd, gs, first, d, _stream())
+        for o, nd, npar, n, lr in ((off, 3, 3, 3, lr0), (off + 3, 0, 4, 4, lr1), (off + 7, 0, 0, 2, 0.0)):
+            L.call("ydl_sgd_ema_step", *[_p(x[o:]) for x in b], nd, npar, n, lr, lr, mom, wd, gs, first, d, _stream())
         torch.cuda.synchronize()
-        for x, y, z in ((pa, pb, pc), (sa, sb, sc), (va, vb, vc), (ea, eb, ec), (ga, gb, gc)):
-            assert torch.equal(x, y) and torch.equal(x, z)
-        assert torch.equal(ga, base[1]) and not torch.equal(pa, base[0]) and not torch.equal(va, base[3])
-        assert torch.equal(ea, base[4]) != bool(use_ema)
-        assert bool(torch.isfinite(pa).all())
+        for x, y, z in zip(a, b, base):
+            assert torch.equal(x, y) and torch.equal(x[:off], z[:off]) and torch.equal(x[off + 9:], z[off + 9:])
+        assert torch.equal(a[1], base[1]) and not torch.equal(a[0][off:off + 7], base[0][off:off + 7])
+        assert torch.equal(a[0][off + 7:], base[0][off + 7:]) and not torch.equal(a[3][off:off + 9], base[3][off:off + 9])
+
+
+@pytest.mark.parametrize("name", ("SGD", "AdamW"))
+def test_per_run_launches_on_arrays_that_are_not_co_aligned(name):
+    """the per-run forms with the gradient array one element out of step with the others (a view from element 1 of a longer tensor)
+    cannot rebase onto a common 16-byte boundary and take the element walk: bit for bit the multi launch on co-aligned copies"""
+    n = 4099
+    base = _arrays(n, 4 if name == "SGD" else 5)
+    base[-2] = base[-2].abs()                              # the adaptive rule's sums of squares (SGD: its momentum, any sign would do)
+    cols, none = ((), ()) if name == "SGD" else ((1, 0), (0, 0))          # the family's rows go on with {class, 0}
+    rows = [(0, 1501, 1501, 1501, 0, 1) + cols, (1501, 0, 1300, 1300, 1, 0) + cols, (2801, 0, 0, 298, 0, 0) + none,
+            (3099, 0, 1000, 1000, 2, 0) + cols]
+    hyper, h = _hyper_vector(name)
+    for use_ema in (1, 0):
+        a = [t.clone() for t in base]
+        _step_multi(name, a, rows, hyper, use_ema)
+        for form in ("dev", "host"):
+            b = [t.clone() for t in base]
+            longer = torch.zeros(n + 1, device="cuda")
+            longer[1:].copy_(base[1])
+            b[1] = longer[1:]
+            assert b[1].data_ptr() % 16 == 4 and all(x.data_ptr() % 16 == 0 for x in b if x is not b[1])
+            _step_runs(name, form, b, rows, hyper, h, use_ema)
+            torch.cuda.synchronize()
+            for x, y in zip(a, b):
+                assert torch.equal(x, y), form
+            assert float(longer[0]) == 0.0 and torch.equal(b[1], base[1]) and not torch.equal(b[0], base[0])
 
 
 class _TorchConv(nn.Module):

@@ -106,7 +106,8 @@ def test_state_of_another_rule_or_model_is_refused():
 
 
 def test_new_entry_points_validate_on_the_host():
-    """null pointers, a bad arena partition, an unknown rule, a bad class / lr index and too many runs are refused before any launch"""
+    """null pointers, a bad arena partition, an unknown rule, a bad class / lr index, too many runs and arenas of the run-table
+    forms (the family's and SGD's) that are not 16-byte aligned are refused before any launch"""
     from yolo_dual_amd import _lib as L
     lib = L.lib()
     vp = ctypes.c_void_p
@@ -134,6 +135,7 @@ def test_new_entry_points_validate_on_the_host():
     assert lib.ydl_optim_ema_step_multi(-1, ptr, ptr, ptr, ptr, None, ptr, 1, 4, ptr, 0, None) != 0 and "rule" in err()
     off4 = vp(ctypes.addressof(buf) + 4)
     assert lib.ydl_optim_ema_step_multi(L.OPT_ADAM, off4, ptr, ptr, ptr, None, ptr, 1, 4, ptr, 0, None) != 0 and "aligned" in err()
+    assert lib.ydl_sgd_ema_step_multi(off4, ptr, ptr, None, ptr, 1, 4, ptr, 0, None) != 0 and "aligned" in err()
 
 
 def test_host_numbers_follow_torch_in_double_precision():

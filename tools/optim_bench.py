@@ -70,8 +70,9 @@ def main():
         us = statistics.median(ts)
         nbytes = 4.0 * WORDS[name] * opt.n_params      # nominal: the few dead parameters and the float buffers stream 3 words (EMA only)
         res[name] = (us, nbytes / us / 1e3)
+        q1, _q2, q3 = statistics.quantiles(ts, n=4)
         print(f"{name:8s} runs {len(rows):3d}  params {opt.n_params}  live {live}  total {opt.n_total} | median {us:7.1f} us "
-              f"(min {min(ts):.1f}, max {max(ts):.1f}) | {WORDS[name]} words/param | {res[name][1]:7.1f} GB/s", flush=True)
+              f"(min {min(ts):.1f}, IQR {q3 - q1:.1f}, max {max(ts):.1f}) | {WORDS[name]} words/param | {res[name][1]:7.1f} GB/s", flush=True)
         del m, opt
         torch.cuda.empty_cache()
     for name in ("Adam", "AdamW", "RMSProp"):

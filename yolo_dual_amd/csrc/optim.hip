@@ -1,5 +1,6 @@
-// Weight re-layout (f32 KRSC master -> compute copies), wgrad un-padding, and the fused SGD(nesterov)+EMA step
-// over flat arenas (utils/torch_utils.py:318-346 smart_optimizer groups, :404-428 ModelEMA.update).
+// Weight re-layout (f32 KRSC master -> compute copies), wgrad un-padding, and the fused optimizer+EMA step over flat arenas
+// (utils/torch_utils.py:318-346 smart_optimizer groups, :404-428 ModelEMA.update): SGD(nesterov), Adam, AdamW and RMSProp as four
+// rules of one walk and one set of three kernels (host scalars, device hyper vector, run table).
 #include "common.h"
 
 // w[co][t][ci_p] = master[co][t][ci] (zero pad);  wt[ci][t][co_p] = master[co][t][ci]
@@ -197,82 +198,16 @@ extern "C" int ydl_wgrad_unpack_s2d(const float* dw2, float* grad, int Cout, int
     return 0;
 }
 
-// One pass over [params | buffers]: SGD-nesterov on params (two lr/decay groups), EMA on everything.
+// ---- SGD(nesterov) / Adam / AdamW / RMSProp + EMA over the flat arenas: one family, four rules ------------------------------------
+// One streaming pass over [params | buffers]: the rule on the parameters (two lr / decay groups), the EMA on everything.  Seven
+// words per parameter for SGD (p rw, g r, momentum rw, ema rw), nine for the others (state1 rw, state2 rw).  The three entry forms
+// (host scalars, device hyper vector, run table) of every rule share ONE element function and ONE walk, so that they agree bit for
+// bit.
+//
+// SGD, torch.optim.SGD(nesterov=True) (utils/torch_utils.py:318-346):
 //   g = grad*grad_scale + wd*p ; buf = first ? g : mom*buf + g ; p -= lr*(g + mom*buf) ; ema = d*ema + (1-d)*p
-__global__ __launch_bounds__(256) void sgd_ema_kernel(float* __restrict__ params, const float* __restrict__ grads,
-                                                      float* __restrict__ mombuf, float* __restrict__ ema,
-                                                      long long n_decay, long long n_params, long long n_total,
-                                                      float lr0, float lr1, float mom, float wd, float gscale, int first, float d) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_total; i += (long long)gridDim.x * blockDim.x) {
-        float p = params[i];
-        if (i < n_params) {
-            bool dec = i < n_decay;
-            float g = grads[i] * gscale;
-            if (dec && wd != 0.f) g = g + wd * p;
-            float b = first ? g : mom * mombuf[i] + g;
-            mombuf[i] = b;
-            float upd = g + mom * b;
-            p = p - (dec ? lr0 : lr1) * upd;
-            params[i] = p;
-        }
-        if (d >= 0.f && ema != nullptr) {
-            float e = ema[i];
-            e = e * d;
-            e = e + (1.f - d) * p;
-            ema[i] = e;
-        }
-    }
-}
-
-extern "C" int ydl_sgd_ema_step(float* params, const float* grads, float* momentum, float* ema,
-                                int64_t n_decay, int64_t n_params, int64_t n_total,
-                                float lr_decay_group, float lr_nodecay_group, float mom, float weight_decay, float grad_scale,
-                                int first_step, float ema_decay, void* stream) {
-    YDL_CHECK(params && grads && momentum, "null pointer");
-    YDL_CHECK(0 <= n_decay && n_decay <= n_params && n_params <= n_total, "bad arena partition");
-    int grid = (int)((n_total + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    sgd_ema_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(params, grads, momentum, ema, n_decay, n_params, n_total,
-                                                           lr_decay_group, lr_nodecay_group, mom, weight_decay, grad_scale,
-                                                           first_step, ema_decay);
-    YDL_LAUNCH_CHECK();
-    return 0;
-}
-
-
-// Same update with the hyper-parameters read from DEVICE memory, so that the launch can live inside a captured HIP graph
-// while lr / EMA decay change every step.  hyper = {lr_weights, lr_bn, lr_bias, momentum, weight_decay, grad_scale, ema_d}
-__global__ __launch_bounds__(256) void sgd_ema_dev_kernel(float* __restrict__ params, const float* __restrict__ grads,
-                                                          float* __restrict__ mombuf, float* __restrict__ ema,
-                                                          long long n_decay, long long n_params, long long n_total,
-                                                          const float* __restrict__ hyper, int lr_idx, int use_wd, int first,
-                                                          int use_ema) {
-    const float lr = hyper[lr_idx], mom = hyper[3], wd = use_wd ? hyper[4] : 0.f, gscale = hyper[5], d = hyper[6];
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_total; i += (long long)gridDim.x * blockDim.x) {
-        float p = params[i];
-        if (i < n_params) {
-            bool dec = i < n_decay;
-            float g = grads[i] * gscale;
-            if (dec && wd != 0.f) g = g + wd * p;
-            float b = first ? g : mom * mombuf[i] + g;
-            mombuf[i] = b;
-            float upd = g + mom * b;
-            p = p - lr * upd;
-            params[i] = p;
-        }
-        if (use_ema && ema != nullptr) {
-            float e = ema[i];
-            e = e * d;
-            e = e + (1.f - d) * p;
-            ema[i] = e;
-        }
-    }
-}
-
-// All runs of one optimizer step in ONE launch: grid row y handles run y = {offset, n_decay, n_params, n_total, lr_index,
-// flags (bit 0 weight decay, bit 1 first step)} of the device table (the per-run launches of the dead / live / BN / bias / buffer
-// ranges cost ~7 us each, nine of them per step on BASELINE config 2).  Same arithmetic as sgd_ema_dev_kernel.
+// Its element function is compiled like the rest of the library, with -ffp-contract=on: the SOURCE expressions decide which
+// products fuse (five fused multiply-adds and two multiplies per element), in every inlining context alike.
 __device__ __forceinline__ void sgd_ema_elem(float& p, float g, float& b, float& e, bool is_param, bool dec, bool first, bool use_ema,
                                              float lr, float mom, float wd, float gscale, float d) {
     if (is_param) {
@@ -287,87 +222,17 @@ __device__ __forceinline__ void sgd_ema_elem(float& p, float g, float& b, float&
         e = e + (1.f - d) * p;
     }
 }
-__global__ __launch_bounds__(256) void sgd_ema_multi_kernel(float* __restrict__ params, const float* __restrict__ grads,
-                                                            float* __restrict__ mombuf, float* __restrict__ ema,
-                                                            const long long* __restrict__ runs, const float* __restrict__ hyper,
-                                                            int use_ema) {
-    const long long* r = runs + (size_t)blockIdx.y * 6;
-    const long long off = r[0], n_decay = r[1], n_params = r[2], n_total = r[3];
-    const int lr_idx = (int)r[4], flags = (int)r[5];
-    const bool first = (flags >> 1) & 1;
-    const float lr = hyper[lr_idx], mom = hyper[3], wd = (flags & 1) ? hyper[4] : 0.f, gscale = hyper[5], d = hyper[6];
-    const bool ue = use_ema && ema != nullptr;
-    // 16 bytes per lane and stream (seven streams: p rw, g r, momentum rw, ema rw): the run is walked in float4 groups aligned to the
-    // ARENA (so every access is 16-byte aligned whatever the run's offset); the groups that straddle the run's ends, and runs whose
-    // decay / parameter boundary is not the whole run, take the element form.  Same arithmetic per element either way.
-    const long long a0 = off & ~3ll, end = off + n_total;
-    const bool uniform = (n_params == n_total || n_params == 0) && (n_decay == n_params || n_decay == 0);
-    for (long long q = a0 + 4 * ((long long)blockIdx.x * blockDim.x + threadIdx.x); q < end; q += 4ll * gridDim.x * blockDim.x) {
-        if (uniform && q >= off && q + 4 <= end) {
-            const bool isp = n_params != 0, dec = n_decay != 0;
-            float4 p4 = *(const float4*)(params + q), g4 = make_float4(0.f, 0.f, 0.f, 0.f), b4 = g4, e4 = g4;
-            if (isp) { g4 = *(const float4*)(grads + q); if (!first) b4 = *(const float4*)(mombuf + q); }
-            if (ue) e4 = *(const float4*)(ema + q);
-            sgd_ema_elem(p4.x, g4.x, b4.x, e4.x, isp, dec, first, ue, lr, mom, wd, gscale, d);
-            sgd_ema_elem(p4.y, g4.y, b4.y, e4.y, isp, dec, first, ue, lr, mom, wd, gscale, d);
-            sgd_ema_elem(p4.z, g4.z, b4.z, e4.z, isp, dec, first, ue, lr, mom, wd, gscale, d);
-            sgd_ema_elem(p4.w, g4.w, b4.w, e4.w, isp, dec, first, ue, lr, mom, wd, gscale, d);
-            if (isp) { *(float4*)(params + q) = p4; *(float4*)(mombuf + q) = b4; }
-            if (ue) *(float4*)(ema + q) = e4;
-        } else {
-            for (int k = 0; k < 4; ++k) {
-                const long long i = q + k - off;
-                if (i < 0 || i >= n_total) continue;
-                const bool isp = i < n_params;
-                float p = params[off + i], g = 0.f, b = 0.f, e = 0.f;
-                if (isp) { g = grads[off + i]; if (!first) b = mombuf[off + i]; }
-                if (ue) e = ema[off + i];
-                sgd_ema_elem(p, g, b, e, isp, i < n_decay, first, ue, lr, mom, wd, gscale, d);
-                if (isp) { params[off + i] = p; mombuf[off + i] = b; }
-                if (ue) ema[off + i] = e;
-            }
-        }
-    }
-}
 
-extern "C" int ydl_sgd_ema_step_multi(float* params, const float* grads, float* momentum, float* ema, const int64_t* runs_dev,
-                                      int nruns, int64_t max_run, const float* hyper_dev, int use_ema, void* stream) {
-    YDL_CHECK(params && grads && momentum && runs_dev && hyper_dev && nruns > 0 && nruns <= 65535 && max_run >= 0, "bad arguments");
-    long long gx = (max_run + 4 + 1023) / 1024;           // four elements per thread (+ the alignment slack of the first group)
-    if (gx > 2048) gx = 2048;
-    if (gx < 1) gx = 1;
-    sgd_ema_multi_kernel<<<dim3((unsigned)gx, (unsigned)nruns), 256, 0, (hipStream_t)stream>>>(params, grads, momentum, ema,
-                                                                                             (const long long*)runs_dev, hyper_dev, use_ema);
-    YDL_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int ydl_sgd_ema_step_dev(float* params, const float* grads, float* momentum, float* ema,
-                                    int64_t n_decay, int64_t n_params, int64_t n_total, const float* hyper_dev,
-                                    int lr_index, int use_weight_decay, int first_step, int use_ema, void* stream) {
-    YDL_CHECK(params && grads && momentum && hyper_dev, "null pointer");
-    YDL_CHECK(0 <= n_decay && n_decay <= n_params && n_params <= n_total && lr_index >= 0 && lr_index <= 2, "bad arguments");
-    int grid = (int)((n_total + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    sgd_ema_dev_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(params, grads, momentum, ema, n_decay, n_params, n_total,
-                                                               hyper_dev, lr_index, use_weight_decay, first_step, use_ema);
-    YDL_LAUNCH_CHECK();
-    return 0;
-}
-
-
-// ---- Adam / AdamW / RMSProp + EMA over the flat arenas (torch.optim.{Adam,AdamW,RMSprop}, single-tensor path) -------------------
-// One streaming pass, nine words per parameter (p rw, g r, state1 rw, state2 rw, ema rw; SGD has seven).  The three entry forms
-// (host scalars, device hyper vector, run table) share ONE element function and ONE walk, so that they agree bit for bit; the
-// element function keeps torch's operation order and is compiled without FMA contraction (a contraction the compiler picks in one
-// inlining context and not in another would break that agreement, and torch's CPU kernels do not contract either).
+// Adam / AdamW / RMSProp, torch.optim.{Adam,AdamW,RMSprop}, single-tensor path: the element function keeps torch's operation order
+// and is compiled WITHOUT FMA contraction (torch's CPU kernels do not contract either, and the trajectory tests measure against them).
+constexpr int OPT_SGD = 0;     // internal: not a YDL_OPT_* value, ydl_optim_ema_step* refuse it; SGD enters through ydl_sgd_ema_step*
 struct OptHyper {
-    float step;        // Adam/AdamW: lr / (1 - beta1^t);  RMSProp: lr
+    float step;        // Adam/AdamW: lr / (1 - beta1^t);  RMSProp, SGD: lr
     float bc2s;        // Adam/AdamW: sqrt(1 - beta2^t)
     float dmul;        // AdamW: 1 - lr*wd
-    float wd;          // Adam/RMSProp: coupled decay
-    float b1, b2, omb1, omb2, eps, gscale, d;
+    float wd;          // Adam/RMSProp/SGD: coupled decay
+    float b1, b2, omb1, omb2, eps, gscale, d;      // b1: beta1 | momentum
+    float step_nd;     // SGD: lr of the elements past n_decay (the host-scalar form takes two; otherwise == step)
 };
 
 template <int RULE>
@@ -404,14 +269,27 @@ __device__ __forceinline__ void optim_ema_elem(float& p, float g, float& s1, flo
     }
 }
 
+// the element function of a rule (the contract(off) pragma above covers optim_ema_elem's own body only)
+template <int RULE>
+__device__ __forceinline__ void optim_ema_elem_of(float& p, float g, float& s1, float& s2, float& e, bool is_param, bool dec, bool first,
+                                                  bool use_ema, const OptHyper& h) {
+    if (RULE == OPT_SGD) sgd_ema_elem(p, g, s1, e, is_param, dec, first, use_ema, dec ? h.step : h.step_nd, h.b1, h.wd, h.gscale, h.d);
+    else optim_ema_elem<RULE>(p, g, s1, s2, e, is_param, dec, use_ema, h);
+}
+
 // One run [off, off + n_total) of the arenas, walked in float4 groups aligned to the ARENA (16-byte accesses whatever the run's
 // offset); the groups that straddle the run's ends, runs whose decay / parameter boundary is not the whole run, and arenas that are
-// not co-aligned (`vec` false) take the element form.  Same arithmetic per element either way.
+// not co-aligned (`vec` false) take the element form.  Same arithmetic per element either way.  SGD has no second state array
+// (`st2` is never touched) and does not read its momentum on the first step of a run (`first`; false for the other rules).
+// The arrays do not alias; that is declared on the kernels' parameters and not repeated here: with __restrict__ on these
+// parameters too the SLP vectorizer pairs SGD's arithmetic into v_pk_* instructions (34 VGPRs instead of 28, same results).
 template <int RULE>
-__device__ __forceinline__ void optim_ema_walk(float* __restrict__ params, const float* __restrict__ grads, float* __restrict__ st1,
-                                               float* __restrict__ st2, float* __restrict__ ema, long long off, long long n_decay,
-                                               long long n_params, long long n_total, const OptHyper& h, bool ue, bool vec) {
-    const bool us1 = RULE != YDL_OPT_RMSPROP || h.b1 > 0.f;              // RMSProp without momentum keeps no buffer
+__device__ __forceinline__ void optim_ema_walk(float* params, const float* grads, float* st1, float* st2, float* ema, long long off,
+                                               long long n_decay, long long n_params, long long n_total, const OptHyper& h, bool first,
+                                               bool ue, bool vec) {
+    constexpr bool us2 = RULE != OPT_SGD;
+    const bool ws1 = RULE != YDL_OPT_RMSPROP || h.b1 > 0.f;              // RMSProp without momentum keeps no buffer
+    const bool us1 = RULE == OPT_SGD ? !first : ws1;
     const long long a0 = off & ~3ll, end = off + n_total;
     const bool uniform = vec && (n_params == n_total || n_params == 0) && (n_decay == n_params || n_decay == 0);
     for (long long q = a0 + 4 * ((long long)blockIdx.x * blockDim.x + threadIdx.x); q < end; q += 4ll * gridDim.x * blockDim.x) {
@@ -421,17 +299,17 @@ __device__ __forceinline__ void optim_ema_walk(float* __restrict__ params, const
             if (isp) {
                 g4 = *(const float4*)(grads + q);
                 if (us1) a4 = *(const float4*)(st1 + q);
-                b4 = *(const float4*)(st2 + q);
+                if (us2) b4 = *(const float4*)(st2 + q);
             }
             if (ue) e4 = *(const float4*)(ema + q);
-            optim_ema_elem<RULE>(p4.x, g4.x, a4.x, b4.x, e4.x, isp, dec, ue, h);
-            optim_ema_elem<RULE>(p4.y, g4.y, a4.y, b4.y, e4.y, isp, dec, ue, h);
-            optim_ema_elem<RULE>(p4.z, g4.z, a4.z, b4.z, e4.z, isp, dec, ue, h);
-            optim_ema_elem<RULE>(p4.w, g4.w, a4.w, b4.w, e4.w, isp, dec, ue, h);
+            optim_ema_elem_of<RULE>(p4.x, g4.x, a4.x, b4.x, e4.x, isp, dec, first, ue, h);
+            optim_ema_elem_of<RULE>(p4.y, g4.y, a4.y, b4.y, e4.y, isp, dec, first, ue, h);
+            optim_ema_elem_of<RULE>(p4.z, g4.z, a4.z, b4.z, e4.z, isp, dec, first, ue, h);
+            optim_ema_elem_of<RULE>(p4.w, g4.w, a4.w, b4.w, e4.w, isp, dec, first, ue, h);
             if (isp) {
                 *(float4*)(params + q) = p4;
-                if (us1) *(float4*)(st1 + q) = a4;
-                *(float4*)(st2 + q) = b4;
+                if (ws1) *(float4*)(st1 + q) = a4;
+                if (us2) *(float4*)(st2 + q) = b4;
             }
             if (ue) *(float4*)(ema + q) = e4;
         } else {
@@ -443,14 +321,14 @@ __device__ __forceinline__ void optim_ema_walk(float* __restrict__ params, const
                 if (isp) {
                     g = grads[off + i];
                     if (us1) a = st1[off + i];
-                    b = st2[off + i];
+                    if (us2) b = st2[off + i];
                 }
                 if (ue) e = ema[off + i];
-                optim_ema_elem<RULE>(p, g, a, b, e, isp, i < n_decay, ue, h);
+                optim_ema_elem_of<RULE>(p, g, a, b, e, isp, i < n_decay, first, ue, h);
                 if (isp) {
                     params[off + i] = p;
-                    if (us1) st1[off + i] = a;
-                    st2[off + i] = b;
+                    if (ws1) st1[off + i] = a;
+                    if (us2) st2[off + i] = b;
                 }
                 if (ue) ema[off + i] = e;
             }
@@ -459,40 +337,51 @@ __device__ __forceinline__ void optim_ema_walk(float* __restrict__ params, const
 }
 
 __device__ __forceinline__ OptHyper optim_hyper_load(int rule, const float* __restrict__ hyper, int lr_idx, int cls, bool use_wd) {
-    OptHyper h;
+    OptHyper h{};
+    h.wd = use_wd ? hyper[4] : 0.f;
+    h.b1 = hyper[3]; h.gscale = hyper[5]; h.d = hyper[6];
+    if (rule == OPT_SGD) {                                                // its vector ends at [6]
+        h.step = h.step_nd = hyper[lr_idx];
+        return h;
+    }
     const bool rms = rule == YDL_OPT_RMSPROP;
     h.step = rms ? hyper[lr_idx] : hyper[12 + 4 * cls + lr_idx];
     h.bc2s = rms ? 1.f : hyper[12 + 4 * cls + 3];
     h.dmul = hyper[11];
-    h.wd = use_wd ? hyper[4] : 0.f;
-    h.b1 = hyper[3]; h.b2 = hyper[7]; h.eps = hyper[8]; h.omb1 = hyper[9]; h.omb2 = hyper[10];
-    h.gscale = hyper[5]; h.d = hyper[6];
+    h.b2 = hyper[7]; h.eps = hyper[8]; h.omb1 = hyper[9]; h.omb2 = hyper[10];
     return h;
 }
 
 template <int RULE>
-__global__ __launch_bounds__(256) void optim_ema_kernel(float* params, const float* grads, float* st1, float* st2, float* ema, long long off,
-                                                        long long n_decay, long long n_params, long long n_total, OptHyper h, int vec) {
-    optim_ema_walk<RULE>(params, grads, st1, st2, ema, off, n_decay, n_params, n_total, h, h.d >= 0.f && ema != nullptr, vec != 0);
+__global__ __launch_bounds__(256) void optim_ema_kernel(float* __restrict__ params, const float* __restrict__ grads,
+                                                        float* __restrict__ st1, float* __restrict__ st2, float* __restrict__ ema,
+                                                        long long off, long long n_decay, long long n_params, long long n_total,
+                                                        OptHyper h, int first, int vec) {
+    optim_ema_walk<RULE>(params, grads, st1, st2, ema, off, n_decay, n_params, n_total, h, first != 0, h.d >= 0.f && ema != nullptr, vec != 0);
 }
 
 template <int RULE>
-__global__ __launch_bounds__(256) void optim_ema_dev_kernel(float* params, const float* grads, float* st1, float* st2, float* ema, long long off,
-                                                            long long n_decay, long long n_params, long long n_total,
-                                                            const float* __restrict__ hyper, int lr_idx, int cls, int use_wd, int use_ema,
-                                                            int vec) {
+__global__ __launch_bounds__(256) void optim_ema_dev_kernel(float* __restrict__ params, const float* __restrict__ grads,
+                                                            float* __restrict__ st1, float* __restrict__ st2, float* __restrict__ ema,
+                                                            long long off, long long n_decay, long long n_params, long long n_total,
+                                                            const float* __restrict__ hyper, int lr_idx, int cls, int use_wd, int first,
+                                                            int use_ema, int vec) {
     const OptHyper h = optim_hyper_load(RULE, hyper, lr_idx, cls, use_wd != 0);
-    optim_ema_walk<RULE>(params, grads, st1, st2, ema, off, n_decay, n_params, n_total, h, use_ema && ema != nullptr, vec != 0);
+    optim_ema_walk<RULE>(params, grads, st1, st2, ema, off, n_decay, n_params, n_total, h, first != 0, use_ema && ema != nullptr, vec != 0);
 }
 
-// grid row y handles run y = {offset, n_decay, n_params, n_total, lr_index, flags (bit 0 weight decay), bc_class, 0} of the device table
+// grid row y handles run y of the device table: {offset, n_decay, n_params, n_total, lr_index, flags (bit 0 weight decay, SGD: bit 1
+// first step)} and, but for SGD whose rows end there, {bc_class, 0}
 template <int RULE>
-__global__ __launch_bounds__(256) void optim_ema_multi_kernel(float* params, const float* grads, float* st1, float* st2, float* ema,
+__global__ __launch_bounds__(256) void optim_ema_multi_kernel(float* __restrict__ params, const float* __restrict__ grads,
+                                                              float* __restrict__ st1, float* __restrict__ st2, float* __restrict__ ema,
                                                               const long long* __restrict__ runs, const float* __restrict__ hyper,
                                                               int use_ema) {
-    const long long* r = runs + (size_t)blockIdx.y * 8;
-    const OptHyper h = optim_hyper_load(RULE, hyper, (int)r[4], (int)r[6], ((int)r[5] & 1) != 0);
-    optim_ema_walk<RULE>(params, grads, st1, st2, ema, r[0], r[1], r[2], r[3], h, use_ema && ema != nullptr, true);
+    const long long* r = runs + (size_t)blockIdx.y * (RULE == OPT_SGD ? 6 : 8);
+    const int flags = (int)r[5];
+    const OptHyper h = optim_hyper_load(RULE, hyper, (int)r[4], RULE == OPT_SGD ? 0 : (int)r[6], (flags & 1) != 0);
+    optim_ema_walk<RULE>(params, grads, st1, st2, ema, r[0], r[1], r[2], r[3], h, RULE == OPT_SGD && (flags & 2) != 0,
+                         use_ema && ema != nullptr, true);
 }
 
 static inline unsigned optim_grid_x(long long n) {
@@ -504,17 +393,17 @@ static inline unsigned optim_grid_x(long long n) {
 
 // per-run forms: the pointers are arena + offset and need not be 16-byte aligned.  When every array the run touches sits at the
 // same distance `lead` (0..3 elements) behind a 16-byte boundary, all are rebased onto that boundary and the run starts at `lead`
-// (the vector walk); otherwise the element walk.
+// (the vector walk); otherwise the element walk.  SGD has no `s2`.
 static inline int optim_lead(const void* p) { return (int)((((uintptr_t)p) >> 2) & 3u); }
 struct OptRebase { float *p, *s1, *s2, *e; const float* g; long long off; int vec; };
 static OptRebase optim_rebase(float* params, const float* grads, float* s1, float* s2, float* ema, bool has_params, bool has_ema) {
     const int lead = optim_lead(params);
     bool co = (((uintptr_t)params) & 3u) == 0;
-    if (has_params) co = co && optim_lead(grads) == lead && optim_lead(s1) == lead && optim_lead(s2) == lead;
+    if (has_params) co = co && optim_lead(grads) == lead && optim_lead(s1) == lead && (s2 == nullptr || optim_lead(s2) == lead);
     if (has_ema) co = co && optim_lead(ema) == lead;
     OptRebase r{params, s1, s2, ema, grads, 0, 0};
     if (co) {
-        r.p = params - lead; r.g = grads - lead; r.s1 = s1 - lead; r.s2 = s2 - lead; r.e = ema ? ema - lead : nullptr;
+        r.p = params - lead; r.g = grads - lead; r.s1 = s1 - lead; r.s2 = s2 ? s2 - lead : nullptr; r.e = ema ? ema - lead : nullptr;
         r.off = lead; r.vec = 1;
     }
     return r;
@@ -523,50 +412,45 @@ static OptRebase optim_rebase(float* params, const float* grads, float* s1, floa
 #define YDL_OPT_RULE_OK(rule) ((rule) == YDL_OPT_ADAM || (rule) == YDL_OPT_ADAMW || (rule) == YDL_OPT_RMSPROP)
 #define YDL_OPT_DISPATCH(rule, KERNEL, grid, st, ...)                                              \
     do {                                                                                           \
-        if ((rule) == YDL_OPT_ADAM) KERNEL<YDL_OPT_ADAM><<<grid, 256, 0, st>>>(__VA_ARGS__);       \
+        if ((rule) == OPT_SGD) KERNEL<OPT_SGD><<<grid, 256, 0, st>>>(__VA_ARGS__);                 \
+        else if ((rule) == YDL_OPT_ADAM) KERNEL<YDL_OPT_ADAM><<<grid, 256, 0, st>>>(__VA_ARGS__);  \
         else if ((rule) == YDL_OPT_ADAMW) KERNEL<YDL_OPT_ADAMW><<<grid, 256, 0, st>>>(__VA_ARGS__); \
         else KERNEL<YDL_OPT_RMSPROP><<<grid, 256, 0, st>>>(__VA_ARGS__);                           \
     } while (0)
 
-extern "C" int ydl_optim_ema_step(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
-                                  int64_t n_decay, int64_t n_params, int64_t n_total,
-                                  float step_size, float bc2_sqrt, float decay_mul, float weight_decay,
-                                  float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
-                                  float grad_scale, float ema_decay, void* stream) {
-    YDL_CHECK(YDL_OPT_RULE_OK(rule), "unknown optimizer rule");
-    YDL_CHECK(params && grads && state1 && state2, "null pointer");
+// The three entry forms of every rule: validation and launch.  The public entry points below add only what is theirs: the
+// family's refuse a rule that is not a YDL_OPT_* value, SGD's pass OPT_SGD and no second state array.
+static int optim_step(int rule, float* params, const float* grads, float* state1, float* state2, float* ema, int64_t n_decay,
+                      int64_t n_params, int64_t n_total, const OptHyper& h, int first_step, void* stream) {
+    YDL_CHECK(params && grads && state1 && (state2 || rule == OPT_SGD), "null pointer");
     YDL_CHECK(0 <= n_decay && n_decay <= n_params && n_params <= n_total, "bad arena partition");
-    const OptHyper h{step_size, bc2_sqrt, decay_mul, weight_decay, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, grad_scale, ema_decay};
-    const OptRebase r = optim_rebase(params, grads, state1, state2, ema, n_params > 0, ema != nullptr && ema_decay >= 0.f);
+    const OptRebase r = optim_rebase(params, grads, state1, state2, ema, n_params > 0, ema != nullptr && h.d >= 0.f);
     const dim3 grid(optim_grid_x(n_total));
     hipStream_t st = (hipStream_t)stream;
     YDL_OPT_DISPATCH(rule, optim_ema_kernel, grid, st, r.p, r.g, r.s1, r.s2, r.e, r.off, (long long)n_decay, (long long)n_params,
-                     (long long)n_total, h, r.vec);
+                     (long long)n_total, h, first_step, r.vec);
     YDL_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int ydl_optim_ema_step_dev(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
-                                      int64_t n_decay, int64_t n_params, int64_t n_total, const float* hyper_dev,
-                                      int lr_index, int bc_class, int use_weight_decay, int use_ema, void* stream) {
-    YDL_CHECK(YDL_OPT_RULE_OK(rule), "unknown optimizer rule");
-    YDL_CHECK(params && grads && state1 && state2 && hyper_dev, "null pointer");
+static int optim_step_dev(int rule, float* params, const float* grads, float* state1, float* state2, float* ema, int64_t n_decay,
+                          int64_t n_params, int64_t n_total, const float* hyper_dev, int lr_index, int bc_class, int use_weight_decay,
+                          int first_step, int use_ema, void* stream) {
+    YDL_CHECK(params && grads && state1 && (state2 || rule == OPT_SGD) && hyper_dev, "null pointer");
     YDL_CHECK(0 <= n_decay && n_decay <= n_params && n_params <= n_total, "bad arena partition");
     YDL_CHECK(lr_index >= 0 && lr_index <= 2 && bc_class >= 0 && bc_class < YDL_OPT_MAX_CLASSES, "bad lr index or bias-correction class");
     const OptRebase r = optim_rebase(params, grads, state1, state2, ema, n_params > 0, ema != nullptr && use_ema);
     const dim3 grid(optim_grid_x(n_total));
     hipStream_t st = (hipStream_t)stream;
     YDL_OPT_DISPATCH(rule, optim_ema_dev_kernel, grid, st, r.p, r.g, r.s1, r.s2, r.e, r.off, (long long)n_decay, (long long)n_params,
-                     (long long)n_total, hyper_dev, lr_index, bc_class, use_weight_decay, use_ema, r.vec);
+                     (long long)n_total, hyper_dev, lr_index, bc_class, use_weight_decay, first_step, use_ema, r.vec);
     YDL_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int ydl_optim_ema_step_multi(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
-                                        const int64_t* runs_dev, int nruns, int64_t max_run, const float* hyper_dev, int use_ema,
-                                        void* stream) {
-    YDL_CHECK(YDL_OPT_RULE_OK(rule), "unknown optimizer rule");
-    YDL_CHECK(params && grads && state1 && state2 && runs_dev && hyper_dev, "null pointer");
+static int optim_step_multi(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
+                            const int64_t* runs_dev, int nruns, int64_t max_run, const float* hyper_dev, int use_ema, void* stream) {
+    YDL_CHECK(params && grads && state1 && (state2 || rule == OPT_SGD) && runs_dev && hyper_dev, "null pointer");
     YDL_CHECK(nruns > 0 && nruns <= 65535 && max_run >= 0, "bad run count");
     YDL_CHECK(aligned16(params) && aligned16(grads) && aligned16(state1) && aligned16(state2) && (ema == nullptr || aligned16(ema)),
               "arenas must be 16-byte aligned");
@@ -576,4 +460,50 @@ extern "C" int ydl_optim_ema_step_multi(int rule, float* params, const float* gr
                      use_ema);
     YDL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int ydl_sgd_ema_step(float* params, const float* grads, float* momentum, float* ema,
+                                int64_t n_decay, int64_t n_params, int64_t n_total,
+                                float lr_decay_group, float lr_nodecay_group, float mom, float weight_decay, float grad_scale,
+                                int first_step, float ema_decay, void* stream) {
+    OptHyper h{};
+    h.step = lr_decay_group; h.step_nd = lr_nodecay_group; h.b1 = mom; h.wd = weight_decay; h.gscale = grad_scale; h.d = ema_decay;
+    return optim_step(OPT_SGD, params, grads, momentum, nullptr, ema, n_decay, n_params, n_total, h, first_step, stream);
+}
+
+extern "C" int ydl_sgd_ema_step_dev(float* params, const float* grads, float* momentum, float* ema,
+                                    int64_t n_decay, int64_t n_params, int64_t n_total, const float* hyper_dev,
+                                    int lr_index, int use_weight_decay, int first_step, int use_ema, void* stream) {
+    return optim_step_dev(OPT_SGD, params, grads, momentum, nullptr, ema, n_decay, n_params, n_total, hyper_dev, lr_index, 0,
+                          use_weight_decay, first_step, use_ema, stream);
+}
+
+extern "C" int ydl_sgd_ema_step_multi(float* params, const float* grads, float* momentum, float* ema, const int64_t* runs_dev,
+                                      int nruns, int64_t max_run, const float* hyper_dev, int use_ema, void* stream) {
+    return optim_step_multi(OPT_SGD, params, grads, momentum, nullptr, ema, runs_dev, nruns, max_run, hyper_dev, use_ema, stream);
+}
+
+extern "C" int ydl_optim_ema_step(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
+                                  int64_t n_decay, int64_t n_params, int64_t n_total,
+                                  float step_size, float bc2_sqrt, float decay_mul, float weight_decay,
+                                  float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                                  float grad_scale, float ema_decay, void* stream) {
+    YDL_CHECK(YDL_OPT_RULE_OK(rule), "unknown optimizer rule");
+    const OptHyper h{step_size, bc2_sqrt, decay_mul, weight_decay, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, grad_scale, ema_decay};
+    return optim_step(rule, params, grads, state1, state2, ema, n_decay, n_params, n_total, h, 0, stream);
+}
+
+extern "C" int ydl_optim_ema_step_dev(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
+                                      int64_t n_decay, int64_t n_params, int64_t n_total, const float* hyper_dev,
+                                      int lr_index, int bc_class, int use_weight_decay, int use_ema, void* stream) {
+    YDL_CHECK(YDL_OPT_RULE_OK(rule), "unknown optimizer rule");
+    return optim_step_dev(rule, params, grads, state1, state2, ema, n_decay, n_params, n_total, hyper_dev, lr_index, bc_class,
+                          use_weight_decay, 0, use_ema, stream);
+}
+
+extern "C" int ydl_optim_ema_step_multi(int rule, float* params, const float* grads, float* state1, float* state2, float* ema,
+                                        const int64_t* runs_dev, int nruns, int64_t max_run, const float* hyper_dev, int use_ema,
+                                        void* stream) {
+    YDL_CHECK(YDL_OPT_RULE_OK(rule), "unknown optimizer rule");
+    return optim_step_multi(rule, params, grads, state1, state2, ema, runs_dev, nruns, max_run, hyper_dev, use_ema, stream);
 }

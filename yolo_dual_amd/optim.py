@@ -34,8 +34,8 @@ def _is_bn(m: nn.Module) -> bool:
 class FlatArenaOptimizer(torch.optim.Optimizer):
     """what every flat-arena optimizer shares: the arenas ``[weights with decay | BN weights | biases | float buffers]``, the slots,
     the EMA shadow, the device hyper-parameter vector with its pinned ring, and the cache of device run tables.  A rule adds its
-    state arenas (``n_state`` of them, allocated once between the gradient arena and the EMA shadow), its param_groups and its step"""
-    _HYPER_FLOATS = 7
+    state arenas (``n_state`` of them, allocated once between the gradient arena and the EMA shadow), its param_groups, its
+    checkpoint format and the hooks of the step driver"""
 
     def _init_arenas(self, model: nn.Module, n_state: int, ema: bool, ema_decay: float, ema_tau: float, ema_updates: int):
         """lay the model out in the arenas; returns (decay weights, BN weights, biases, device)"""
@@ -98,27 +98,31 @@ class FlatArenaOptimizer(torch.optim.Optimizer):
         config.bump_weight_epoch()
 
     # ------------------------------------------------------------------
+    @staticmethod
+    def _view(arena: torch.Tensor, off: int, n: int, shape) -> torch.Tensor:
+        """``arena[off:off + n]`` in the logical ``shape``; conv weights are KRSC physical, OIHW logical"""
+        flat = arena[off:off + n]
+        if len(shape) == 4:
+            O, I, kh, kw = shape
+            return flat.view(O, kh, kw, I).permute(0, 3, 1, 2)
+        return flat.view(shape)
+
+    def _slot_of_ptr(self) -> Dict[int, Tuple[int, int]]:
+        """data pointer of every parameter and float buffer -> (offset, numel) in the arenas"""
+        return {t.data_ptr(): (off, n) for t, off, n, *_g in self._slots + self._buf_slots}
+
     def _rehome(self, p: nn.Parameter, off: int, n: int) -> None:
-        flat = self.params_arena[off:off + n]
-        gflat = self.grads_arena[off:off + n]
-        if p.dim() == 4:
-            O, I, kh, kw = p.shape
-            view = flat.view(O, kh, kw, I).permute(0, 3, 1, 2)          # KRSC physical, OIHW logical
-            gview = gflat.view(O, kh, kw, I).permute(0, 3, 1, 2)
-        else:
-            view, gview = flat.view(p.shape), gflat.view(p.shape)
+        view = self._view(self.params_arena, off, n, p.shape)
         view.copy_(p.data)
         p.data = view
-        p.grad = gview
+        p.grad = self._view(self.grads_arena, off, n, p.shape)
         p._ydl_touched = False
 
     def reattach(self) -> None:
         """(re)bind ``p.grad`` to the arena (needed if foreign code set grads to None)"""
         for p, off, n, _g in self._slots:
             if p.grad is None or p.grad.data_ptr() != self.grads_arena.data_ptr() + 4 * off:
-                gflat = self.grads_arena[off:off + n]
-                p.grad = gflat.view(p.shape[0], p.shape[2], p.shape[3], p.shape[1]).permute(0, 3, 1, 2) if p.dim() == 4 \
-                    else gflat.view(p.shape)
+                p.grad = self._view(self.grads_arena, off, n, p.shape)
 
     def zero_grad(self, set_to_none: bool = False) -> None:   # grads stay attached to the arena
         zero_(self.grads_arena)
@@ -173,16 +177,142 @@ class FlatArenaOptimizer(torch.optim.Optimizer):
             cache[sig] = tab
         return tab
 
+    # ------------------------------------------------------------------ the step driver; a rule supplies the hooks below it
+    def _ema_d(self, off: float) -> float:
+        """advance the EMA counter; the decay of this step, or ``off`` without an EMA"""
+        if self.ema_arena is None:
+            return off
+        self.updates += 1
+        return self.ema_decay * (1.0 - math.exp(-self.updates / self.ema_tau))
+
+    def _runs(self, commit: bool = False) -> List[List]:
+        """maximal runs of consecutive slots with identical (touched, group, rule state) key; ``commit`` tells the rule that the
+        touched parameters are being stepped with that state"""
+        runs: List[List] = []
+        for i, (p, off, n, gi) in enumerate(self._slots):
+            touched = bool(getattr(p, "_ydl_touched", False))
+            key = (touched, gi, self._run_state(i, p, touched))
+            if runs and runs[-1][0] == key and runs[-1][2] == off:
+                runs[-1][2] = off + n
+            else:
+                runs.append([key, off, off + n])
+            if touched and commit:
+                self._commit(p)
+        return runs
+
+    def _spans(self, runs):
+        """(offset, length, group, rule state) of every launch of a step: the touched runs and, with an EMA, the untouched runs and
+        the float buffers behind the parameters (group None: EMA only, gradients and state are not read)"""
+        for (touched, gi, state), a, b in runs:
+            if touched:
+                yield a, b - a, gi, state
+            elif self.ema_arena is not None:
+                yield a, b - a, None, 0
+        if self.ema_arena is not None and self.n_total > self.n_params:
+            yield self.n_params, self.n_total - self.n_params, None, 0
+
+    def _run_rows(self, runs) -> tuple:
+        """rows {offset, n_decay, n_params, n_total, lr index, flags (bit 0 weight decay), rule columns} of the ``_multi`` entry"""
+        cls = self._classes()
+        return tuple((a, 0, 0, n) + (0,) * (self._ROW_COLS - 4) if gi is None else
+                     (a, n if gi == 0 else 0, n, n, gi) + self._row_tail(gi, state, cls) for a, n, gi, state in self._spans(runs))
+
+    def _ptrs(self, a: int = 0, live: bool = True) -> list:
+        """the array arguments of a launch that starts at element ``a``; an EMA-only launch (``live`` false) gets the gradient and
+        state arenas as they are: they end at ``n_params`` and are not read"""
+        ea = self.ema_arena
+        return [_p(self.params_arena[a:])] + [_p(t[a:] if live else t) for t in [self.grads_arena] + self._state_arenas] + \
+            [_p(ea[a:]) if ea is not None else None]
+
+    def _hyper(self, grad_scale: float, d: float) -> List[float]:
+        """the head of the hyper vector (ydl.h): lr of {weights, BN weights, biases}, the rule's values, grad_scale and EMA decay in
+        their places, in double precision"""
+        lr_bias, lr_w, lr_bn = (float(g["lr"]) for g in self.param_groups)
+        return self._hyper_vals([lr_w, lr_bn, lr_bias], float(self.param_groups[1]["weight_decay"]), grad_scale, d)
+
+    def prepare_step(self, grad_scale: float = 1.0) -> None:
+        """host half of a step: advance the EMA counter and the rule's counters, and push the hyper-parameters and the EMA decay to
+        the device vector the captured kernels read (call OUTSIDE the graph, before replaying it; layout: ydl.h)"""
+        d = self._ema_d(0.0)
+        self._advance()
+        vals = self._hyper(grad_scale, d)
+        vals += self._class_vals(vals)
+        self.ensure_hyper()
+        i = self._hyper_slot
+        self._hyper_slot = (i + 1) % len(self._hyper_ring)
+        h, ev = self._hyper_ring[i]
+        if self._hyper_used[i]:
+            ev.synchronize()              # normally long complete (8 steps ago)
+        h.copy_(torch.tensor(vals, dtype=torch.float64))         # one rounding, double -> f32
+        self._hyper_dev.copy_(h, non_blocking=True)
+        ev.record()
+        self._hyper_used[i] = True
+
+    @torch.no_grad()
+    def step_device_hyper(self) -> None:
+        """device half: the same kernels as ``step`` but reading hyper-parameters from ``_hyper_dev`` (capturable)"""
+        st = _stream()
+        use_ema = 1 if self.ema_arena is not None else 0
+        hp = _p(self._hyper_dev)
+        rows = self._run_rows(self._runs(commit=True))
+        # one launch for all runs.  The table is a persistent device tensor keyed by the run structure (constant while the same
+        # parameters stay live); inside a recording / capture pass a NEW table must not be allocated (private pool), so a miss
+        # there takes the per-run launches below
+        tab = getattr(self, "_runs_dev", None)
+        if (tab is None or tab[0] != rows) and rows and L.recorder() is None and not torch.cuda.is_current_stream_capturing():
+            tab = self._runs_table(rows)
+            self._runs_dev = tab
+        if tab is not None and tab[0] == rows:
+            if rows:
+                L.call(self._ENTRY + "_multi", *self._rule_args(), *self._ptrs(), _p(tab[1]), len(rows), max(r[3] for r in rows),
+                       hp, use_ema, st)
+        else:
+            for row in rows:
+                L.call(self._ENTRY + "_dev", *self._rule_args(), *self._ptrs(row[0], row[2] > 0), *row[1:4], hp,
+                       *self._dev_args(row), use_ema, st)
+        config.bump_weight_epoch()
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale: float = 1.0):
+        d = self._ema_d(-1.0)
+        self._advance()
+        hv = self._hyper(grad_scale, d)
+        st = _stream()
+        for a, n, gi, state in self._spans(self._runs(commit=True)):
+            L.call(self._ENTRY, *self._rule_args(), *self._ptrs(a, gi is not None), n if gi == 0 else 0, 0 if gi is None else n, n,
+                   *self._host_args(gi, state, hv), st)
+        config.bump_weight_epoch()
+        return None
+
+    # ------------------------------------------------------------------ what a rule supplies
+    # _ENTRY (name of its host-scalar entry point; "_dev" / "_multi" are the other two), _ROW_COLS and _HYPER_FLOATS (widths of
+    # its run-table row and hyper vector), the number of state arenas (``_init_arenas``), _run_state (third component of a run
+    # key), _row_tail (columns of a row after the lr index), _hyper_vals (head of the hyper vector), _dev_args / _host_args (the
+    # scalars of the per-run entry points between n_total | hyper_dev and use_ema | stream), and where it needs them:
+    RULE = 0                 # the ``rule`` argument of the family's entry points; SGD has entry points of its own and none
+
+    def _rule_args(self) -> tuple:
+        return (self.RULE,) if self.RULE else ()
+
+    def _advance(self) -> None:
+        """counters that move once per step, before the runs are formed (``step`` and ``prepare_step``)"""
+
+    def _commit(self, p: nn.Parameter) -> None:
+        """``p`` is being stepped (``step`` and ``step_device_hyper``)"""
+
+    def _classes(self) -> Dict[int, int]:
+        return {}
+
+    def _class_vals(self, vals: List[float]) -> List[float]:
+        """what follows the head of the hyper vector"""
+        return []
+
     def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         """restore the EMA shadow from a ``state_dict`` (smart_resume: ``ema.ema.load_state_dict(ckpt['ema']...)``)"""
         if self.ema_arena is None:
             raise RuntimeError("EMA disabled")
         cur = self.ema_state_dict()
-        by_ptr = {}
-        for p, off, n, _g in self._slots:
-            by_ptr[p.data_ptr()] = (off, n)
-        for b, off, n in self._buf_slots:
-            by_ptr[b.data_ptr()] = (off, n)
+        by_ptr = self._slot_of_ptr()
         for k, v in self.model.state_dict().items():
             slot = by_ptr.get(v.data_ptr())
             if slot is None or not v.dtype.is_floating_point or k not in sd or tuple(sd[k].shape) != tuple(cur[k].shape):
@@ -198,28 +328,20 @@ class FlatArenaOptimizer(torch.optim.Optimizer):
         """state_dict of the EMA shadow (same keys as model.state_dict(); integer buffers are copied as is)."""
         if self.ema_arena is None:
             raise RuntimeError("EMA disabled")
-        by_ptr = {}
-        for p, off, n, _g in self._slots:
-            by_ptr[p.data_ptr()] = (off, n)
-        for b, off, n in self._buf_slots:
-            by_ptr[b.data_ptr()] = (off, n)
+        by_ptr = self._slot_of_ptr()
         out = {}
         for k, v in self.model.state_dict().items():
             slot = by_ptr.get(v.data_ptr())
             if slot is None or not v.dtype.is_floating_point:
                 out[k] = v.clone()
-                continue
-            off, n = slot
-            flat = self.ema_arena[off:off + n]
-            if v.dim() == 4:
-                O, I, kh, kw = v.shape
-                out[k] = flat.view(O, kh, kw, I).permute(0, 3, 1, 2).clone()
             else:
-                out[k] = flat.view(v.shape).clone()
+                out[k] = self._view(self.ema_arena, *slot, v.shape).clone()
         return out
 
 
 class FlatSGDEMA(FlatArenaOptimizer):
+    _ENTRY, _ROW_COLS, _HYPER_FLOATS = "ydl_sgd_ema_step", 6, 7
+
     def __init__(self, model: nn.Module, lr: float = 0.01, momentum: float = 0.937, weight_decay: float = 5e-4,
                  ema: bool = True, ema_decay: float = 0.9999, ema_tau: float = 2000.0, ema_updates: int = 0):
         g0, g1, g2, dev = self._init_arenas(model, 1, ema, ema_decay, ema_tau, ema_updates)
@@ -227,133 +349,28 @@ class FlatSGDEMA(FlatArenaOptimizer):
         self._has_buf: Dict[int, bool] = {}
         self._init_groups(g0, g1, g2, dev, dict(lr=lr, momentum=momentum, nesterov=True, weight_decay=0.0), weight_decay)
 
-    def prepare_step(self, grad_scale: float = 1.0) -> None:
-        """host half of a step: advance the EMA counter and push {lr, momentum, wd, grad_scale, ema decay} to the device
-        vector the captured kernels read (call OUTSIDE the graph, before replaying it)"""
-        lr_bias, lr_w, lr_bn = (g["lr"] for g in self.param_groups)
-        d = 0.0
-        if self.ema_arena is not None:
-            self.updates += 1
-            d = self.ema_decay * (1.0 - math.exp(-self.updates / self.ema_tau))
-        self.ensure_hyper()
-        i = self._hyper_slot
-        self._hyper_slot = (i + 1) % len(self._hyper_ring)
-        h, ev = self._hyper_ring[i]
-        if self._hyper_used[i]:
-            ev.synchronize()              # normally long complete (8 steps ago)
-        h[0], h[1], h[2] = lr_w, lr_bn, lr_bias
-        h[3], h[4] = self.param_groups[1]["momentum"], self.param_groups[1]["weight_decay"]
-        h[5], h[6] = grad_scale, d
-        self._hyper_dev.copy_(h, non_blocking=True)
-        ev.record()
-        self._hyper_used[i] = True
+    def _run_state(self, i: int, p: nn.Parameter, touched: bool) -> bool:
+        """first step of this parameter: its momentum buffer is initialised with the gradient"""
+        return touched and not self._has_buf.get(id(p), False)
 
-    def _runs(self, commit: bool) -> List[List]:
-        """maximal runs of consecutive slots with identical (touched, group, first-step) state; ``commit`` marks the touched
-        parameters as having a momentum buffer from now on"""
-        runs: List[List] = []
-        for p, off, n, gi in self._slots:
-            touched = bool(getattr(p, "_ydl_touched", False))
-            first = touched and not self._has_buf.get(id(p), False)
-            key = (touched, gi, first)
-            if runs and runs[-1][0] == key and runs[-1][2] == off:
-                runs[-1][2] = off + n
-            else:
-                runs.append([key, off, off + n])
-            if touched and commit:
-                self._has_buf[id(p)] = True
-        return runs
+    def _commit(self, p: nn.Parameter) -> None:
+        self._has_buf[id(p)] = True
 
-    def _run_rows(self, runs) -> tuple:
-        """rows {offset, n_decay, n_params, n_total, lr index, flags} of ydl_sgd_ema_step_multi"""
-        rows = []
-        for (touched, gi, first), a, b in runs:
-            n = b - a
-            if touched:
-                rows.append((a, n if gi == 0 else 0, n, n, gi, (1 if gi == 0 else 0) | (2 if first else 0)))
-            elif self.ema_arena is not None:
-                rows.append((a, 0, 0, n, 0, 0))
-        if self.ema_arena is not None and self.n_total > self.n_params:
-            rows.append((self.n_params, 0, 0, self.n_total - self.n_params, 0, 0))
-        return tuple(rows)
+    def _row_tail(self, gi: int, first: bool, cls) -> tuple:
+        return ((1 if gi == 0 else 0) | (2 if first else 0),)
 
-    @torch.no_grad()
-    def step_device_hyper(self) -> None:
-        """device half: the same kernels as ``step`` but reading hyper-parameters from ``_hyper_dev`` (capturable)"""
-        st = _stream()
-        pa, ga, ma, ea = self.params_arena, self.grads_arena, self.mom_arena, self.ema_arena
-        use_ema = 1 if ea is not None else 0
-        runs = self._runs(commit=True)
-        hp = _p(self._hyper_dev)
-        # one launch for all runs.  The table is a persistent device tensor keyed by the run structure (constant once every live
-        # parameter has its momentum buffer); inside a recording / capture pass a NEW table must not be allocated (private pool),
-        # so a miss there takes the per-run launches below
-        rows = self._run_rows(runs)
-        sig = rows
-        tab = getattr(self, "_runs_dev", None)
-        if (tab is None or tab[0] != sig) and rows and L.recorder() is None and not torch.cuda.is_current_stream_capturing():
-            tab = self._runs_table(sig)
-            self._runs_dev = tab
-        if tab is not None and tab[0] == sig:
-            if rows:
-                L.call("ydl_sgd_ema_step_multi", _p(pa), _p(ga), _p(ma), _p(ea) if ea is not None else None, _p(tab[1]), len(rows),
-                       max(r[3] for r in rows), hp, use_ema, st)
-            config.bump_weight_epoch()
-            return
-        for (touched, gi, first), a, b in runs:
-            n = b - a
-            eptr = _p(ea[a:b]) if ea is not None else None
-            if touched:
-                L.call("ydl_sgd_ema_step_dev", _p(pa[a:b]), _p(ga[a:b]), _p(ma[a:b]), eptr, n if gi == 0 else 0, n, n,
-                       hp, gi, 1 if gi == 0 else 0, 1 if first else 0, use_ema, st)
-            elif ea is not None:
-                L.call("ydl_sgd_ema_step_dev", _p(pa[a:b]), _p(ga[a:b]), _p(ma[a:b]), eptr, 0, 0, n, hp, 0, 0, 0, 1, st)
-        if ea is not None and self.n_total > self.n_params:
-            a, b = self.n_params, self.n_total
-            L.call("ydl_sgd_ema_step_dev", _p(pa[a:b]), _p(ga), _p(ma), _p(ea[a:b]), 0, 0, b - a, hp, 0, 0, 0, 1, st)
-        config.bump_weight_epoch()
+    def _hyper_vals(self, lrs, wd, grad_scale, d) -> List[float]:
+        return lrs + [float(self.param_groups[1]["momentum"]), wd, grad_scale, d]
 
-    @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0):
-        lr_bias, lr_w, lr_bn = (g["lr"] for g in self.param_groups)
-        mom = self.param_groups[1]["momentum"]
-        wd = self.param_groups[1]["weight_decay"]
-        lrs = (lr_w, lr_bn, lr_bias)
-        d = -1.0
-        if self.ema_arena is not None:
-            self.updates += 1
-            d = self.ema_decay * (1.0 - math.exp(-self.updates / self.ema_tau))
-        st = _stream()
-        # maximal runs of consecutive slots with identical (touched, group, first-step) state
-        runs: List[List] = []
-        for p, off, n, gi in self._slots:
-            touched = bool(getattr(p, "_ydl_touched", False))
-            first = touched and not self._has_buf.get(id(p), False)
-            key = (touched, gi, first)
-            if runs and runs[-1][0] == key and runs[-1][2] == off:
-                runs[-1][2] = off + n
-            else:
-                runs.append([key, off, off + n])
-            if touched:
-                self._has_buf[id(p)] = True
-        pa, ga, ma = self.params_arena, self.grads_arena, self.mom_arena
-        ea = self.ema_arena
-        for (touched, gi, first), a, b in runs:
-            n = b - a
-            eptr = _p(ea[a:b]) if ea is not None else None
-            if touched:
-                nd = n if gi == 0 else 0
-                L.call("ydl_sgd_ema_step", _p(pa[a:b]), _p(ga[a:b]), _p(ma[a:b]), eptr, nd, n, n,
-                       lrs[gi], lrs[gi], mom, wd if gi == 0 else 0.0, grad_scale, 1 if first else 0, d, st)
-            elif ea is not None:
-                L.call("ydl_sgd_ema_step", _p(pa[a:b]), _p(ga[a:b]), _p(ma[a:b]), eptr, 0, 0, n,
-                       0.0, 0.0, mom, 0.0, 1.0, 0, d, st)
-        if ea is not None and self.n_total > self.n_params:
-            a, b = self.n_params, self.n_total
-            L.call("ydl_sgd_ema_step", _p(pa[a:b]), _p(ga), _p(ma), _p(ea[a:b]), 0, 0, b - a,
-                   0.0, 0.0, mom, 0.0, 1.0, 0, d, st)
-        config.bump_weight_epoch()
-        return None
+    def _dev_args(self, row) -> tuple:
+        """lr index, weight decay, first step"""
+        return row[4], row[5] & 1, row[5] >> 1
+
+    def _host_args(self, gi, first, hv) -> tuple:
+        """lr of the decay and of the no-decay part, momentum, weight decay, grad_scale, first step, EMA decay"""
+        if gi is None:
+            return 0.0, 0.0, hv[3], 0.0, 1.0, 0, hv[6]
+        return hv[gi], hv[gi], hv[3], hv[4] if gi == 0 else 0.0, hv[5], 1 if first else 0, hv[6]
 
     # ------------------------------------------------------------------ checkpoint state (seg_diceloss_yolov5.py:1204-1212)
     def state_dict(self):
@@ -387,9 +404,8 @@ class _FlatAdaptiveEMA(FlatArenaOptimizer):
     advance), so parameters can sit at different ``t``.  Everything torch derives from ``t`` in Python double precision — the bias
     corrections, ``lr / (1 - beta1^t)``, ``1 - lr*wd`` — is computed here in double and reaches the kernels rounded once to f32.
     Parameters with the same ``t`` form a bias-correction class; runs never span two classes."""
-    RULE = 0
     FORMAT = ""
-    _HYPER_FLOATS = L.OPT_HYPER_FLOATS
+    _ENTRY, _ROW_COLS, _HYPER_FLOATS = "ydl_optim_ema_step", 8, L.OPT_HYPER_FLOATS
 
     def _init_adaptive(self, model, defaults: dict, weight_decay: float, ema, ema_decay, ema_tau, ema_updates) -> None:
         g0, g1, g2, dev = self._init_arenas(model, 2, ema, ema_decay, ema_tau, ema_updates)
@@ -412,12 +428,6 @@ class _FlatAdaptiveEMA(FlatArenaOptimizer):
         b1, b2, _eps = self._betas()
         return lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5
 
-    def _ema_d(self, off: float) -> float:
-        if self.ema_arena is None:
-            return off
-        self.updates += 1
-        return self.ema_decay * (1.0 - math.exp(-self.updates / self.ema_tau))
-
     def _advance(self) -> None:
         """step_t += 1 of every parameter that received a gradient"""
         for i, (p, *_r) in enumerate(self._slots):
@@ -432,120 +442,38 @@ class _FlatAdaptiveEMA(FlatArenaOptimizer):
         ts = sorted({t for (p, *_r), t in zip(self._slots, self._steps) if getattr(p, "_ydl_touched", False)})
         return {t: c for c, t in enumerate(ts)}
 
-    def _runs(self, commit: bool = False) -> List[List]:
-        """maximal runs of consecutive slots with identical (touched, group, step count) state.  ``commit`` is accepted for the
-        protocol of FlatSGDEMA and ignored: the step counts advance in ``step`` / ``prepare_step``"""
-        runs: List[List] = []
-        rms = self.RULE == L.OPT_RMSPROP
-        for (p, off, n, gi), t in zip(self._slots, self._steps):
-            touched = bool(getattr(p, "_ydl_touched", False))
-            key = (touched, gi, t if touched and not rms else 0)
-            if runs and runs[-1][0] == key and runs[-1][2] == off:
-                runs[-1][2] = off + n
-            else:
-                runs.append([key, off, off + n])
-        return runs
+    def _run_state(self, i: int, p: nn.Parameter, touched: bool) -> int:
+        """the step count: runs never span two bias-correction classes"""
+        return self._steps[i] if touched and self.RULE != L.OPT_RMSPROP else 0
 
-    def _run_rows(self, runs) -> tuple:
-        """rows {offset, n_decay, n_params, n_total, lr index, flags, bias-correction class, 0} of ydl_optim_ema_step_multi"""
-        cls = self._classes()
-        rows = []
-        for (touched, gi, t), a, b in runs:
-            n = b - a
-            if touched:
-                rows.append((a, n if gi == 0 else 0, n, n, gi, 1 if gi == 0 else 0, cls.get(t, 0), 0))
-            elif self.ema_arena is not None:
-                rows.append((a, 0, 0, n, 0, 0, 0, 0))
-        if self.ema_arena is not None and self.n_total > self.n_params:
-            rows.append((self.n_params, 0, 0, self.n_total - self.n_params, 0, 0, 0, 0))
-        return tuple(rows)
+    def _row_tail(self, gi: int, t: int, cls) -> tuple:
+        return 1 if gi == 0 else 0, cls.get(t, 0), 0
 
-    # ------------------------------------------------------------------ graph-capturable step
-    def prepare_step(self, grad_scale: float = 1.0) -> None:
-        """host half of a step: advance the EMA counter and the step counts of the live parameters, and push the hyper-parameters,
-        the bias corrections of every class and the EMA decay to the device vector the captured kernels read (call OUTSIDE the
-        graph, before replaying it; layout: ydl.h, ydl_optim_ema_step_dev)"""
-        lr_bias, lr_w, lr_bn = (float(g["lr"]) for g in self.param_groups)
-        lrs = (lr_w, lr_bn, lr_bias)
-        d = self._ema_d(0.0)
-        self._advance()
+    def _hyper_vals(self, lrs, wd, grad_scale, d) -> List[float]:
+        b1, b2, eps = self._betas()
+        return lrs + [b1, wd, grad_scale, d, b2, eps, 1.0 - b1, 1.0 - b2, 1.0 - lrs[0] * wd]
+
+    def _class_vals(self, vals: List[float]) -> List[float]:
+        """the bias corrections of every class, per lr index"""
         cls = self._classes()
         if len(cls) > L.OPT_MAX_CLASSES:
             raise RuntimeError(f"{len(cls)} distinct step counts among the live parameters: the device hyper vector holds "
                                f"{L.OPT_MAX_CLASSES} bias-correction classes (use step(), which has no such limit)")
-        b1, b2, eps = self._betas()
-        wd = float(self.param_groups[1]["weight_decay"])
-        vals = [0.0] * self._HYPER_FLOATS
-        vals[0:12] = [lr_w, lr_bn, lr_bias, b1, wd, grad_scale, d, b2, eps, 1.0 - b1, 1.0 - b2, 1.0 - lr_w * wd]
+        tail = [0.0] * (self._HYPER_FLOATS - len(vals))
         for t, c in cls.items():
             for i in range(3):
-                vals[12 + 4 * c + i], vals[12 + 4 * c + 3] = self._corrections(t, lrs[i])
-        self.ensure_hyper()
-        i = self._hyper_slot
-        self._hyper_slot = (i + 1) % len(self._hyper_ring)
-        h, ev = self._hyper_ring[i]
-        if self._hyper_used[i]:
-            ev.synchronize()              # normally long complete (8 steps ago)
-        h.copy_(torch.tensor(vals, dtype=torch.float64))         # one rounding, double -> f32
-        self._hyper_dev.copy_(h, non_blocking=True)
-        ev.record()
-        self._hyper_used[i] = True
+                tail[4 * c + i], tail[4 * c + 3] = self._corrections(t, vals[i])
+        return tail
 
-    @torch.no_grad()
-    def step_device_hyper(self) -> None:
-        """device half: the update with everything read from ``_hyper_dev`` (capturable).  Changes no host state: ``prepare_step``
-        has advanced the counters"""
-        st = _stream()
-        pa, ga, s1, s2, ea = self.params_arena, self.grads_arena, self.state1_arena, self.state2_arena, self.ema_arena
-        use_ema = 1 if ea is not None else 0
-        hp = _p(self._hyper_dev)
-        rows = self._run_rows(self._runs())
-        # one launch for all runs; inside a recording / capture pass a NEW table must not be allocated (private pool), so a miss
-        # there takes the per-run launches below (see FlatSGDEMA.step_device_hyper)
-        tab = getattr(self, "_runs_dev", None)
-        if (tab is None or tab[0] != rows) and rows and L.recorder() is None and not torch.cuda.is_current_stream_capturing():
-            tab = self._runs_table(rows)
-            self._runs_dev = tab
-        if tab is not None and tab[0] == rows:
-            if rows:
-                L.call("ydl_optim_ema_step_multi", self.RULE, _p(pa), _p(ga), _p(s1), _p(s2), _p(ea) if ea is not None else None,
-                       _p(tab[1]), len(rows), max(r[3] for r in rows), hp, use_ema, st)
-            config.bump_weight_epoch()
-            return
-        for off, nd, npar, n, gi, fl, c, _z in rows:
-            if npar:
-                L.call("ydl_optim_ema_step_dev", self.RULE, _p(pa[off:]), _p(ga[off:]), _p(s1[off:]), _p(s2[off:]),
-                       _p(ea[off:]) if ea is not None else None, nd, npar, n, hp, gi, c, fl & 1, use_ema, st)
-            else:                       # EMA only (dead parameters, float buffers): gradients and state are not read
-                L.call("ydl_optim_ema_step_dev", self.RULE, _p(pa[off:]), _p(ga), _p(s1), _p(s2), _p(ea[off:]), 0, 0, n, hp, 0, 0, 0, 1, st)
-        config.bump_weight_epoch()
+    def _dev_args(self, row) -> tuple:
+        """lr index, bias-correction class, weight decay"""
+        return row[4], row[6], row[5] & 1
 
-    @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0):
-        lr_bias, lr_w, lr_bn = (float(g["lr"]) for g in self.param_groups)
-        lrs = (lr_w, lr_bn, lr_bias)
-        b1, b2, eps = self._betas()
-        wd = float(self.param_groups[1]["weight_decay"])
-        d = self._ema_d(-1.0)
-        self._advance()
-        st = _stream()
-        pa, ga, s1, s2, ea = self.params_arena, self.grads_arena, self.state1_arena, self.state2_arena, self.ema_arena
-        for (touched, gi, t), a, b in self._runs():
-            n = b - a
-            eptr = _p(ea[a:b]) if ea is not None else None
-            if touched:
-                step_size, bc2s = self._corrections(t, lrs[gi])
-                L.call("ydl_optim_ema_step", self.RULE, _p(pa[a:b]), _p(ga[a:b]), _p(s1[a:b]), _p(s2[a:b]), eptr, n if gi == 0 else 0, n, n,
-                       step_size, bc2s, 1.0 - lr_w * wd, wd if gi == 0 else 0.0, b1, b2, 1.0 - b1, 1.0 - b2, eps, grad_scale, d, st)
-            elif ea is not None:
-                L.call("ydl_optim_ema_step", self.RULE, _p(pa[a:b]), _p(ga), _p(s1), _p(s2), eptr, 0, 0, n,
-                       0.0, 1.0, 1.0, 0.0, b1, b2, 1.0 - b1, 1.0 - b2, eps, 1.0, d, st)
-        if ea is not None and self.n_total > self.n_params:
-            a, b = self.n_params, self.n_total
-            L.call("ydl_optim_ema_step", self.RULE, _p(pa[a:b]), _p(ga), _p(s1), _p(s2), _p(ea[a:b]), 0, 0, b - a,
-                   0.0, 1.0, 1.0, 0.0, b1, b2, 1.0 - b1, 1.0 - b2, eps, 1.0, d, st)
-        config.bump_weight_epoch()
-        return None
+    def _host_args(self, gi, t, hv) -> tuple:
+        """step_size, bc2_sqrt, decay_mul, weight decay, beta1, beta2, 1 - beta1, 1 - beta2, eps, grad_scale, EMA decay"""
+        if gi is None:
+            return 0.0, 1.0, 1.0, 0.0, hv[3], hv[7], hv[9], hv[10], hv[8], 1.0, hv[6]
+        return (*self._corrections(t, hv[gi]), hv[11], hv[4] if gi == 0 else 0.0, hv[3], hv[7], hv[9], hv[10], hv[8], hv[5], hv[6])
 
     # ------------------------------------------------------------------ checkpoint state
     def state_dict(self):
