@@ -761,6 +761,44 @@ int ydl_label_bincount(const void* labels, int is_i64, int64_t n, int nbins, int
 int ydl_labels_render(int mode, const uint8_t* pred, const uint8_t* target, const float* img, const uint8_t* palette, int npal,
                       uint8_t* out, int N, int H, int W, int bgr, void* stream);
 
+/* ---- ConvNeXt block pieces (csrc/convnext.hip) -----------------------------------------------------------------------------
+ * NHWC rows with element strides (any tensor may be a channel slice of a wider buffer: channels outside [0, C) are neither read
+ * into a result nor written), f32 or bf16 storage, f32 arithmetic, 16-byte accesses (data pointers 16-byte aligned, strides whole
+ * chunks, C a multiple of 8).  No atomics: every per-channel sum goes through one partial row per CTA in `ws` (the *_ws_bytes
+ * functions size it; pure host functions) and a fixed-order fold in double, so two runs give the same bits.  Parameter gradients
+ * are ADDED into their destination, which holds zeros or a running sum.  Bad arguments are refused on the host before any launch.
+ *
+ * LayerNorm over C at every pixel, 8 <= C <= 1024 (ydl_ln_supported):
+ *   u = x + pre_bias[c] (pre_bias: f32 [C], or NULL), mu = mean_c u, var = mean_c (u - mu)^2 (second pass over the
+ *   registers), r = 1 / sqrtf(var + eps), y = (u - mu) * r * gamma[c] + beta[c]; stats: f32 [npix][2] = (mu, r), or NULL (eval).
+     The f32 parameter rows need no alignment.
+ * Backward, one pass over x and dy, with g = dy * gamma and xh = (u - mu) * r:
+ *   dx (+)= r * (g - mean_c g - xh * mean_c (g * xh)) (accumulate != 0 adds in f32 with one rounding),
+ *   dgamma[c] += sum_p dy * xh, dbeta[c] += sum_p dy, dpre_bias[c] += sum_p (the new dx term); dpre_bias may be NULL. */
+int ydl_ln_supported(int C);
+int ydl_ln_fwd(int dtype, const void* x, int ldx, const float* pre_bias, const float* gamma, const float* beta, float eps,
+               void* y, int ldy, float* stats, int64_t npix, int C, void* stream);
+int64_t ydl_ln_bwd_ws_bytes(int64_t npix, int C);
+int ydl_ln_bwd(int dtype, const void* x, int ldx, const float* pre_bias, const float* gamma, const float* stats,
+               const void* dy, int lddy, void* dx, int lddx, int accumulate, float* dgamma, float* dbeta, float* dpre_bias,
+               float* ws, int64_t npix, int C, void* stream);
+/* bias + exact GELU: u = z + bias[c], y = 0.5 * u * (1 + erff(u / sqrt 2)).  Backward: dz = dy * (Phi(u) + u * phi(u)),
+ * dbias[c] += sum_p dz; dz may be dy's own buffer. */
+int ydl_bias_gelu_fwd(int dtype, const void* z, int ldz, const float* bias, void* y, int ldy, int64_t npix, int C, void* stream);
+int64_t ydl_bias_gelu_bwd_ws_bytes(int64_t npix, int C);
+int ydl_bias_gelu_bwd(int dtype, const void* z, int ldz, const float* bias, const void* dy, int lddy, void* dz, int lddz,
+                      float* dbias, float* ws, int64_t npix, int C, void* stream);
+/* layer-scaled residual with per-sample keep factors (stochastic depth, "row" mode): out[n][p][c] = x + keep[n] * gamma[c] * y over
+ * N samples of hw pixels; keep: f32 [N], or NULL meaning 1.  The product is formed in f32 and added to x with one rounding; a
+ * sample with keep[n] == 0 gets x bit for bit.  Backward: dy = keep[n] * gamma[c] * dout, dgamma[c] += sum keep[n] * dout * y,
+ * dx (+)= dout; dx may be NULL (the caller aliases the residual's gradient). */
+int ydl_scale_res_fwd(int dtype, const void* y, int ldy, const float* gamma, const float* keep, const void* x, int ldx,
+                      void* out, int ldo, int N, int64_t hw, int C, void* stream);
+int64_t ydl_scale_res_bwd_ws_bytes(int N, int64_t hw, int C);
+int ydl_scale_res_bwd(int dtype, const void* dout, int lddo, const void* y, int ldy, const float* gamma, const float* keep,
+                      void* dy, int lddy, void* dx, int lddx, int accumulate, float* dgamma, float* ws, int N, int64_t hw,
+                      int C, void* stream);
+
 /* ---- activations with a run-time parameter ----------------------------------------------------------------------------
  * The six streaming BatchNorm entry points above, each with one more argument after `act`: act_param, the parameter of the
  * activation (the negative slope of YDL_ACT_LEAKY; ignored by every other code).  The entry points without it are these with

@@ -16,7 +16,8 @@ from .modules import (GAM, AttentionConv, AttentionStem, C2f, C3, C3k2, C3_DCNV3
                       Conv, C2f_DCN, C3_DCN, C3_DCNCommon, Bottleneck_DCN, DCNv2, DCNv3, DCNV3_YoLo, DeformConv2d, Linear, MaxPool2d, SegmentHead, SPPF, Upsample, autopad,
                       C3Ghost, DWConv, GhostBottleneck, GhostConv, C3TR, TransformerBlock, TransformerLayer, ASPP, RFB, BasicConv,
                       SPP, C3SPP, SimConv, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF, CrossConv, C3x, ConvTranspose2d, DWConvTranspose2d,
-                      Focus, Contract, Expand, BottleneckCSP, BatchNorm2d)
+                      Focus, Contract, Expand, BottleneckCSP, BatchNorm2d,
+                      LayerNorm2d, CNBlock, convnext_tiny1, convnext_tiny2, convnext_tiny3, convnext_key_map)
 from .deform import deform_conv2d
 from . import activations
 from .activations import AconC, FReLU, Hardswish, MemoryEfficientMish, MetaAconC, Mish, SiLU

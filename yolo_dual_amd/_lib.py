@@ -203,6 +203,16 @@ SIGNATURES = {
     "ydl_confusion_labels": (_i, [_vp, _i64, _i64, _vp, _i, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
     "ydl_label_bincount": (_i, [_vp, _i, _i64, _i, _vp, _vp]),
     "ydl_labels_render": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "ydl_ln_supported": (_i, [_i]),
+    "ydl_ln_fwd": (_i, [_i, _vp, _i, _vp, _vp, _vp, _f, _vp, _i, _vp, _i64, _i, _vp]),
+    "ydl_ln_bwd_ws_bytes": (_i64, [_i64, _i]),
+    "ydl_ln_bwd": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
+    "ydl_bias_gelu_fwd": (_i, [_i, _vp, _i, _vp, _vp, _i, _i64, _i, _vp]),
+    "ydl_bias_gelu_bwd_ws_bytes": (_i64, [_i64, _i]),
+    "ydl_bias_gelu_bwd": (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _i, _vp]),
+    "ydl_scale_res_fwd": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i64, _i, _vp]),
+    "ydl_scale_res_bwd_ws_bytes": (_i64, [_i, _i64, _i]),
+    "ydl_scale_res_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i64, _i, _vp]),
     "ydl_replay_create": (_vp, []),
     "ydl_replay_destroy": (None, [_vp]),
     "ydl_replay_fn_count": (_i, []),

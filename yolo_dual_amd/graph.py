@@ -18,7 +18,7 @@ from typing import List, Optional
 import torch
 
 from . import config
-from .modules import _BNHolder
+from .modules import _BNHolder, refuse_stochastic_depth
 from .optim import FlatArenaOptimizer
 
 
@@ -35,6 +35,7 @@ class GraphedTrainStep:
         self._bns: List[_BNHolder] = [m for m in model.modules() if isinstance(m, _BNHolder)]
         if getattr(criterion, "sync", False):
             raise ValueError("graph capture needs a loss that does not sync: SegmentationLoss(..., sync=False)")
+        refuse_stochastic_depth(model, "graph capture")
         cur = torch.cuda.current_stream()
         s = torch.cuda.Stream()
         s.wait_stream(cur)

@@ -31,7 +31,7 @@ from .modules import (ASPP, RFB, GAM, AttentionConv, AttentionStem, BasicBlock, 
                       C3Common, C3Ghost, C3k2, C3TR, Concat, DWConv, GhostBottleneck, GhostConv, TransformerBlock,
                       Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region,
                       SPP, C3SPP, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF, CrossConv, C3x, ConvTranspose2d, DWConvTranspose2d,
-                      Focus, Contract, Expand, BottleneckCSP, BatchNorm2d)
+                      Focus, Contract, Expand, BottleneckCSP, BatchNorm2d, convnext_tiny1, convnext_tiny2, convnext_tiny3)
 from .tape import Tape, Var
 
 LOGGER = logging.getLogger("yolo_dual_amd")
@@ -545,7 +545,8 @@ _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": 
                 "ASPP": ASPP, "RFB": RFB, "SPP": SPP, "C3SPP": C3SPP, "SimSPPF": SimSPPF, "SPPCSPC": SPPCSPC,
                 "SPPCSPC_group": SPPCSPC_group, "SimCSPSPPF": SimCSPSPPF, "CrossConv": CrossConv, "C3x": C3x,
                 "nn.ConvTranspose2d": ConvTranspose2d, "DWConvTranspose2d": DWConvTranspose2d, "Focus": Focus,
-                "BottleneckCSP": BottleneckCSP, "Contract": Contract, "Expand": Expand, "nn.BatchNorm2d": BatchNorm2d}
+                "BottleneckCSP": BottleneckCSP, "Contract": Contract, "Expand": Expand, "nn.BatchNorm2d": BatchNorm2d,
+                "convnext_tiny1": convnext_tiny1, "convnext_tiny2": convnext_tiny2, "convnext_tiny3": convnext_tiny3}
 
 
 # the activations a yaml can name: ``nn.Name(...)`` is torch's class, a bare ``Name(...)`` the class of yolo_dual_amd.activations where
@@ -648,6 +649,8 @@ def _parse_model(d: dict, ch: List[int], deformable: bool = False):
         elif cls is BatchNorm2d:                         # models/yolo.py:330-331
             args = [ch[f]]
             c2 = ch[f]
+        elif cls in (convnext_tiny1, convnext_tiny2, convnext_tiny3):      # models/yolo.py:367-368: c2 as written, no width gain
+            c2 = args[0]
         elif cls is Contract:                            # models/yolo.py:341-342
             c2 = ch[f] * args[0] ** 2
         elif cls is Expand:                              # models/yolo.py:343-344

@@ -2447,3 +2447,241 @@ class C3TR(C3Common):
         self.m._fwd(tape, self.cv1._fwd(tape, x), out=left)
         self.cv2._fwd(tape, x, out=right)
         return self.cv3._fwd(tape, cat)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# ConvNeXt Tiny backbone rows (models/common.py:1241-1269: the slices features[:4], [4:6], [6:8] of torchvision's convnext_tiny).
+# torchvision is not a dependency: its definition is restated here with its state_dict keys, so a user's own state_dict loads.
+# ----------------------------------------------------------------------------------------------------------
+class LayerNorm2d(YdlModule):
+    """LayerNorm over the channels of an (N, C, H, W) tensor (torchvision's LayerNorm2d; inside a CNBlock, ``nn.LayerNorm(C)`` between
+    the two permutes): parameters ``weight``, ``bias``.  One launch each way on the NHWC rows (Tape.layer_norm), C a multiple of 8 up
+    to 1024.  The class name contains "Norm": ``smart_optimizer`` keeps its weight out of the decayed group."""
+    _keep_init = True
+
+    def __init__(self, normalized_shape, eps=1e-6):
+        super().__init__()
+        C = normalized_shape[0] if isinstance(normalized_shape, (list, tuple)) and len(normalized_shape) == 1 else normalized_shape
+        if isinstance(C, bool) or not isinstance(C, int) or C < 8 or C > 1024 or C % 8:
+            raise ValueError(f"LayerNorm2d: normalized_shape={normalized_shape!r} must be one channel count, a multiple of 8 in 8..1024")
+        self.normalized_shape, self.eps = (C,), float(eps)
+        self.weight = nn.Parameter(torch.ones(C))
+        self.bias = nn.Parameter(torch.zeros(C))
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None, pre_bias=None) -> Var:
+        return tape.layer_norm(x, self, pre_bias=pre_bias, out=out)
+
+    def extra_repr(self):
+        return f"{self.normalized_shape}, eps={self.eps}"
+
+
+class _PatchConv2d(_GemmWeights, nn.Conv2d):
+    """``nn.Conv2d(c1, c2, k, k, bias=True)``, a patchify convolution: run as space-to-depth and a 1x1 GEMM over k*k*c1 channels
+    (Tape.patch_conv).  The weight [c2, c1, k, k] in channels_last storage is that GEMM's [c2][1][k*k*c1] master as it stands."""
+    _keep_init = True
+    _wname = "patch Conv2d"
+
+    def __init__(self, c1, c2, k):
+        super().__init__(c1, c2, k, k)
+        self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
+        nn.init.trunc_normal_(self.weight, std=0.02)
+        nn.init.zeros_(self.bias)
+        self.patch = k
+        self._wcache = {}
+
+    def _krsc(self, t: torch.Tensor) -> torch.Tensor:
+        if t.dim() == 4:
+            t = t.permute(0, 2, 3, 1)
+            if not t.is_contiguous():
+                return t                      # _master_krsc re-homes the parameter; a gradient laid out otherwise is refused by wgrad
+            return t.view(t.shape[0], 1, -1)
+        return t
+
+    def _gemm_dims(self):
+        return self.out_channels, 1, self.patch * self.patch * self.in_channels
+
+    def forward(self, x):
+        if isinstance(x, Var):
+            return self._fwd(x.tape, x)
+        return run_region(self, [x])
+
+    def _fwd(self, tape: Tape, x: Var, out: Optional[Var] = None) -> Var:
+        k = self.patch
+        if x.LH % k or x.LW % k:
+            raise ValueError(f"Conv2d({self.in_channels}, {self.out_channels}, {k}, {k}): the {x.LH} x {x.LW} map is not a multiple of {k}")
+        return tape.patch_conv(x, self, out=out)
+
+
+_PatchConv2d.takes_list = False
+
+
+class _DWConv2d(nn.Conv2d):
+    """``nn.Conv2d(C, C, 7, padding=3, groups=C, bias=True)`` of a CNBlock: the weight [C, 1, k, k] is the [C][k*k] master the depth-wise
+    kernels read (Tape.dw_conv); the bias is applied by the LayerNorm behind it."""
+    _keep_init = True
+
+    def __init__(self, dim, k=7):
+        super().__init__(dim, dim, k, padding=k // 2, groups=dim)
+        nn.init.trunc_normal_(self.weight, std=0.02)
+        nn.init.zeros_(self.bias)
+        self.k = k
+
+    def master_dw(self) -> torch.Tensor:
+        w = self.weight.detach().permute(0, 2, 3, 1)
+        return w if w.is_contiguous() else w.contiguous()
+
+    def grad_dw(self) -> torch.Tensor:
+        if self.weight.grad is None:
+            self.weight.grad = torch.zeros_like(self.weight)
+        g = self.weight.grad.permute(0, 2, 3, 1)
+        if not g.is_contiguous():
+            raise RuntimeError("CNBlock depth-wise weight gradient must be [C][k*k]-contiguous")
+        return g
+
+    def forward(self, x):  # pragma: no cover - run through CNBlock
+        raise RuntimeError("run through CNBlock")
+
+
+class _CNLinear(Linear):
+    """a CNBlock's Linear: torchvision's init (trunc_normal 0.02, zero bias)"""
+
+    def __init__(self, in_features, out_features):
+        super().__init__(in_features, out_features)
+        nn.init.trunc_normal_(self.weight, std=0.02)
+        nn.init.zeros_(self.bias)
+
+
+class CNBlock(YdlModule):
+    """torchvision's CNBlock: ``x + stochastic_depth(layer_scale * fc2(GELU(fc1(LayerNorm(dwconv7x7(x))))))``, stochastic depth in "row"
+    mode.  state_dict: block.0 (depth-wise conv, weight [dim,1,7,7] and bias), block.2 (LayerNorm, eps 1e-6), block.3 (Linear dim ->
+    4 dim), block.5 (Linear 4 dim -> dim), layer_scale [dim,1,1]; block.1 / .4 / .6 hold no state (the permutes and the GELU).
+
+    Launches: the depth-wise kernel without bias; LayerNorm, which adds that bias on the way in; the fc1 GEMM without bias; bias + erf
+    GELU; the fc2 GEMM with bias; the layer-scaled residual, which takes the per-sample keep factors."""
+    _keep_init = True
+
+    def __init__(self, dim, layer_scale=1e-6, stochastic_depth_prob=0.0):
+        super().__init__()
+        if isinstance(dim, bool) or not isinstance(dim, int) or dim < 8 or dim > 1024 or dim % 8:
+            raise ValueError(f"CNBlock: dim={dim!r} must be a multiple of 8 in 8..1024")
+        p = float(stochastic_depth_prob)
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"CNBlock: stochastic_depth_prob={stochastic_depth_prob!r} must be in [0, 1)")
+        self.block = nn.Sequential(_DWConv2d(dim), nn.Identity(), LayerNorm2d(dim, eps=1e-6), _CNLinear(dim, 4 * dim), nn.Identity(),
+                                   _CNLinear(4 * dim, dim), nn.Identity())
+        self.layer_scale = nn.Parameter(torch.ones(dim, 1, 1) * layer_scale)
+        self.stochastic_depth_prob = p
+        self.generator = None             # torch.Generator of the keep draws, or None for the device's default generator
+
+    def draw_keep(self, N: int, device) -> Optional[torch.Tensor]:
+        """the per-sample keep factors bernoulli(1 - p) / (1 - p) of this forward as an f32 [N] tensor on the device, or None (eval, p = 0)"""
+        p = self.stochastic_depth_prob
+        if not self.training or p == 0.0:
+            return None
+        if L.recorder() is not None:
+            raise NotImplementedError("stochastic depth (CNBlock with stochastic_depth_prob > 0 in training) draws its keep factors with "
+                                      "torch before the launch: a recorded step cannot replay it; build the rows with stochastic_depth_prob=0")
+        keep = torch.empty(N, dtype=torch.float32, device=device).bernoulli_(1.0 - p, generator=self.generator)
+        return keep.div_(1.0 - p)
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        dw, ln, fc1, fc2 = self.block[0], self.block[2], self.block[3], self.block[5]
+        x = tape.materialize(x)
+        keep = self.draw_keep(x.N, tape.device)
+        t = tape.dw_conv(x, dw)
+        t = tape.layer_norm(t, ln, pre_bias=dw.bias)
+        t = tape.conv_bias(t, fc1, bias=False)
+        t = tape.bias_gelu(t, fc1)
+        t = tape.conv_bias(t, fc2)
+        return tape.scale_residual(t, self, keep, x)
+
+    def extra_repr(self):
+        return f"stochastic_depth_prob={self.stochastic_depth_prob:.4g}"
+
+
+def refuse_stochastic_depth(model: nn.Module, who: str) -> None:
+    """the recorded-step paths re-issue one step's launches: the keep factors of stochastic depth are drawn by torch before the launch,
+    every step anew, which a recording cannot repeat"""
+    bad = [n for n, m in model.named_modules() if isinstance(m, CNBlock) and m.training and m.stochastic_depth_prob > 0.0]
+    if bad:
+        raise NotImplementedError(f"{who} cannot re-draw the keep factors of stochastic depth: {len(bad)} CNBlock(s) in training mode have "
+                                  f"stochastic_depth_prob > 0 (first: {bad[0]}); build the rows with stochastic_depth_prob=0")
+
+
+_CN_DIMS, _CN_DEPTHS = (96, 192, 384, 768), (3, 3, 9, 3)
+
+
+def _cn_stage(i: int, sd: float, ls: float) -> nn.Sequential:
+    """stage i of convnext_tiny: block j of the 18 (counted over the whole network) gets p = sd * j / 17"""
+    first, total = sum(_CN_DEPTHS[:i]), sum(_CN_DEPTHS)
+    return nn.Sequential(*(CNBlock(_CN_DIMS[i], ls, sd * (first + j) / (total - 1.0)) for j in range(_CN_DEPTHS[i])))
+
+
+def _cn_down(i: int) -> nn.Sequential:
+    return nn.Sequential(LayerNorm2d(_CN_DIMS[i - 1]), _PatchConv2d(_CN_DIMS[i - 1], _CN_DIMS[i], 2))
+
+
+class _ConvNeXtRow(YdlModule):
+    """one of the three rows: ``self.model`` is the slice of torchvision's ``convnext_tiny().features`` the reference keeps; the row's
+    positional argument (the yaml's channel count) is ignored, as in the reference"""
+    _keep_init = True
+    _first = 0          # index in ``features`` of model.0
+    _stride = 2         # the row's total down-sampling
+
+    def __init__(self, ignore=None, *, stochastic_depth_prob=0.1, layer_scale=1e-6):
+        super().__init__()
+        self.model = nn.Sequential(*self._parts(float(stochastic_depth_prob), float(layer_scale)))
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        if x.LH % self._stride or x.LW % self._stride:
+            raise ValueError(f"{type(self).__name__}: the {x.LH} x {x.LW} map is not a multiple of {self._stride}, the row's stride")
+        for part in self.model:
+            for sub in part:
+                x = sub._fwd(tape, x)
+        return x
+
+
+class convnext_tiny1(_ConvNeXtRow):
+    """models/common.py:1241-1249: features[:4] = stem (Conv2d(3, 96, 4, 4) + LayerNorm2d), 3 x CNBlock(96), LayerNorm2d + Conv2d(96, 192,
+    2, 2), 3 x CNBlock(192): 3 -> 192 channels at 1/8 of the input size"""
+    _stride = 8
+
+    def _parts(self, sd, ls):
+        return [nn.Sequential(_PatchConv2d(3, 96, 4), LayerNorm2d(96)), _cn_stage(0, sd, ls), _cn_down(1), _cn_stage(1, sd, ls)]
+
+
+class convnext_tiny2(_ConvNeXtRow):
+    """models/common.py:1251-1259: features[4:6] = LayerNorm2d + Conv2d(192, 384, 2, 2), 9 x CNBlock(384)"""
+    _first = 4
+
+    def _parts(self, sd, ls):
+        return [_cn_down(2), _cn_stage(2, sd, ls)]
+
+
+class convnext_tiny3(_ConvNeXtRow):
+    """models/common.py:1261-1269: features[6:8] = LayerNorm2d + Conv2d(384, 768, 2, 2), 3 x CNBlock(768)"""
+    _first = 6
+
+    def _parts(self, sd, ls):
+        return [_cn_down(3), _cn_stage(3, sd, ls)]
+
+
+def convnext_key_map(keys=None) -> dict:
+    """torchvision ``convnext_tiny`` state_dict key -> (row index 0..2, key inside that row): ``features.N.rest`` belongs to row 0 for
+    N < 4, row 1 for N in (4, 5), row 2 for N in (6, 7), as ``model.M.rest`` with M = N, N - 4, N - 6.  ``keys``: the keys to map (the
+    classifier's are left out); default: every key of the three rows.  Nothing is downloaded: the state_dict is the user's own."""
+    rows = (convnext_tiny1, convnext_tiny2, convnext_tiny3)
+    if keys is None:
+        keys = [f"features.{r._first + int(k.split('.')[1])}.{k.split('.', 2)[2]}" for r in rows for k in r().state_dict()]
+    out = {}
+    for k in keys:
+        parts = k.split(".", 2)
+        if len(parts) != 3 or parts[0] != "features" or not parts[1].isdigit() or int(parts[1]) > 7:
+            continue
+        n = int(parts[1])
+        row = 0 if n < 4 else 1 if n < 6 else 2
+        out[k] = (row, f"model.{n - rows[row]._first}.{parts[2]}")
+    return out
+
+
+__all__ += ["LayerNorm2d", "CNBlock", "convnext_tiny1", "convnext_tiny2", "convnext_tiny3", "convnext_key_map"]

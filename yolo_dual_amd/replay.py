@@ -29,7 +29,7 @@ import torch
 
 from . import _lib as L
 from . import config
-from .modules import _BNHolder
+from .modules import _BNHolder, refuse_stochastic_depth
 from .optim import FlatArenaOptimizer
 
 _G = L._G
@@ -132,6 +132,7 @@ class ReplayedTrainStep:
                  prioritize: bool = False):
         if getattr(criterion, "sync", False):
             raise ValueError("a launch list needs a loss that does not sync: SegmentationLoss(..., sync=False)")
+        refuse_stochastic_depth(model, "a launch list")
         self.model, self.criterion, self.opt, self.dp = model, criterion, optimizer, dp
         self.imgs, self.targets = imgs, targets
         self.multi = dp is not None and dp.reducer.world > 1

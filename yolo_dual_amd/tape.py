@@ -1290,6 +1290,180 @@ class Tape:
         self.bw.append(bw)
         return out
 
+    # ------------------------------------------------------------------ ConvNeXt pieces (csrc/convnext.hip)
+    def _touch(self, *params) -> None:
+        for p in params:
+            if p is not None and p.requires_grad:
+                _cfg.mark_touched(p)
+
+    def _cn_out(self, who: str, x: Var, out: Optional[Var]) -> Var:
+        if x.C % 8:
+            raise RuntimeError(f"{who}: {x.C} channels are not a multiple of 8")
+        if out is None:
+            return self.new(x.N, x.C, x.H, x.W)
+        if (out.N, out.C, out.H, out.W) != (x.N, x.C, x.H, x.W) or not out.aligned():
+            raise RuntimeError(f"{who}: the output slice has the wrong shape or is not 16-byte aligned")
+        return out
+
+    def _grad_or_scratch(self, v: Var):
+        """(buffer, ld, accumulate) for a launch that always writes d/dv: v's gradient, or a scratch tensor when nobody wants it"""
+        if v.need:
+            g, acc = self.grad_target(v)
+            return g, v.ld, acc
+        s = self.new(v.N, v.C, v.H, v.W)
+        return s.t, s.ld, 0
+
+    def dw_conv(self, x: Var, m) -> Var:
+        """plain depth-wise k x k convolution, stride 1, padding k // 2, no BatchNorm: ydl_dwconv2_fwd without its statistics rows.
+        ``m`` holds the [C][k*k] master (``master_dw`` / ``grad_dw``); its bias, if any, belongs to the consumer
+        (``layer_norm(pre_bias=...)``)."""
+        x = self._flat(x)
+        C, k = x.C, m.k
+        y = self.new(x.N, C, x.H, x.W)
+        L.call("ydl_dwconv2_fwd", self.dt, _p(x.t), x.ld, _p(m.master_dw()), _p(y.t), y.ld, None, x.N, x.H, x.W, C, k, 1, _stream())
+        if not self.record:
+            return y
+        if x.need:
+            self._use(x)
+
+        def bw():
+            if not y.is_set():
+                return
+            st = _stream()
+            dy = self._gbuf(y)
+            if m.weight.requires_grad:
+                ws = torch.empty(L.lib().ydl_dwconv2_wgrad_ws_bytes(C, k) // 4, dtype=torch.float32, device=self.device)
+                L.call("ydl_dwconv2_wgrad", self.dt, _p(x.t), x.ld, _p(dy), y.ld, _p(m.grad_dw()), _p(ws), x.N, x.H, x.W, C, k, 1, st)
+                self._touch(m.weight)
+            if x.need:
+                gx, acc = self.grad_target(x)
+                L.call("ydl_dwconv2_dgrad", self.dt, _p(dy), y.ld, _p(m.master_dw()), _p(gx), x.ld, acc, x.N, x.H, x.W, C, k, 1, st)
+        self.bw.append(bw)
+        return y
+
+    def layer_norm(self, x: Var, m, pre_bias=None, out: Optional[Var] = None) -> Var:
+        """LayerNorm over the channels of every pixel: out = (u - mean_c u) / sqrt(var_c u + m.eps) * m.weight + m.bias with
+        u = x + pre_bias (``pre_bias``: an f32 [C] parameter, the bias of the depth-wise convolution in front, or None).  One launch
+        each way (ydl_ln_fwd / ydl_ln_bwd); the backward adds the three per-channel sums into the parameters' gradients."""
+        x = self._flat(x)
+        C = x.C
+        if not L.lib().ydl_ln_supported(C):
+            raise RuntimeError(f"layer_norm: {C} channels are outside the served set (a multiple of 8 in 8..1024)")
+        ps = (m.weight, m.bias) + ((pre_bias,) if pre_bias is not None else ())
+        if any(p.numel() != C or not p.is_contiguous() or p.dtype != torch.float32 for p in ps):
+            raise RuntimeError(f"layer_norm: weight / bias / pre_bias must be contiguous f32 rows of {C} channels")
+        out = self._cn_out("layer_norm", x, out)
+        stats = torch.empty((x.npix, 2), dtype=torch.float32, device=self.device) if self.record else None
+        L.call("ydl_ln_fwd", self.dt, _p(x.t), x.ld, _p(pre_bias), _p(m.weight), _p(m.bias), float(m.eps), _p(out.t), out.ld, _p(stats),
+               x.npix, C, _stream())
+        if not self.record:
+            return out
+        if x.need:
+            self._use(x)
+
+        def bw():
+            if not out.is_set():
+                return
+            gg, gb = self._param_grad(m.weight, self.device), self._param_grad(m.bias, self.device)
+            gp = self._param_grad(pre_bias, self.device) if pre_bias is not None else None
+            ws = torch.empty(L.lib().ydl_ln_bwd_ws_bytes(x.npix, C) // 4, dtype=torch.float32, device=self.device)
+            gx, ldx, acc = self._grad_or_scratch(x)
+            L.call("ydl_ln_bwd", self.dt, _p(x.t), x.ld, _p(pre_bias), _p(m.weight), _p(stats), _p(self._gbuf(out)), out.ld, _p(gx), ldx,
+                   acc, _p(gg), _p(gb), _p(gp), _p(ws), x.npix, C, _stream())
+            self._touch(*ps)
+        self.bw.append(bw)
+        return out
+
+    def bias_gelu(self, z: Var, m) -> Var:
+        """out = GELU(z + m.bias), the exact (erf) form; ``z`` is the output of the bias-free GEMM in front.  Backward: one pass
+        (ydl_bias_gelu_bwd) gives dz and adds the bias gradient into ``m.bias.grad``."""
+        z = self._flat(z)
+        C, b = z.C, m.bias
+        if b.numel() != C or not b.is_contiguous() or b.dtype != torch.float32:
+            raise RuntimeError(f"bias_gelu: the bias must be a contiguous f32 row of {C} channels")
+        out = self._cn_out("bias_gelu", z, None)
+        L.call("ydl_bias_gelu_fwd", self.dt, _p(z.t), z.ld, _p(b), _p(out.t), out.ld, z.npix, C, _stream())
+        if not self.record:
+            return out
+        if z.need:
+            self._use(z)
+
+        def bw():
+            if not out.is_set():
+                return
+            st = _stream()
+            dy = self._gbuf(out)
+            ws = torch.empty(L.lib().ydl_bias_gelu_bwd_ws_bytes(z.npix, C) // 4, dtype=torch.float32, device=self.device)
+            gz, acc = self.grad_target(z) if z.need else (None, 1)
+            # first writer of d/dz: straight into it; otherwise in place over dy, then added (or dropped when nobody wants it)
+            dst, ldd = (gz, z.ld) if not acc else (dy, out.ld)
+            L.call("ydl_bias_gelu_bwd", self.dt, _p(z.t), z.ld, _p(b), _p(dy), out.ld, _p(dst), ldd, _p(self._param_grad(b, self.device)),
+                   _p(ws), z.npix, C, st)
+            if z.need and acc:
+                L.call("ydl_copy2d", z.dt, _p(dy), out.ld, _p(gz), z.ld, z.npix, C, 1, st)
+            self._touch(b)
+        self.bw.append(bw)
+        return out
+
+    def scale_residual(self, y: Var, m, keep: Optional[torch.Tensor], x: Var) -> Var:
+        """out = x + keep[n] * m.layer_scale[c] * y: the layer-scaled residual of a ConvNeXt block with the per-sample keep factors of
+        stochastic depth (``keep``: f32 [N] on the device, or None for 1).  Backward: d/dy, the layer-scale gradient, and d/dx = d/dout,
+        which x adopts without a pass where it can (``_alias_grad``)."""
+        y, x = self._flat(y), self._flat(x)
+        C, hw, g = y.C, y.H * y.W, m.layer_scale
+        if (x.N, x.C, x.H, x.W) != (y.N, C, y.H, y.W):
+            raise RuntimeError("scale_residual: the branch and the residual differ in shape")
+        if g.numel() != C or not g.is_contiguous() or g.dtype != torch.float32:
+            raise RuntimeError(f"scale_residual: layer_scale must be a contiguous f32 row of {C} channels")
+        if keep is not None and (keep.numel() != y.N or keep.dtype != torch.float32 or not keep.is_contiguous()):
+            raise RuntimeError(f"scale_residual: keep must hold {y.N} f32 factors")
+        out = self._cn_out("scale_residual", y, None)
+        L.call("ydl_scale_res_fwd", self.dt, _p(y.t), y.ld, _p(g), _p(keep), _p(x.t), x.ld, _p(out.t), out.ld, y.N, hw, C, _stream())
+        if not self.record:
+            return out
+        for v in (y, x):
+            if v.need:
+                self._use(v)
+
+        def bw():
+            if not out.is_set():
+                return
+            st = _stream()
+            dout = self._gbuf(out)
+            ws = torch.empty(L.lib().ydl_scale_res_bwd_ws_bytes(y.N, hw, C) // 4, dtype=torch.float32, device=self.device)
+            gy, ldy, accy = self._grad_or_scratch(y)
+            if accy:                                    # another consumer wrote d/dy first: form ours aside, then add
+                tmp = self.new(y.N, C, y.H, y.W)
+                gy_, ldy = tmp.t, tmp.ld
+            else:
+                gy_ = gy
+            gx, accx = None, 0
+            if x.need and not self._alias_grad(x, out, dout):
+                gx, accx = self.grad_target(x)
+            L.call("ydl_scale_res_bwd", self.dt, _p(dout), out.ld, _p(y.t), y.ld, _p(g), _p(keep), _p(gy_), ldy, _p(gx), x.ld, accx,
+                   _p(self._param_grad(g, self.device)), _p(ws), y.N, hw, C, st)
+            if accy:
+                L.call("ydl_copy2d", y.dt, _p(gy_), ldy, _p(gy), y.ld, y.npix, C, 1, st)
+            if keep is not None:
+                self._keep.append(keep)
+            self._touch(g)
+        self.bw.append(bw)
+        return out
+
+    def patch_conv(self, x: Var, m, out: Optional[Var] = None) -> Var:
+        """patchify convolution, kernel = stride = ``m.patch``, no padding: ``space_to_depth(x, k, order=0)`` and the 1x1 ``conv_bias``
+        over k*k*Cin channels.  The parameter [Cout, Cin, k, k] in channels_last storage IS the [Cout][1][k*k*Cin] master of that 1x1
+        (channel (dy*k + dx)*Cin + c): no weight copy, no gradient re-layout.  The model's NCHW image takes the edge conversion
+        ``input_s2d`` instead of an interior pass."""
+        k = m.patch
+        if x.LH % k or x.LW % k:
+            raise ValueError(f"{m._wname}: the {x.LH} x {x.LW} map is not a multiple of the patch size {k}")
+        if x.ext_src is not None and x.real is None and not x.need:
+            xs = self.input_s2d(x.ext_src, k)
+        else:
+            xs = self.space_to_depth(x, k, order=0)
+        return self.conv_bias(xs, m, out=out)
+
     def concat(self, xs: Sequence[Var], align: bool = True) -> Var:
         """Concat along channels with the reference's auto-align (bilinear, align_corners=False, to the first
         input's size) — seg_diceloss_yolov5.py:484-507.
@@ -1680,10 +1854,10 @@ class Tape:
             ones, bias = shift(self.device)
             self._bn_apply(out, ones, bias, act, out, out.npix, round_up(out.C, 8), st, res, res_mode)
 
-    def _conv_bias_bwd(self, m, gp, x: Var, dy: Var, wt: torch.Tensor, st) -> None:
+    def _conv_bias_bwd(self, m, gp, x: Var, dy: Var, wt: torch.Tensor, st, bias: bool = True) -> None:
         """backward of out = conv(x, m.weight) + m.bias from dy = d out: the bias gradient (ydl_channel_sum), the weight gradient,
         and the input gradient added into d x"""
-        if m.bias is not None and m.bias.requires_grad:
+        if bias and m.bias is not None and m.bias.requires_grad:
             # a row block of a shared parameter reports it once, after its last writer
             self._channel_sum_grad(dy, m._grad_of(m.bias), m.bias if m.final else None, st)
         m.wgrad(self, gp, x, dy, st)
@@ -1691,12 +1865,13 @@ class Tape:
             gx, acc = self.grad_target(x)
             L.call("ydl_conv_dgrad", gp, self.dt, _p(dy.t), _p(wt), _p(gx), acc, st)
 
-    def conv_bias(self, x: Var, m, out: Optional[Var] = None) -> Var:
+    def conv_bias(self, x: Var, m, out: Optional[Var] = None, bias: bool = True) -> Var:
         """convolution + optional bias with no BatchNorm and no activation: ``nn.Conv2d`` (DCNv2's conv_offset_mask,
         models/common.py:1652-1659) and ``nn.Linear`` on the channel dimension of an NHWC tensor (modules/dcnv3.py:92-100), which is
         its 1x1 case.  ``m`` is a yolo_dual_amd.modules._GemmWeights holder: weight [out][taps][in] in KRSC order, ``bias`` [out] or
         None.  ``out`` may be an 8-aligned channel slice of a wider buffer (the Q | K | V blocks of Tape.mha).  Backward: bias
-        gradient by ydl_channel_sum, weight and input gradient by the conv kernels."""
+        gradient by ydl_channel_sum, weight and input gradient by the conv kernels.  ``bias`` False leaves ``m.bias`` and its gradient
+        to the consumer (``bias_gelu``)."""
         x = self._flat(x)
         Cout, _taps, Cin = m._gemm_dims()
         k, s, p = m.k, m.s, m.p
@@ -1711,7 +1886,7 @@ class Tape:
             raise RuntimeError("conv_bias: the output slice has the wrong shape or is not 16-byte aligned")
         geom = L.ConvGeom(x.N, x.H, x.W, Cin, Ho, Wo, Cout, k, s, p, x.ld, out.ld, 0)
         gp = ctypes.byref(geom)
-        self._conv_shift_fwd(gp, x, w, out, m.bias_coeffs if m.bias is not None else None, _stream())
+        self._conv_shift_fwd(gp, x, w, out, m.bias_coeffs if (bias and m.bias is not None) else None, _stream())
         if self.record:
             if x.need:
                 self._use(x)
@@ -1720,7 +1895,7 @@ class Tape:
                 # consumers may have written channel slices of this buffer's gradient only (DCNv2: the offset and mask slices)
                 if not (out.is_set() or any(c.gset for c in out.children)):
                     return
-                self._conv_bias_bwd(m, gp, x, Var(self, self._gbuf(out), out.ld, False), wt, _stream())
+                self._conv_bias_bwd(m, gp, x, Var(self, self._gbuf(out), out.ld, False), wt, _stream(), bias)
                 self._keep.append(geom)
             self.bw.append(bw)
         return out
