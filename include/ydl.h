@@ -799,6 +799,37 @@ int ydl_scale_res_bwd(int dtype, const void* dout, int lddo, const void* y, int 
                       void* dy, int lddy, void* dx, int lddx, int accumulate, float* dgamma, float* ws, int N, int64_t hw,
                       int C, void* stream);
 
+/* ---- squeeze-and-excitation gate (csrc/se.hip) ------------------------------------------------------------------------------
+ * SqueezeExcitation(C, Cs) per sample n:  p[c] = mean_hw x[n, :, c],  h = W1 p + b1,  a = act(h),  z = W2 a + b2,  g = scale(z),
+ * out = x * g[n, c].  x is NHWC with an element stride (it may be a channel slice of a wider buffer), f32 or bf16, 16-byte aligned,
+ * C a multiple of 8 in 8..2048, Cs in 1..512 (ydl_se_supported).  W1 [Cs][C], b1 [Cs], W2 [C][Cs], b2 [C] are the f32 masters as they
+ * stand: they are read by element and need no alignment.  act: YDL_ACT_RELU or YDL_ACT_SILU; the gate code selects scale.  f32
+ * arithmetic, no atomics, fixed summation order: two runs give the same bits.  Bad arguments are refused on the host before any launch.
+ *
+ * ydl_se_pool_fwd: ws[n][s][c] = the sum over slice s of sample n's pixels of x (y == NULL) or of x * y (the gate gradient
+ *   dgate = sum_hw dy * x); S = ydl_se_pool_splits(N, HW) slices of ceil(HW / S) pixels, ws of ydl_se_pool_ws_bytes (host functions).
+ * ydl_se_excite_fwd, one launch: folds the S partial rows in order, pooled = sum / HW, then h, z and gate; all four are written
+ *   (pooled, z, gate: f32 [N][C]; h: f32 [N][Cs]) -- the backward differentiates scale at the stored z and act at the stored h.
+ * ydl_se_excite_bwd, two launches: dgate is [N][S][C] partial rows (S = 1: the plain [N][C] gradient), folded in order;
+ *   dz = dgate * scale'(z) (sigmoid: e / (1 + e)^2 with e = exp(-|z|); hardsigmoid: 1/6 for -3 < z < 3, else 0),
+ *   dh = (W2^T dz) * act'(h), dpooled = W1^T dh [N][C]; then dW1[j][c] += sum_n dh[n][j] pooled[n][c], db1 += sum_n dh,
+ *   dW2[c][j] += sum_n dz[n][c] act(h[n][j]), db2 += sum_n dz, the samples in order.  A NULL gradient pointer is skipped (a frozen
+ *   parameter).  ws: ydl_se_excite_bwd_ws_bytes, holds dz [N][C] and dh [N][Cs].
+ * ydl_se_scale_bwd: dx (+)= dy * gate[n][c] + dpooled[n][c] / HW in one pass; accumulate != 0 adds in f32 with one rounding. */
+enum { YDL_SE_GATE_SIGMOID = 0, YDL_SE_GATE_HSIGMOID = 1 /* relu6(z + 3) / 6 */ };
+int ydl_se_supported(int C, int Cs);
+int ydl_se_pool_splits(int N, int64_t HW);
+int64_t ydl_se_pool_ws_bytes(int N, int64_t HW, int C);
+int ydl_se_pool_fwd(int dtype, const void* x, int ldx, const void* y, int ldy, float* ws, int N, int64_t HW, int C, void* stream);
+int ydl_se_excite_fwd(const float* part, int S, const float* w1, const float* b1, const float* w2, const float* b2, int act,
+                      int gate_kind, float* pooled, float* h, float* z, float* gate, int N, int64_t HW, int C, int Cs, void* stream);
+int64_t ydl_se_excite_bwd_ws_bytes(int N, int C, int Cs);
+int ydl_se_excite_bwd(const float* dgate, int S, const float* pooled, const float* h, const float* z, const float* w1,
+                      const float* w2, int act, int gate_kind, float* dpooled, float* dw1, float* db1, float* dw2, float* db2,
+                      float* ws, int N, int C, int Cs, void* stream);
+int ydl_se_scale_bwd(int dtype, const void* dy, int lddy, const float* gate, const float* dpooled, void* dx, int lddx,
+                     int accumulate, int N, int64_t HW, int C, void* stream);
+
 /* ---- activations with a run-time parameter ----------------------------------------------------------------------------
  * The six streaming BatchNorm entry points above, each with one more argument after `act`: act_param, the parameter of the
  * activation (the negative slope of YDL_ACT_LEAKY; ignored by every other code).  The entry points without it are these with

@@ -17,7 +17,9 @@ from .modules import (GAM, AttentionConv, AttentionStem, C2f, C3, C3k2, C3_DCNV3
                       C3Ghost, DWConv, GhostBottleneck, GhostConv, C3TR, TransformerBlock, TransformerLayer, ASPP, RFB, BasicConv,
                       SPP, C3SPP, SimConv, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF, CrossConv, C3x, ConvTranspose2d, DWConvTranspose2d,
                       Focus, Contract, Expand, BottleneckCSP, BatchNorm2d,
-                      LayerNorm2d, CNBlock, convnext_tiny1, convnext_tiny2, convnext_tiny3, convnext_key_map)
+                      LayerNorm2d, CNBlock, convnext_tiny1, convnext_tiny2, convnext_tiny3, convnext_key_map,
+                      SqueezeExcitation, Conv2dNormActivation, InvertedResidual, MBConv, MobileNetV3s1, MobileNetV3s2, MobileNetV3s3,
+                      efficientnet_b01, efficientnet_b02, efficientnet_b03, mobilenet_v3_small_key_map, efficientnet_b0_key_map)
 from .deform import deform_conv2d
 from . import activations
 from .activations import AconC, FReLU, Hardswish, MemoryEfficientMish, MetaAconC, Mish, SiLU

@@ -15,6 +15,7 @@ ACT_LEAKY, ACT_HSWISH, ACT_MISH = 3, 4, 5      # YDL_ACT_* of ydl.h; ACT_LEAKY c
 ACT_ACON, ACT_FRELU = 100, 101                 # host side only: the Conv runs ACT_NONE and the layer's own kernels follow (act.hip)
 RES_NONE, RES_AFTER_ACT, RES_BEFORE_ACT = 0, 1, 2
 RES_GRAD_ACCUMULATE = 16
+SE_GATE_SIGMOID, SE_GATE_HSIGMOID = 0, 1         # YDL_SE_GATE_* of ydl.h
 LOSS_DICE, LOSS_JACCARD = 0, 1
 AXIS_W, AXIS_H = 0, 1             # YDL_AXIS_* of ydl.h
 OPT_ADAM, OPT_ADAMW, OPT_RMSPROP = 1, 2, 3      # YDL_OPT_* of ydl.h
@@ -213,6 +214,14 @@ SIGNATURES = {
     "ydl_scale_res_fwd": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i64, _i, _vp]),
     "ydl_scale_res_bwd_ws_bytes": (_i64, [_i, _i64, _i]),
     "ydl_scale_res_bwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i64, _i, _vp]),
+    "ydl_se_supported": (_i, [_i, _i]),
+    "ydl_se_pool_splits": (_i, [_i, _i64]),
+    "ydl_se_pool_ws_bytes": (_i64, [_i, _i64, _i]),
+    "ydl_se_pool_fwd": (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp]),
+    "ydl_se_excite_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
+    "ydl_se_excite_bwd_ws_bytes": (_i64, [_i, _i, _i]),
+    "ydl_se_excite_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ydl_se_scale_bwd": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _vp]),
     "ydl_replay_create": (_vp, []),
     "ydl_replay_destroy": (None, [_vp]),
     "ydl_replay_fn_count": (_i, []),

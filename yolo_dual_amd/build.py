@@ -11,7 +11,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libydl_hip.so")
-SOURCES = ["err.cpp", "replay.cpp", "igemm.hip", "wgrad.hip", "gconv.hip", "xconv.hip", "bn.hip", "act.hip", "spatial.hip", "s2d.hip", "convnext.hip", "spp.hip", "loss.hip", "optim.hip", "dcnv3.hip", "dcn_blocks.hip", "dwconv.hip", "tconv.hip", "input.hip", "deform.hip", "dilconv.hip", "augment.hip", "local_attn.hip", "mha.hip", "predict.hip"]
+SOURCES = ["err.cpp", "replay.cpp", "igemm.hip", "wgrad.hip", "gconv.hip", "xconv.hip", "bn.hip", "act.hip", "spatial.hip", "s2d.hip", "convnext.hip", "se.hip", "spp.hip", "loss.hip", "optim.hip", "dcnv3.hip", "dcn_blocks.hip", "dwconv.hip", "tconv.hip", "input.hip", "deform.hip", "dilconv.hip", "augment.hip", "local_attn.hip", "mha.hip", "predict.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wno-unused-result",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]

@@ -163,6 +163,26 @@ static inline dim3 lay_grid(long long npix, int Cp, int V, int max_x) {
     return dim3((unsigned)gx, (unsigned)((cpp + 255) / 256));
 }
 
+// the CTA's partial row of the Lay kernels: fold the pixel lanes through LDS in lane order (acon_bwd_kernel's fold, one quantity), one
+// thread per (chunk, element) so that the serial part is the R pixel lanes only
+template <int V>
+__device__ __forceinline__ void lay_partial_row(const Lay& L, const float* s, float* __restrict__ dst /* row of this CTA, [C] */, int C) {
+    __shared__ float red[256 * 8];
+#pragma unroll
+    for (int e = 0; e < V; ++e) red[threadIdx.x * V + e] = s[e];
+    __syncthreads();
+    const int cpp = C / V;
+    for (int t = threadIdx.x; t < L.cpb * V; t += 256) {
+        const int fc = t / V, fe = t % V;
+        const int chunk = blockIdx.y * 256 + fc;
+        if (chunk < cpp) {
+            float a = 0.f;
+            for (int l = 0; l < L.R; ++l) a += red[(l * L.cpb + fc) * V + fe];
+            dst[chunk * V + fe] = a;
+        }
+    }
+}
+
 // Sum over the 64 lanes with DPP row shifts + row broadcasts (six v_add_f32_dpp, no LDS crossbar): the total is valid in LANE 63 ONLY.
 // The ds_bpermute butterfly of wave_sum below occupies the LDS for every step: the loss kernels reduce 39 values per wave with it and
 // spent half their time there (seg_loss_rep_fwd: 25 % LDS-active, 58 us; tools/sq_summary.py).

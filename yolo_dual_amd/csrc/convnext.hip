@@ -42,26 +42,6 @@ __global__ __launch_bounds__(256) void cn_fold_kernel(const float* __restrict__ 
     }
 }
 
-// the CTA's partial row of the Lay kernels: fold the pixel lanes through LDS in lane order (acon_bwd_kernel's fold, one quantity), one
-// thread per (chunk, element) so that the serial part is the R pixel lanes only
-template <int V>
-__device__ __forceinline__ void lay_partial_row(const Lay& L, const float* s, float* __restrict__ dst /* row of this CTA, [C] */, int C) {
-    __shared__ float red[256 * 8];
-#pragma unroll
-    for (int e = 0; e < V; ++e) red[threadIdx.x * V + e] = s[e];
-    __syncthreads();
-    const int cpp = C / V;
-    for (int t = threadIdx.x; t < L.cpb * V; t += 256) {
-        const int fc = t / V, fe = t % V;
-        const int chunk = blockIdx.y * 256 + fc;
-        if (chunk < cpp) {
-            float a = 0.f;
-            for (int l = 0; l < L.R; ++l) a += red[(l * L.cpb + fc) * V + fe];
-            dst[chunk * V + fe] = a;
-        }
-    }
-}
-
 static inline bool cn_rows_ok(int V, int C, int ld) { return ld >= C && ld % V == 0; }
 
 // ------------------------------------------------------------------------------------------------------

@@ -31,7 +31,8 @@ from .modules import (ASPP, RFB, GAM, AttentionConv, AttentionStem, BasicBlock, 
                       C3Common, C3Ghost, C3k2, C3TR, Concat, DWConv, GhostBottleneck, GhostConv, TransformerBlock,
                       Conv, MaxPool2d, SegmentHead, SPPF, Upsample, YdlModule, run_region,
                       SPP, C3SPP, SimSPPF, SPPCSPC, SPPCSPC_group, SimCSPSPPF, CrossConv, C3x, ConvTranspose2d, DWConvTranspose2d,
-                      Focus, Contract, Expand, BottleneckCSP, BatchNorm2d, convnext_tiny1, convnext_tiny2, convnext_tiny3)
+                      Focus, Contract, Expand, BottleneckCSP, BatchNorm2d, convnext_tiny1, convnext_tiny2, convnext_tiny3,
+                      MobileNetV3s1, MobileNetV3s2, MobileNetV3s3, efficientnet_b01, efficientnet_b02, efficientnet_b03)
 from .tape import Tape, Var
 
 LOGGER = logging.getLogger("yolo_dual_amd")
@@ -546,7 +547,31 @@ _PARSE_TABLE = {"Conv": Conv, "Bottleneck": Bottleneck, "C3": C3Common, "SPPF": 
                 "SPPCSPC_group": SPPCSPC_group, "SimCSPSPPF": SimCSPSPPF, "CrossConv": CrossConv, "C3x": C3x,
                 "nn.ConvTranspose2d": ConvTranspose2d, "DWConvTranspose2d": DWConvTranspose2d, "Focus": Focus,
                 "BottleneckCSP": BottleneckCSP, "Contract": Contract, "Expand": Expand, "nn.BatchNorm2d": BatchNorm2d,
-                "convnext_tiny1": convnext_tiny1, "convnext_tiny2": convnext_tiny2, "convnext_tiny3": convnext_tiny3}
+                "convnext_tiny1": convnext_tiny1, "convnext_tiny2": convnext_tiny2, "convnext_tiny3": convnext_tiny3,
+                "MobileNetV3s1": MobileNetV3s1, "MobileNetV3s2": MobileNetV3s2, "MobileNetV3s3": MobileNetV3s3,
+                "efficientnet_b01": efficientnet_b01, "efficientnet_b02": efficientnet_b02, "efficientnet_b03": efficientnet_b03}
+_BACKBONE_ROWS = (convnext_tiny1, convnext_tiny2, convnext_tiny3, MobileNetV3s1, MobileNetV3s2, MobileNetV3s3,
+                  efficientnet_b01, efficientnet_b02, efficientnet_b03)
+
+# the torchvision backbone wrappers of models/common.py:940-1238 that are not built, by family: why
+_REFUSED_FAMILIES = {
+    "efficientnet_b1": "only EfficientNet-B0's table is built (efficientnet_b01 / 2 / 3)",
+    "efficientnet_v2_s": "its FusedMBConv stages are not built",
+    "RegNety400": "its grouped 3x3 convolutions have group width 8, outside the grouped-convolution served set (16 channels per group)",
+    "mobilenet_v2": "its ReLU6 activation is not among the BatchNorm kernels' activation codes",
+    "resnet18": "the torchvision ResNet wrappers are not built (ResNet18Seg / ResNet50SegYaml are this project's ResNet models)",
+    "resnet34": "the torchvision ResNet wrappers are not built (ResNet18Seg / ResNet50SegYaml are this project's ResNet models)",
+    "resnet50": "the torchvision ResNet wrappers are not built (ResNet18Seg / ResNet50SegYaml are this project's ResNet models)",
+    "wide_resnet50_2": "the torchvision ResNet wrappers are not built (ResNet18Seg / ResNet50SegYaml are this project's ResNet models)",
+    "vgg11_bn": "the VGG wrappers (a convolution with bias in front of BatchNorm, max-pools between) are not built",
+}
+
+
+def _refused_row(name: str):
+    """the reason a backbone-wrapper row ``<family>1`` / ``2`` / ``3`` is refused, or None"""
+    if isinstance(name, str) and name[-1:] in ("1", "2", "3"):
+        return _REFUSED_FAMILIES.get(name[:-1])
+    return None
 
 
 # the activations a yaml can name: ``nn.Name(...)`` is torch's class, a bare ``Name(...)`` the class of yolo_dual_amd.activations where
@@ -631,6 +656,9 @@ def _parse_model(d: dict, ch: List[int], deformable: bool = False):
     table = dict(_PARSE_TABLE, C3_DCN=C3_DCNCommon) if deformable else _PARSE_TABLE
     for i, (f, n, m, args) in enumerate(d["backbone"] + d["head"]):
         if m not in table:
+            why = _refused_row(m)
+            if why is not None:
+                raise NotImplementedError(f"parse_model: the backbone row {m} is not served: {why}")
             raise NotImplementedError(f"parse_model: module {m} is outside the segmentation hot path")
         cls = table[m]
         args = [None if a == "None" else a for a in args]
@@ -649,7 +677,7 @@ def _parse_model(d: dict, ch: List[int], deformable: bool = False):
         elif cls is BatchNorm2d:                         # models/yolo.py:330-331
             args = [ch[f]]
             c2 = ch[f]
-        elif cls in (convnext_tiny1, convnext_tiny2, convnext_tiny3):      # models/yolo.py:367-368: c2 as written, no width gain
+        elif cls in _BACKBONE_ROWS:                      # models/yolo.py:345-348,367-368: c2 as written, no width gain
             c2 = args[0]
         elif cls is Contract:                            # models/yolo.py:341-342
             c2 = ch[f] * args[0] ** 2

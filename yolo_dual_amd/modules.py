@@ -2579,7 +2579,7 @@ class CNBlock(YdlModule):
         if not self.training or p == 0.0:
             return None
         if L.recorder() is not None:
-            raise NotImplementedError("stochastic depth (CNBlock with stochastic_depth_prob > 0 in training) draws its keep factors with "
+            raise NotImplementedError(f"stochastic depth ({type(self).__name__} with stochastic_depth_prob > 0 in training) draws its keep factors with "
                                       "torch before the launch: a recorded step cannot replay it; build the rows with stochastic_depth_prob=0")
         keep = torch.empty(N, dtype=torch.float32, device=device).bernoulli_(1.0 - p, generator=self.generator)
         return keep.div_(1.0 - p)
@@ -2602,9 +2602,10 @@ class CNBlock(YdlModule):
 def refuse_stochastic_depth(model: nn.Module, who: str) -> None:
     """the recorded-step paths re-issue one step's launches: the keep factors of stochastic depth are drawn by torch before the launch,
     every step anew, which a recording cannot repeat"""
-    bad = [n for n, m in model.named_modules() if isinstance(m, CNBlock) and m.training and m.stochastic_depth_prob > 0.0]
+    bad = [n for n, m in model.named_modules() if isinstance(m, (CNBlock, MBConv)) and m.training and m.stochastic_depth_prob > 0.0
+           and getattr(m, "use_res_connect", True)]
     if bad:
-        raise NotImplementedError(f"{who} cannot re-draw the keep factors of stochastic depth: {len(bad)} CNBlock(s) in training mode have "
+        raise NotImplementedError(f"{who} cannot re-draw the keep factors of stochastic depth: {len(bad)} CNBlock / MBConv block(s) in training mode have "
                                   f"stochastic_depth_prob > 0 (first: {bad[0]}); build the rows with stochastic_depth_prob=0")
 
 
@@ -2685,3 +2686,306 @@ def convnext_key_map(keys=None) -> dict:
 
 
 __all__ += ["LayerNorm2d", "CNBlock", "convnext_tiny1", "convnext_tiny2", "convnext_tiny3", "convnext_key_map"]
+
+
+# ----------------------------------------------------------------------------------------------------------
+# Squeeze-excitation blocks: the MobileNetV3-small and EfficientNet-B0 backbone rows (models/common.py:870-936: slices of torchvision's
+# ``mobilenet_v3_small().features`` and ``efficientnet_b0().features``).  torchvision is not a dependency: its definitions are restated
+# here with its state_dict keys, so a user's own state_dict loads.  Nothing is downloaded: the reference's ``pretrained=True`` is not
+# reproduced, the initialisation is the builder's (torchvision's rule: kaiming fan-out, zero biases, BatchNorm 1 / 0).
+# ----------------------------------------------------------------------------------------------------------
+_SE_ACTS = {"relu": (nn.ReLU, L.ACT_RELU), "silu": (nn.SiLU, L.ACT_SILU)}
+_SE_GATES = {"sigmoid": (nn.Sigmoid, L.SE_GATE_SIGMOID), "hardsigmoid": (nn.Hardsigmoid, L.SE_GATE_HSIGMOID)}
+
+
+def _se_choice(what: str, v, table: dict):
+    """``v``: a name of ``table``, the torch class it stands for, or an instance of that class -> (module, code)"""
+    for name, (cls, code) in table.items():
+        if v is cls or isinstance(v, cls) or (isinstance(v, str) and v.lower() == name):
+            return cls(), code
+    raise NotImplementedError(f"SqueezeExcitation: {what}={v!r} is not served (one of {', '.join(sorted(table))})")
+
+
+class _SEConv2d(nn.Conv2d):
+    """fc1 / fc2 of a SqueezeExcitation: a 1x1 ``nn.Conv2d`` with bias; the kernels read its f32 parameters as they stand"""
+    _keep_init = True
+
+    def __init__(self, c1, c2):
+        super().__init__(c1, c2, 1)
+        nn.init.kaiming_normal_(self.weight, mode="fan_out")
+        nn.init.zeros_(self.bias)
+
+    def forward(self, x):  # pragma: no cover - run through SqueezeExcitation
+        raise RuntimeError("run through SqueezeExcitation")
+
+
+class SqueezeExcitation(YdlModule):
+    """torchvision's SqueezeExcitation: ``x * scale_activation(fc2(activation(fc1(avgpool(x)))))``.  state_dict: fc1.weight
+    [squeeze, input, 1, 1], fc1.bias, fc2.weight [input, squeeze, 1, 1], fc2.bias.  ``activation``: "relu" or "silu" (or nn.ReLU /
+    nn.SiLU), ``scale_activation``: "sigmoid" or "hardsigmoid" (or the torch classes).  Runs on the kernels of csrc/se.hip
+    (Tape.squeeze_excite): input_channels a multiple of 8 in 8..2048, squeeze_channels in 1..512."""
+
+    def __init__(self, input_channels, squeeze_channels, activation="relu", scale_activation="sigmoid"):
+        super().__init__()
+        C, Cs = input_channels, squeeze_channels
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in (C, Cs)) or C < 8 or C > 2048 or C % 8 or not 1 <= Cs <= 512:
+            raise ValueError(f"SqueezeExcitation: input_channels={C!r} must be a multiple of 8 in 8..2048 and squeeze_channels={Cs!r} in 1..512")
+        self.avgpool = nn.AdaptiveAvgPool2d(1)
+        self.fc1 = _SEConv2d(C, Cs)
+        self.fc2 = _SEConv2d(Cs, C)
+        self.activation, self.act_code = _se_choice("activation", activation, _SE_ACTS)
+        self.scale_activation, self.gate_code = _se_choice("scale_activation", scale_activation, _SE_GATES)
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        return tape.squeeze_excite(x, self)
+
+
+_CNA_ACTS = {"relu": nn.ReLU, "re": nn.ReLU, "hardswish": nn.Hardswish, "hs": nn.Hardswish, "silu": nn.SiLU}
+
+
+class Conv2dNormActivation(Conv):
+    """torchvision's Conv2dNormActivation: Conv2d without bias, BatchNorm2d, activation, padding (k - 1) / 2.  A ``Conv`` whose
+    convolution and BatchNorm sit under torchvision's names: state_dict ``0.weight`` and ``1.{weight, bias, running_mean, running_var,
+    num_batches_tracked}`` (the activation, ``2``, holds no state).  ``conv`` / ``bn`` / ``act`` stay readable, so the tape, ``fuse()``,
+    the optimizer arenas and the checkpoint code see an ordinary Conv.  ``activation``: "relu", "hardswish", "silu" (or "RE" / "HS", or
+    the torch class or an instance), or None for none.  groups: 1, or in_channels == out_channels (depth-wise, k in {1, 3, 5, 7})."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, groups=1, activation="relu", eps=1e-5, momentum=0.1):
+        act = activation
+        if isinstance(act, str):
+            if act.lower() not in _CNA_ACTS:
+                raise NotImplementedError(f"Conv2dNormActivation: activation={activation!r} is not served (one of relu, hardswish, silu, None)")
+            act = _CNA_ACTS[act.lower()]()
+        elif isinstance(act, type):
+            act = act()
+        super().__init__(in_channels, out_channels, kernel_size, stride, None, groups, 1, act if act is not None else False)
+        mods = self._modules
+        conv, bn, a = mods.pop("conv"), mods.pop("bn"), mods.pop("act")
+        mods["0"], mods["1"], mods["2"] = conv, bn, a
+        conv._keep_init = True
+        nn.init.kaiming_normal_(conv.weight, mode="fan_out")
+        bn.eps, bn.momentum = float(eps), float(momentum)
+
+    def _named(self, new: str, old: str):
+        mods = self._modules
+        return mods[new] if new in mods else mods[old]
+
+    conv = property(lambda self: self._named("0", "conv"))
+    bn = property(lambda self: self._named("1", "bn"))
+    act = property(lambda self: self._named("2", "act"))
+
+
+def _make_divisible_tv(v: float, divisor: int = 8) -> int:
+    """torchvision's ``_make_divisible``: the nearest multiple, never below 90 % of ``v``"""
+    new_v = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    return new_v + divisor if new_v < 0.9 * v else new_v
+
+
+def _block_ints(who: str, **kw) -> None:
+    for k, v in kw.items():
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{who}: {k}={v!r} must be a positive int")
+
+
+class InvertedResidual(YdlModule):
+    """torchvision's MobileNetV3 ``InvertedResidual``: ``block`` = [expand 1x1 Conv+BN+act if expanded != in], depth-wise k x k stride s
+    Conv+BN+act, [SqueezeExcitation(expanded, make_divisible(expanded // 4, 8), ReLU, Hardsigmoid)], project 1x1 Conv+BN; the residual
+    ``x + block(x)`` where s == 1 and in == out (joined in the projection's BatchNorm apply).  ``activation``: "RE" (ReLU) or "HS"
+    (Hardswish).  BatchNorm eps 1e-3, momentum 0.01, as ``mobilenet_v3_small`` builds it."""
+
+    def __init__(self, in_channels, kernel, expanded_channels, out_channels, use_se, activation, stride):
+        super().__init__()
+        who = "InvertedResidual"
+        _block_ints(who, in_channels=in_channels, kernel=kernel, expanded_channels=expanded_channels, out_channels=out_channels, stride=stride)
+        if stride not in (1, 2) or kernel not in (1, 3, 5, 7) or str(activation).upper() not in ("RE", "HS"):
+            raise NotImplementedError(f"{who}: stride={stride} in {{1, 2}}, kernel={kernel} in {{1, 3, 5, 7}}, activation={activation!r} 'RE' or 'HS'")
+        bn = dict(eps=1e-3, momentum=0.01)
+        act = str(activation).upper()
+        layers = []
+        if expanded_channels != in_channels:
+            layers.append(Conv2dNormActivation(in_channels, expanded_channels, 1, activation=act, **bn))
+        layers.append(Conv2dNormActivation(expanded_channels, expanded_channels, kernel, stride, expanded_channels, activation=act, **bn))
+        if use_se:
+            layers.append(SqueezeExcitation(expanded_channels, _make_divisible_tv(expanded_channels // 4, 8), "relu", "hardsigmoid"))
+        layers.append(Conv2dNormActivation(expanded_channels, out_channels, 1, activation=None, **bn))
+        self.block = nn.Sequential(*layers)
+        self.use_res_connect = stride == 1 and in_channels == out_channels
+        self.out_channels = out_channels
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        x = tape.materialize(x)
+        h = x
+        for sub in self.block[:-1]:
+            h = sub._fwd(tape, h)
+        if self.use_res_connect:
+            return self.block[-1]._fwd(tape, h, res=x, res_mode=L.RES_AFTER_ACT)
+        return self.block[-1]._fwd(tape, h)
+
+
+class MBConv(YdlModule):
+    """torchvision's EfficientNet ``MBConv``: ``block`` = [expand 1x1 Conv+BN+SiLU if expand_ratio != 1], depth-wise k x k stride s
+    Conv+BN+SiLU, SqueezeExcitation(expanded, max(1, in // 4), SiLU, Sigmoid), project 1x1 Conv+BN; where s == 1 and in == out the
+    residual ``x + stochastic_depth(block(x))``, "row" mode.  Without keep factors (eval, p = 0) the projection's BatchNorm apply joins
+    the residual; with them the keep-factor kernel of the ConvNeXt blocks does (a sample with keep 0 leaves as it came, bit for bit)."""
+
+    def __init__(self, expand_ratio, kernel, stride, in_channels, out_channels, stochastic_depth_prob=0.0):
+        super().__init__()
+        who = "MBConv"
+        _block_ints(who, expand_ratio=expand_ratio, kernel=kernel, stride=stride, in_channels=in_channels, out_channels=out_channels)
+        if stride not in (1, 2) or kernel not in (1, 3, 5, 7):
+            raise NotImplementedError(f"{who}: stride={stride} in {{1, 2}}, kernel={kernel} in {{1, 3, 5, 7}}")
+        p = float(stochastic_depth_prob)
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"{who}: stochastic_depth_prob={stochastic_depth_prob!r} must be in [0, 1)")
+        exp = in_channels * expand_ratio
+        layers = []
+        if exp != in_channels:
+            layers.append(Conv2dNormActivation(in_channels, exp, 1, activation="silu"))
+        layers.append(Conv2dNormActivation(exp, exp, kernel, stride, exp, activation="silu"))
+        layers.append(SqueezeExcitation(exp, max(1, in_channels // 4), "silu", "sigmoid"))
+        layers.append(Conv2dNormActivation(exp, out_channels, 1, activation=None))
+        self.block = nn.Sequential(*layers)
+        self.use_res_connect = stride == 1 and in_channels == out_channels
+        self.out_channels = out_channels
+        self.stochastic_depth_prob = p
+        self.generator = None             # torch.Generator of the keep draws, or None for the device's default generator
+
+    draw_keep = CNBlock.draw_keep
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        x = tape.materialize(x)
+        keep = self.draw_keep(x.N, tape.device) if self.use_res_connect else None
+        h = x
+        for sub in self.block[:-1]:
+            h = sub._fwd(tape, h)
+        if not self.use_res_connect:
+            return self.block[-1]._fwd(tape, h)
+        if keep is None:
+            return self.block[-1]._fwd(tape, h, res=x, res_mode=L.RES_AFTER_ACT)
+        ones = self.__dict__.get("_ones")
+        if ones is None or ones.device != x.t.device:      # the constant gamma row of the keep-factor kernel, made once
+            ones = self.__dict__["_ones"] = torch.ones(self.out_channels, dtype=torch.float32, device=x.t.device)
+        return tape.scale_residual(self.block[-1]._fwd(tape, h), None, keep, x, gamma=ones)
+
+    def extra_repr(self):
+        return f"stochastic_depth_prob={self.stochastic_depth_prob:.4g}"
+
+
+# mobilenet_v3_small: features[1..11] as (in, kernel, expanded, out, SE, activation, stride)
+_MNV3S = ((16, 3, 16, 16, True, "RE", 2), (16, 3, 72, 24, False, "RE", 2), (24, 3, 88, 24, False, "RE", 1), (24, 5, 96, 40, True, "HS", 2),
+          (40, 5, 240, 40, True, "HS", 1), (40, 5, 240, 40, True, "HS", 1), (40, 5, 120, 48, True, "HS", 1), (48, 5, 144, 48, True, "HS", 1),
+          (48, 5, 288, 96, True, "HS", 2), (96, 5, 576, 96, True, "HS", 1), (96, 5, 576, 96, True, "HS", 1))
+# efficientnet_b0: stages features[1..7] as (expand ratio, kernel, stride of the first block, in, out, repeats)
+_EFFB0 = ((1, 3, 1, 32, 16, 1), (6, 3, 2, 16, 24, 2), (6, 5, 2, 24, 40, 2), (6, 3, 2, 40, 80, 3), (6, 5, 1, 80, 112, 3),
+          (6, 5, 2, 112, 192, 4), (6, 3, 1, 192, 320, 1))
+
+
+def _mnv3s_feature(i: int) -> nn.Module:
+    bn = dict(eps=1e-3, momentum=0.01)
+    if i == 0:
+        return Conv2dNormActivation(3, 16, 3, 2, activation="hardswish", **bn)
+    if i == 12:
+        return Conv2dNormActivation(96, 576, 1, activation="hardswish", **bn)
+    return InvertedResidual(*_MNV3S[i - 1])
+
+
+def _effb0_feature(i: int, sd: float) -> nn.Module:
+    """block j of the 16 (counted over the whole network) gets p = sd * j / 16"""
+    if i == 0:
+        return Conv2dNormActivation(3, 32, 3, 2, activation="silu")
+    if i == 8:
+        return Conv2dNormActivation(320, 1280, 1, activation="silu")
+    ratio, k, s, cin, cout, reps = _EFFB0[i - 1]
+    first, total = sum(st[5] for st in _EFFB0[:i - 1]), sum(st[5] for st in _EFFB0)
+    return nn.Sequential(*(MBConv(ratio, k, s if j == 0 else 1, cin if j == 0 else cout, cout, sd * (first + j) / total) for j in range(reps)))
+
+
+class _SERow(YdlModule):
+    """one backbone row: ``self.model`` is the slice ``features[_first:_last]`` the reference keeps, so the keys are ``model.<j>. ...``;
+    the row's positional argument (the yaml's channel count) is ignored, as in the reference"""
+    _first, _last = 0, 0
+    _stride = 2         # the row's total down-sampling
+
+    def _fwd(self, tape: Tape, x: Var) -> Var:
+        if x.LH % self._stride or x.LW % self._stride:
+            raise ValueError(f"{type(self).__name__}: the {x.LH} x {x.LW} map is not a multiple of {self._stride}, the row's stride")
+        for part in self.model:
+            for sub in (part if isinstance(part, nn.Sequential) else (part,)):
+                x = sub._fwd(tape, x)
+        return x
+
+
+class _MobileNetV3sRow(_SERow):
+    def __init__(self, ignore=None):
+        super().__init__()
+        self.model = nn.Sequential(*(_mnv3s_feature(i) for i in range(self._first, self._last)))
+
+
+class MobileNetV3s1(_MobileNetV3sRow):
+    """models/common.py:870-880: features[:4] of mobilenet_v3_small, 3 -> 24 channels at 1/8 of the input size"""
+    _first, _last, _stride = 0, 4, 8
+
+
+class MobileNetV3s2(_MobileNetV3sRow):
+    """models/common.py:882-892: features[4:9], 24 -> 48 channels, 1/16"""
+    _first, _last = 4, 9
+
+
+class MobileNetV3s3(_MobileNetV3sRow):
+    """models/common.py:894-903: features[9:], 48 -> 576 channels, 1/32"""
+    _first, _last = 9, 13
+
+
+class _EfficientNetB0Row(_SERow):
+    def __init__(self, ignore=None, *, stochastic_depth_prob=0.2):
+        super().__init__()
+        sd = float(stochastic_depth_prob)
+        if not 0.0 <= sd < 1.0:
+            raise ValueError(f"{type(self).__name__}: stochastic_depth_prob={stochastic_depth_prob!r} must be in [0, 1)")
+        self.model = nn.Sequential(*(_effb0_feature(i, sd) for i in range(self._first, self._last)))
+
+
+class efficientnet_b01(_EfficientNetB0Row):
+    """models/common.py:908-916: features[:4] of efficientnet_b0, 3 -> 40 channels at 1/8 of the input size"""
+    _first, _last, _stride = 0, 4, 8
+
+
+class efficientnet_b02(_EfficientNetB0Row):
+    """models/common.py:918-926: features[4:6], 40 -> 112 channels, 1/16"""
+    _first, _last = 4, 6
+
+
+class efficientnet_b03(_EfficientNetB0Row):
+    """models/common.py:928-936: features[6:], 112 -> 1280 channels, 1/32"""
+    _first, _last = 6, 9
+
+
+def _features_key_map(rows, keys) -> dict:
+    """torchvision ``features.N.rest`` -> (row index, ``model.M.rest``) with M = N minus the row's first feature"""
+    if keys is None:
+        keys = [f"features.{r._first + int(k.split('.')[1])}.{k.split('.', 2)[2]}" for r in rows for k in r().state_dict()]
+    out = {}
+    for k in keys:
+        parts = k.split(".", 2)
+        if len(parts) != 3 or parts[0] != "features" or not parts[1].isdigit():
+            continue
+        n = int(parts[1])
+        for i, r in enumerate(rows):
+            if r._first <= n < r._last:
+                out[k] = (i, f"model.{n - r._first}.{parts[2]}")
+    return out
+
+
+def mobilenet_v3_small_key_map(keys=None) -> dict:
+    """torchvision ``mobilenet_v3_small`` state_dict key -> (row index 0..2, key inside that row) for MobileNetV3s1 / 2 / 3.  ``keys``:
+    the keys to map (the classifier's are left out); default: every key of the three rows.  Nothing is downloaded."""
+    return _features_key_map((MobileNetV3s1, MobileNetV3s2, MobileNetV3s3), keys)
+
+
+def efficientnet_b0_key_map(keys=None) -> dict:
+    """torchvision ``efficientnet_b0`` state_dict key -> (row index 0..2, key inside that row) for efficientnet_b01 / 2 / 3"""
+    return _features_key_map((efficientnet_b01, efficientnet_b02, efficientnet_b03), keys)
+
+
+__all__ += ["SqueezeExcitation", "Conv2dNormActivation", "InvertedResidual", "MBConv", "MobileNetV3s1", "MobileNetV3s2", "MobileNetV3s3",
+            "efficientnet_b01", "efficientnet_b02", "efficientnet_b03", "mobilenet_v3_small_key_map", "efficientnet_b0_key_map"]

@@ -1405,12 +1405,13 @@ class Tape:
         self.bw.append(bw)
         return out
 
-    def scale_residual(self, y: Var, m, keep: Optional[torch.Tensor], x: Var) -> Var:
+    def scale_residual(self, y: Var, m, keep: Optional[torch.Tensor], x: Var, gamma: Optional[torch.Tensor] = None) -> Var:
         """out = x + keep[n] * m.layer_scale[c] * y: the layer-scaled residual of a ConvNeXt block with the per-sample keep factors of
         stochastic depth (``keep``: f32 [N] on the device, or None for 1).  Backward: d/dy, the layer-scale gradient, and d/dx = d/dout,
-        which x adopts without a pass where it can (``_alias_grad``)."""
+        which x adopts without a pass where it can (``_alias_grad``).  ``gamma``: a constant f32 [C] row in place of ``m.layer_scale``
+        (MBConv: ones; ``m`` is not read then and the row's gradient goes to a scratch row)."""
         y, x = self._flat(y), self._flat(x)
-        C, hw, g = y.C, y.H * y.W, m.layer_scale
+        C, hw, g = y.C, y.H * y.W, m.layer_scale if gamma is None else gamma
         if (x.N, x.C, x.H, x.W) != (y.N, C, y.H, y.W):
             raise RuntimeError("scale_residual: the branch and the residual differ in shape")
         if g.numel() != C or not g.is_contiguous() or g.dtype != torch.float32:
@@ -1440,13 +1441,68 @@ class Tape:
             gx, accx = None, 0
             if x.need and not self._alias_grad(x, out, dout):
                 gx, accx = self.grad_target(x)
+            dg = self._param_grad(g, self.device) if gamma is None else torch.empty(C, dtype=torch.float32, device=self.device)
             L.call("ydl_scale_res_bwd", self.dt, _p(dout), out.ld, _p(y.t), y.ld, _p(g), _p(keep), _p(gy_), ldy, _p(gx), x.ld, accx,
-                   _p(self._param_grad(g, self.device)), _p(ws), y.N, hw, C, st)
+                   _p(dg), _p(ws), y.N, hw, C, st)
             if accy:
                 L.call("ydl_copy2d", y.dt, _p(gy_), ldy, _p(gy), y.ld, y.npix, C, 1, st)
             if keep is not None:
                 self._keep.append(keep)
-            self._touch(g)
+            if gamma is None:
+                self._touch(g)
+        self.bw.append(bw)
+        return out
+
+    # ------------------------------------------------------------------ squeeze-and-excitation (csrc/se.hip)
+    def squeeze_excite(self, x: Var, m) -> Var:
+        """out = x * scale(fc2(act(fc1(mean_hw x))))[n, c], torchvision's SqueezeExcitation: ``m.fc1`` / ``m.fc2`` are the 1x1
+        ``nn.Conv2d(C, Cs)`` / ``(Cs, C)`` with bias whose f32 parameters the kernels read as they stand, ``m.act_code`` is ACT_RELU or
+        ACT_SILU and ``m.gate_code`` SE_GATE_SIGMOID or SE_GATE_HSIGMOID.  Forward: ydl_se_pool_fwd (partial sums), ydl_se_excite_fwd
+        (one launch from the partial rows to the gate; pooled, h and z are kept), ydl_scale_channels.  Backward: the gate gradient
+        sum_hw dout * x through ydl_se_pool_fwd's product form, ydl_se_excite_bwd (dpooled and the four parameter gradients), and
+        ydl_se_scale_bwd: dx (+)= dout * gate + dpooled / HW, two reads and one write of the tensor."""
+        x = self._flat(x)
+        N, C, HW = x.N, x.C, x.H * x.W
+        fc1, fc2 = m.fc1, m.fc2
+        Cs = fc1.out_channels
+        lib = L.lib()
+        if not lib.ydl_se_supported(C, Cs):
+            raise RuntimeError(f"squeeze_excite: C={C}, Cs={Cs} are outside the served set (C a multiple of 8 in 8..2048, Cs in 1..512)")
+        ps = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+        if (fc1.in_channels, fc2.in_channels, fc2.out_channels) != (C, Cs, C) or any(
+                p is None or p.dtype != torch.float32 or not p.is_contiguous() for p in ps):
+            raise RuntimeError(f"squeeze_excite: fc1 / fc2 must be 1x1 convolutions {C} -> {Cs} -> {C} with contiguous f32 weights and biases")
+        f32 = dict(dtype=torch.float32, device=self.device)
+        S = lib.ydl_se_pool_splits(N, HW)
+        part = torch.empty(lib.ydl_se_pool_ws_bytes(N, HW, C) // 4, **f32)
+        pooled, z, gate = torch.empty((3, N, C), **f32).unbind(0)
+        h = torch.empty((N, Cs), **f32)
+        st = _stream()
+        L.call("ydl_se_pool_fwd", self.dt, _p(x.t), x.ld, None, 0, _p(part), N, HW, C, st)
+        L.call("ydl_se_excite_fwd", _p(part), S, _p(ps[0]), _p(ps[1]), _p(ps[2]), _p(ps[3]), m.act_code, m.gate_code, _p(pooled), _p(h),
+               _p(z), _p(gate), N, HW, C, Cs, st)
+        out = self.scale_channels(x, gate)
+        if not self.record:
+            return out
+        if x.need:
+            self._use(x)
+
+        def bw():
+            if not out.is_set() or not (x.need or any(p.requires_grad for p in ps)):
+                return
+            st2 = _stream()
+            dout = self._gbuf(out)
+            dgate = torch.empty(N * S * C, **f32)
+            L.call("ydl_se_pool_fwd", self.dt, _p(dout), out.ld, _p(x.t), x.ld, _p(dgate), N, HW, C, st2)
+            grads = [self._param_grad(p, self.device) if p.requires_grad else None for p in ps]
+            dpooled = torch.empty((N, C), **f32)
+            ws = torch.empty(lib.ydl_se_excite_bwd_ws_bytes(N, C, Cs) // 4, **f32)
+            L.call("ydl_se_excite_bwd", _p(dgate), S, _p(pooled), _p(h), _p(z), _p(ps[0]), _p(ps[2]), m.act_code, m.gate_code, _p(dpooled),
+                   _p(grads[0]), _p(grads[1]), _p(grads[2]), _p(grads[3]), _p(ws), N, C, Cs, st2)
+            self._touch(*ps)
+            if x.need:
+                gx, acc = self.grad_target(x)
+                L.call("ydl_se_scale_bwd", self.dt, _p(dout), out.ld, _p(gate), _p(dpooled), _p(gx), x.ld, acc, N, HW, C, st2)
         self.bw.append(bw)
         return out
 
