@@ -6,6 +6,9 @@ import pytest
 import yaml
 
 CFG = os.path.join(os.path.dirname(__file__), "..", "yolo_dual_amd", "cfg")
+# 3 x 32 x 32 -> 32 ch @ 16^2 -> C3_DCN with two DCNv2 bottlenecks (64 ch) -> 12 classes
+YAML = {"nc": 12, "depth_multiple": 1.0, "width_multiple": 1.0,
+        "backbone": [[-1, 1, "Conv", [32, 3, 2]], [-1, 2, "C3_DCN", [64]]], "head": [[-1, 1, "Conv", [12, 1, 1]]]}
 
 
 def _cfg(name):
@@ -67,8 +70,7 @@ def test_parse_model_resolves_c3_dcn_to_the_common_dcnv2_block():
     """models/yolo.py:321,327: C3_DCN gets (c1, c2) and n inserted; models/common.py:1629-1711: DCNv2 with a zero-initialised
     biased conv_offset_mask (27 = 3 * 3 * 3 channels) and a zero bias"""
     import yolo_dual_amd as ydl
-    d = {"nc": 12, "depth_multiple": 1.0, "width_multiple": 1.0,
-         "backbone": [[-1, 1, "Conv", [32, 3, 2]], [-1, 2, "C3_DCN", [64]]], "head": [[-1, 1, "Conv", [12, 1, 1]]]}
+    d = YAML
     with pytest.raises(NotImplementedError, match="outside the segmentation hot path"):
         ydl.parse_model(d, [3])
     seq, _ = ydl.parse_model(d, [3], deformable=True)

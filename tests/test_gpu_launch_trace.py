@@ -20,7 +20,30 @@ pytestmark = pytest.mark.gpu
 FIXTURE = os.path.join(os.path.dirname(__file__), "golden", "launch_trace.json.gz")
 # the yaml models of tests/test_builders_<name>_cpu.py and the side of their output for a 32 x 32 input
 YAMLS = {"ghost": 4, "gconv": 8, "cross": 8, "act": 8, "up": 32, "dilated": 8, "spp": 8}
-MODELS = {"YOLOv5Seg": "cfg2", "YOLOv8Seg": "cfg4", "YOLOv9Seg": "cfg5", "ResNet50Seg": "cfg3"}      # -> bench.WORKLOADS
+# further yaml models: case name -> (builder test, its variable, side of the output for a 32 x 32 input).  "dcn" is built with
+# deformable=True; "acon" is the act yaml under nn.Mish() with an AconC and an FReLU Conv swapped in (tests/test_gpu_act_blocks.py)
+VARIANTS = {"convnext": ("convnext", "YAML", 2), "attention": ("attention", "YAML", 16), "transformer": ("transformer", "YAML", 16),
+            "sd": ("sd", "YAML", 32), "mnv3": ("se", "YAML_MNV3", 2), "effb0": ("se", "YAML_EFF", 2), "dcn": ("dcn", "YAML", 16),
+            "acon": ("act", "YAML", 8)}
+# case name -> bench.WORKLOADS
+MODELS = {"YOLOv5Seg": "cfg2", "YOLOv8Seg": "cfg4", "YOLOv9Seg": "cfg5", "ResNet50Seg": "cfg3", "YOLOv9SegDCNv3": "cfg5dcn"}
+
+
+def _yaml_model(name):
+    """the yaml model of a case name, on the CPU"""
+    import yolo_dual_amd as ydl
+    mod, var, _side = VARIANTS.get(name, (name, "YAML", None))
+    yaml = getattr(importlib.import_module(f"tests.test_builders_{mod}_cpu"), var)
+    if name == "acon":
+        from tests.test_gpu_act_blocks import _swap_in_acon_and_frelu
+        m = ydl.SegYoloModel(dict(yaml, activation="nn.Mish()"))
+        _swap_in_acon_and_frelu(m)
+        return m
+    m = ydl.SegYoloModel(yaml, deformable=(name == "dcn"))
+    for sub in m.modules():                  # CNBlock, MBConv: under a recorder the keep draw of stochastic depth is refused
+        if getattr(sub, "stochastic_depth_prob", 0.0):
+            sub.stochastic_depth_prob = 0.0
+    return m
 
 
 def _yaml_setup(name, freeze=False):
@@ -28,7 +51,8 @@ def _yaml_setup(name, freeze=False):
     the middle block (SPPCSPC_group / C3x) frozen"""
     import yolo_dual_amd as ydl
     torch.manual_seed(11)
-    m = ydl.SegYoloModel(importlib.import_module(f"tests.test_builders_{name}_cpu").YAML)
+    m = _yaml_model(name)
+    side = VARIANTS[name][2] if name in VARIANTS else YAMLS[name]
     if freeze:
         for p in m.model[2].parameters():
             p.requires_grad_(False)
@@ -37,7 +61,7 @@ def _yaml_setup(name, freeze=False):
     crit = ydl.SegmentationLoss(12, 0.0, torch.ones(12), "dice", sync=False)
     gen = torch.Generator("cuda").manual_seed(3)
     xs = [torch.rand(2, 3, 32, 32, device="cuda", generator=gen) for _ in range(2)]
-    ts = [torch.randint(0, 12, (2, YAMLS[name], YAMLS[name]), device="cuda", generator=gen) for _ in range(2)]
+    ts = [torch.randint(0, 12, (2, side, side), device="cuda", generator=gen) for _ in range(2)]
     return m, opt, crit, xs, ts
 
 
@@ -51,7 +75,7 @@ def _model_setup(name, n, size):
     if name == "ResNet50Seg":
         m, out = ydl.ResNet50Seg({"nc": 12}), 640           # its head resizes to 640 x 640 whatever the input
     else:
-        m = getattr(ydl, name)(bench.load_cfg(wl["yaml"], wl["swap"]))
+        m = getattr(ydl, wl["model"])(bench.load_cfg(wl["yaml"], wl["swap"]))
         m.img_size = [size, size]
     sd = m.state_dict()
     fill_state_dict(sd, 1234, bn_stats=False)
@@ -71,6 +95,10 @@ for _n in YAMLS:
     CASES[f"{_n}-bf16"] = (_yaml_setup, (_n,), "bf16", {}, False)
     CASES[f"{_n}-f32"] = (_yaml_setup, (_n,), "f32", {}, False)
     CASES[f"{_n}-bf16-rows"] = (_yaml_setup, (_n,), "bf16", {"set_bn_sums": (False, True)}, False)
+    CASES[f"{_n}-eval"] = (_yaml_setup, (_n,), "bf16", {}, True)
+for _n in VARIANTS:
+    CASES[f"{_n}-bf16"] = (_yaml_setup, (_n,), "bf16", {}, False)
+    CASES[f"{_n}-f32"] = (_yaml_setup, (_n,), "f32", {}, False)
     CASES[f"{_n}-eval"] = (_yaml_setup, (_n,), "bf16", {}, True)
 for _n in ("gconv", "cross"):
     CASES[f"{_n}-bf16-frozen"] = (_yaml_setup, (_n, True), "bf16", {}, False)
@@ -165,7 +193,9 @@ def test_fixture_holds_every_family():
     used = [fx["ops"][i] for i in sorted({i for parts in fx["cases"].values() for idx in parts.values() for i in idx})]
     names = _names(used)
     need = {"ydl_dwconv2_fwd", "ydl_dwconv_wgrad", "ydl_dwconv2_wgrad", "ydl_gconv_wgrad", "ydl_xconv_dgrad", "ydl_resize_fwd",
-            "ydl_resize_bwd", "ydl_bn_act_fwd_p", "ydl_bn_finalize", "ydl_conv_dgrad_bnred"}
+            "ydl_resize_bwd", "ydl_bn_act_fwd_p", "ydl_bn_finalize", "ydl_conv_dgrad_bnred", "ydl_ln_bwd", "ydl_bias_gelu_bwd",
+            "ydl_scale_res_bwd", "ydl_se_excite_bwd", "ydl_se_scale_bwd", "ydl_local_attn_bwd", "ydl_mha_bwd", "ydl_deform_bwd",
+            "ydl_dcnv3_bwd", "ydl_acon_bwd", "ydl_max2_bwd", "ydl_space_to_depth", "ydl_depth_to_space", "ydl_group_softmax_bwd"}
     assert need <= names, sorted(need - names)
     for entry in ("ydl_resize_fwd", "ydl_resize_bwd"):           # the commuted conv-over-concat: bilinear, second argument
         assert any(op[0] == entry and op[2] == L.RESIZE_BILINEAR for op in used), entry

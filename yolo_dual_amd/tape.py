@@ -11,6 +11,7 @@ receive a gradient are skipped, which reproduces autograd's "grad is None" for t
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Callable, List, Optional, Sequence
 
 import torch
@@ -37,7 +38,7 @@ def _stream() -> ctypes.c_void_p:
 
 
 _SIDE = {}
-_NO_SLAB = __import__("os").environ.get("YDL_SLAB", "1") == "0"
+_NO_SLAB = os.environ.get("YDL_SLAB", "1") == "0"
 
 
 def side_stream(device) -> "torch.cuda.Stream":
@@ -57,6 +58,16 @@ def _p(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
 def _at(t: torch.Tensor, c0: int) -> ctypes.c_void_p:
     """``t`` from channel ``c0`` on: a per-channel row, or the (N,C,H,W) view of an NHWC buffer (c fastest)"""
     return ctypes.c_void_p(t.data_ptr() + c0 * t.element_size())
+
+
+def _blocks(t: torch.Tensor, n: int, C: int) -> List[ctypes.c_void_p]:
+    """the ``n`` channel blocks of ``C`` channels each that the rows of the NHWC buffer ``t`` hold side by side (Q | K | V ...)"""
+    return [_at(t, i * C) for i in range(n)]
+
+
+def _out_size(n: int, k: int, s: int, p: int, d: int = 1) -> int:
+    """output length of a convolution or pool along one axis: ``k`` taps of dilation ``d``, stride ``s``, padding ``p``"""
+    return (n + 2 * p - d * (k - 1) - 1) // s + 1
 
 
 def _bn_part(y: "Var", cf, c0: int):
@@ -299,6 +310,33 @@ class Tape:
     def new_like(self, v: Var) -> Var:
         return self.new(v.N, v.C, v.H, v.W, v.need, f32=(v.dt == L.YDL_F32))
 
+    def _flat(self, x: Var) -> Var:
+        """``x`` as a real tensor with 16-byte aligned rows: materialised, and an odd channel slice staged through a buffer of its own"""
+        x = self.materialize(x)
+        if not x.aligned():
+            x = self.copy(x, self.new_like(x))
+        return x
+
+    def _out(self, who: str, shape, out: Optional[Var], need: bool = True, f32: bool = False, aligned: bool = False) -> Var:
+        """where the op ``who`` writes its (N, C, H, W) = ``shape`` result: a fresh buffer (``need``, ``f32`` as in ``new``), or the
+        caller's ``out`` (typically a concat slice) once its shape has been checked, and its 16-byte alignment where the kernels
+        need it (``aligned``)"""
+        if out is None:
+            return self.new(*shape, need=need, f32=f32)
+        if (out.N, out.C, out.H, out.W) != tuple(shape) or (aligned and not out.aligned()):
+            raise RuntimeError(f"{who}: the output slice has the wrong shape" + (" or is not 16-byte aligned" if aligned else ""))
+        return out
+
+    def _ws(self, nbytes: int, keep: bool = False) -> torch.Tensor:
+        """an uninitialised f32 workspace of ``nbytes`` bytes.  The lifetime rule of every scratch buffer of the tape: one used only
+        by launches on the stream it was allocated under needs no ``keep``, because the caching allocator orders the reuse of its
+        memory on that stream.  Anything a launch on the side stream reads or writes (deferred weight gradients, the dead head
+        branch) goes into ``_keep``, which ``run_backward`` clears only after it has joined the streams."""
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+        if keep:
+            self._keep.append(ws)
+        return ws
+
     def _gbuf(self, v: Var) -> torch.Tensor:
         """gradient buffer of v (a slice shares its parent's buffer)"""
         v = v.root()
@@ -425,6 +463,58 @@ class Tape:
             acc = 1
         v.gset = True
         return g, acc
+
+    def _record(self, out: Var, bw: Callable[[], None], uses: Sequence[Optional[Var]] = ()) -> Var:
+        """the tail of a taped op, returning ``out``: when the tape records, note the inputs in ``uses`` whose gradient the backward
+        will write (``_use``; None and inputs nobody differentiates are skipped) and queue ``bw``, which runs only if ``out`` has
+        received a gradient (a dead branch leaves its parameters' grad None)"""
+        if self.record:
+            for v in uses:
+                if v is not None and v.need:
+                    self._use(v)
+
+            def run():
+                if out.is_set():
+                    bw()
+            self.bw.append(run)
+        return out
+
+    def _grad_via(self, v: Var, launch: Callable[[Var], None], st, aside: Optional[Var] = None) -> None:
+        """d/dv from ``launch(dst)``, a pass that can only OVERWRITE its destination: straight into v's gradient when this is its
+        first write; otherwise into a buffer of its own (``aside``, or a fresh one), which ydl_copy2d then adds in.  When nobody
+        wants d/dv the pass still runs (it forms parameter sums too) and its output is dropped."""
+        g, acc = self.grad_target(v) if v.need else (None, 1)
+        if not acc:
+            launch(Var(self, g, v.ld, False))
+            return
+        tmp = self.new_like(v) if aside is None else aside
+        launch(tmp)
+        if v.need:
+            L.call("ydl_copy2d", v.dt, _p(tmp.t), tmp.ld, _p(g), v.ld, v.npix, v.C, 1, st)
+
+    def _grad_or_scratch(self, v: Var):
+        """(buffer, ld, accumulate) for a launch that always writes d/dv: v's gradient, or a scratch tensor when nobody wants it"""
+        if v.need:
+            g, acc = self.grad_target(v)
+            return g, v.ld, acc
+        s = self.new(v.N, v.C, v.H, v.W)
+        return s.t, s.ld, 0
+
+    # ------------------------------------------------------------------ per-channel parameters: gradient rows and reporting
+    @staticmethod
+    def _param_grad(p: torch.nn.Parameter, device) -> torch.Tensor:
+        """gradient row of a per-channel parameter; a frozen one gets a scratch row (the launch writes all its rows)"""
+        if not p.requires_grad:
+            return torch.empty(p.numel(), dtype=torch.float32, device=device)
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+        return p.grad
+
+    def _touch(self, *params) -> None:
+        """report parameters whose gradient launches are enqueued (the data-parallel hook may now reduce their bucket)"""
+        for p in params:
+            if p is not None and p.requires_grad:
+                _cfg.mark_touched(p)
 
     # ------------------------------------------------------------------ region boundary
     def input_nchw(self, x: torch.Tensor, lazy: bool = False) -> Var:
@@ -602,7 +692,7 @@ class Tape:
         gw, gb, accw = rows
         dout = self._gbuf(o)
         dres_t, dres_ld, rmode = self._res_grad(res, res_mode, o, dout)
-        ws = torch.empty(L.lib().ydl_bn_bwd_ws_bytes(npix, cp) // 4, dtype=torch.float32, device=self.device)
+        ws = self._ws(L.lib().ydl_bn_bwd_ws_bytes(npix, cp))
         L.call_act("ydl_bn_act_bwd", self.dt, _at(y.t, c0), y.ld, _p(dout), o.ld, _p(o.t), o.ld, _at(m.bn.weight, c0),
                    _at(cf["mean"], c0), _at(cf["invstd"], c0), _at(cf["scale"], c0), _at(cf["shift"], c0), rmode, act,
                    _at(dy.t, c0), dy.ld, _p(dres_t), dres_ld, _at(gw, c0), _at(gb, c0), accw, _p(ws), npix, cw, cp, st)
@@ -651,17 +741,15 @@ class Tape:
         if outs is None and out is not None and not out.aligned():
             tmp = self.conv_bn_act(x, m, s, p, act, None, res, res_mode)
             return self.copy(tmp, out)
-        Ho = (x.H + 2 * p - k) // s + 1
-        Wo = (x.W + 2 * p - k) // s + 1
+        Ho, Wo = _out_size(x.H, k, s, p), _out_size(x.W, k, s, p)
         y = self.new(x.N, Cout, Ho, Wo)
         if outs is None:
-            if out is None:
-                out = self.new(x.N, Cout, Ho, Wo)
+            fresh = out is None
+            out = self._out("conv_bn_act", (x.N, Cout, Ho, Wo), out)
+            if fresh:
                 out.rep = x.rep
                 if virt is None and not x.need and not any(m.trainable()) and (res is None or not res.need):
                     out.need = False      # frozen layer on a prefix that needs no gradient: consumers skip their dgrad into it
-            elif (out.N, out.C, out.H, out.W) != (x.N, Cout, Ho, Wo):
-                raise RuntimeError("conv_bn_act: output slice has the wrong shape")
             outs = [out]
         else:
             if sum(o.C for o in outs) != Cout or any(o.C % 8 or not o.aligned() for o in outs) or res is not None:
@@ -710,7 +798,7 @@ class Tape:
             else:
                 nbytes = L.lib().ydl_conv_fwd_stats_ws_bytes(gp, self.dt)
                 grid_m, block_m = L.lib().ydl_conv_fwd_grid_m(gp, self.dt), L.lib().ydl_conv_fwd_block_m(gp, self.dt)
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+            ws = self._ws(nbytes)
         ws_ptr = _p(sums if sums_mode else ws) if self.train else None
         fwd_entry = "ydl_conv_fwd_sums" if sums_mode else "ydl_conv_fwd"
         if subs is None:
@@ -828,8 +916,7 @@ class Tape:
         if res is not None:
             res = self._flat(res)
         k, s, p = m.k, m.s, m.p
-        Ho = (x.H + 2 * p - k) // s + 1
-        Wo = (x.W + 2 * p - k) // s + 1
+        Ho, Wo = _out_size(x.H, k, s, p), _out_size(x.W, k, s, p)
         out = self.new(x.N, m.c2, Ho, Wo)
         w, _wt = m._fused_weights(self)
         geom = L.ConvGeom(x.N, x.H, x.W, m.c1, Ho, Wo, m.c2, k, s, p, x.ld, out.ld, 0)
@@ -946,11 +1033,8 @@ class Tape:
 
     # ------------------------------------------------------------------ pooling / resize / copies
     def maxpool(self, x: Var, k: int, s: int, p: int, out: Optional[Var] = None) -> Var:
-        x = self.materialize(x)
-        Ho = (x.H + 2 * p - k) // s + 1
-        Wo = (x.W + 2 * p - k) // s + 1
-        if not x.aligned():
-            x = self.copy(x, self.new(x.N, x.C, x.H, x.W, need=x.need, f32=(x.dt == L.YDL_F32)))
+        x = self._flat(x)
+        Ho, Wo = _out_size(x.H, k, s, p), _out_size(x.W, k, s, p)
         if out is not None and not out.aligned():
             return self.copy(self.maxpool(x, k, s, p), out)
         if out is None:
@@ -960,15 +1044,14 @@ class Tape:
         L.call("ydl_maxpool_fwd", x.dt, _p(x.t), x.ld, _p(out.t), out.ld, _p(idx), x.N, x.H, x.W, Ho, Wo, x.C,
                k, s, p, _stream())
         if self.record:
-            self._use(x)
-            def bw():
-                if not out.is_set() or not x.need:
-                    return
+            self._use(x)              # (noted whether or not x wants a gradient, unlike ``_record``'s notes)
+
+        def bw():
+            if x.need:
                 gx, acc = self.grad_target(x)
                 L.call("ydl_maxpool_bwd", x.dt, _p(self._gbuf(out)), out.ld, _p(idx), _p(gx), x.ld, acc,
                        x.N, x.H, x.W, Ho, Wo, x.C, k, s, p, _stream())
-            self.bw.append(bw)
-        return out
+        return self._record(out, bw)
 
     def sppf_pools(self, x: Var, k: int, outs: Sequence[Var]) -> Sequence[Var]:
         """SPPF's chain y1 = mp(x), y2 = mp(y1), y3 = mp(y2) (k x k, stride 1, pad k//2; seg_diceloss_yolov5.py:468-481) into the
@@ -976,41 +1059,24 @@ class Tape:
         (ydl_sppf_pool_fwd / _bwd, bit-identical to the chain), otherwise three ``maxpool`` calls."""
         o1, o2, o3 = outs
         x = self.materialize(x)
-        fused = (k % 2 == 1 and x.aligned() and all(o.aligned() and o.ld == o1.ld and o.dt == x.dt for o in outs)
-                 and all((o.N, o.C, o.H, o.W) == (x.N, x.C, x.H, x.W) for o in outs)
-                 and L.lib().ydl_sppf_pool_supported(x.dt, x.H, x.W, x.C, k))
-        if not fused:
+
+        def chain_bw(idx, st):
+            # a slice without a gradient (dead consumer): the chain link by link, as three maxpool closures would run it
+            for src, dst, ix in ((o2, o3, idx[2]), (o1, o2, idx[1]), (x, o1, idx[0])):
+                if not dst.is_set() or not src.need:
+                    continue
+                gx, acc = self.grad_target(src)
+                L.call("ydl_maxpool_bwd", x.dt, _p(self._gbuf(dst)), dst.ld, _p(ix), _p(gx), src.ld, acc,
+                       x.N, x.H, x.W, x.H, x.W, x.C, k, 1, k // 2, st)
+        idx = self._pools3("ydl_sppf_pool", x, outs, [k], chain_bw) if k % 2 == 1 else None
+        if idx is None:
             s1 = self.maxpool(x, k, 1, k // 2, out=o1)
             s2 = self.maxpool(s1, k, 1, k // 2, out=o2)
             s3 = self.maxpool(s2, k, 1, k // 2, out=o3)
             return s1, s2, s3
-        Cp = round_up(x.C, 4 if x.dt == L.YDL_F32 else 8)
-        n = x.N * x.H * x.W * Cp
-        idx = [torch.empty((n,), dtype=torch.uint8, device=self.device) for _ in range(3)] if self.record else [None] * 3
-        L.call("ydl_sppf_pool_fwd", x.dt, _p(x.t), x.ld, _p(o1.t), _p(o2.t), _p(o3.t), o1.ld, _p(idx[0]), _p(idx[1]), _p(idx[2]),
-               x.N, x.H, x.W, x.C, k, _stream())
-        if self.record:
-            self._use(x)
-            hook = _cfg.sppf_argmax_hook()
-            if hook is not None:          # test instrument: read or replace the three arg-max planes the backward will route by
-                hook(idx)
-
-            def bw():
-                st = _stream()
-                if all(o.is_set() for o in outs) and x.need:
-                    g1, g2, g3 = (self._gbuf(o) for o in outs)
-                    gx, acc = self.grad_target(x)
-                    L.call("ydl_sppf_pool_bwd", x.dt, _p(g1), _p(g2), _p(g3), o1.ld, _p(idx[0]), _p(idx[1]), _p(idx[2]),
-                           _p(gx), x.ld, acc, x.N, x.H, x.W, x.C, k, st)
-                    return
-                # a slice without a gradient (dead consumer): the chain link by link, as three maxpool closures would run it
-                for src, dst, ix in ((o2, o3, idx[2]), (o1, o2, idx[1]), (x, o1, idx[0])):
-                    if not dst.is_set() or not src.need:
-                        continue
-                    gx, acc = self.grad_target(src)
-                    L.call("ydl_maxpool_bwd", x.dt, _p(self._gbuf(dst)), dst.ld, _p(ix), _p(gx), src.ld, acc,
-                           x.N, x.H, x.W, x.H, x.W, x.C, k, 1, k // 2, st)
-            self.bw.append(bw)
+        hook = _cfg.sppf_argmax_hook()
+        if self.record and hook is not None:          # test instrument: read or replace the three arg-max planes the backward will route by
+            hook(idx)
         return o1, o2, o3
 
     def spp_pools(self, x: Var, ks: Sequence[int], outs: Sequence[Var]) -> Sequence[Var]:
@@ -1022,48 +1088,53 @@ class Tape:
         if len(ks) != len(outs):
             raise ValueError(f"spp_pools: {len(ks)} window sizes for {len(outs)} destinations")
         x = self.materialize(x)
-        fused = (len(ks) == 3 and x.aligned() and all(o.aligned() and o.ld == outs[0].ld and o.dt == x.dt for o in outs)
-                 and all((o.N, o.C, o.H, o.W) == (x.N, x.C, x.H, x.W) for o in outs)
-                 and L.lib().ydl_spp_pool_supported(x.dt, x.H, x.W, x.C, *ks))
-        if not fused:
+
+        def each_bw(idx, st):
+            # a slice without a gradient (dead consumer): pool by pool, in the order the fused kernel sums them
+            for k, dst, ix in zip(ks, outs, idx):
+                if not dst.is_set() or not x.need:
+                    continue
+                gx, acc = self.grad_target(x)
+                L.call("ydl_maxpool_bwd", x.dt, _p(self._gbuf(dst)), dst.ld, _p(ix), _p(gx), x.ld, acc,
+                       x.N, x.H, x.W, x.H, x.W, x.C, k, 1, k // 2, st)
+        if len(ks) != 3 or self._pools3("ydl_spp_pool", x, outs, ks, each_bw) is None:
             x = self._flat(x)
             return tuple(self.maxpool(x, k, 1, k // 2, out=o) for k, o in zip(ks, outs))
-        o1, o2, o3 = outs
+        return tuple(outs)
+
+    def _pools3(self, entry: str, x: Var, outs: Sequence[Var], ks: Sequence[int], part_bw) -> Optional[list]:
+        """what ``sppf_pools`` (``entry`` "ydl_sppf_pool", ks = [k]) and ``spp_pools`` ("ydl_spp_pool", three ks) share, the one-launch
+        form of three stride-1 pools into three destinations: None when x, the destinations or the plane do not qualify; otherwise
+        the fused forward launch with its three arg-max planes (returned) and a backward that is the one fused launch when every
+        destination holds a gradient and x wants one, and else ``part_bw(planes, stream)``, the caller's own pool-wise order"""
+        o1 = outs[0]
+        if not (x.aligned() and all(o.aligned() and o.ld == o1.ld and o.dt == x.dt for o in outs)
+                and all((o.N, o.C, o.H, o.W) == (x.N, x.C, x.H, x.W) for o in outs)
+                and getattr(L.lib(), entry + "_supported")(x.dt, x.H, x.W, x.C, *ks)):
+            return None
         Cp = round_up(x.C, 4 if x.dt == L.YDL_F32 else 8)
         n = x.N * x.H * x.W * Cp
         idx = [torch.empty((n,), dtype=torch.uint8, device=self.device) for _ in range(3)] if self.record else [None] * 3
-        L.call("ydl_spp_pool_fwd", x.dt, _p(x.t), x.ld, _p(o1.t), _p(o2.t), _p(o3.t), o1.ld, _p(idx[0]), _p(idx[1]), _p(idx[2]),
-               x.N, x.H, x.W, x.C, *ks, _stream())
+        L.call(entry + "_fwd", x.dt, _p(x.t), x.ld, *[_p(o.t) for o in outs], o1.ld, *[_p(i) for i in idx], x.N, x.H, x.W, x.C, *ks,
+               _stream())
         if self.record:
             self._use(x)
 
             def bw():
-                if not x.need:
-                    return
                 st = _stream()
-                if all(o.is_set() for o in outs):
-                    g1, g2, g3 = (self._gbuf(o) for o in outs)
-                    gx, acc = self.grad_target(x)
-                    L.call("ydl_spp_pool_bwd", x.dt, _p(g1), _p(g2), _p(g3), o1.ld, _p(idx[0]), _p(idx[1]), _p(idx[2]),
-                           _p(gx), x.ld, acc, x.N, x.H, x.W, x.C, *ks, st)
-                    return
-                # a slice without a gradient (dead consumer): pool by pool, in the order the fused kernel sums them
-                for k, dst, ix in zip(ks, outs, idx):
-                    if not dst.is_set():
-                        continue
-                    gx, acc = self.grad_target(x)
-                    L.call("ydl_maxpool_bwd", x.dt, _p(self._gbuf(dst)), dst.ld, _p(ix), _p(gx), x.ld, acc,
-                           x.N, x.H, x.W, x.H, x.W, x.C, k, 1, k // 2, st)
+                if not (all(o.is_set() for o in outs) and x.need):
+                    return part_bw(idx, st)
+                gs = [_p(self._gbuf(o)) for o in outs]
+                gx, acc = self.grad_target(x)
+                L.call(entry + "_bwd", x.dt, *gs, o1.ld, *[_p(i) for i in idx], _p(gx), x.ld, acc, x.N, x.H, x.W, x.C, *ks, st)
             self.bw.append(bw)
-        return o1, o2, o3
+        return idx
 
     def resize(self, x: Var, Ho: int, Wo: int, mode: int, scale_h: float = 0.0, scale_w: float = 0.0,
                out: Optional[Var] = None) -> Var:
         """mode: L.RESIZE_NEAREST / RESIZE_BILINEAR (align_corners=False) / RESIZE_BILINEAR_AC (True) / RESIZE_BICUBIC (False) /
         RESIZE_BICUBIC_AC (True)."""
-        x = self.materialize(x)
-        if not x.aligned():
-            x = self.copy(x, self.new(x.N, x.C, x.H, x.W, need=x.need, f32=(x.dt == L.YDL_F32)))
+        x = self._flat(x)
         if out is not None and not out.aligned():
             return self.copy(self.resize(x, Ho, Wo, mode, scale_h, scale_w), out)
         if out is None:
@@ -1073,50 +1144,40 @@ class Tape:
         fwd, bwd, arg = ("ydl_bicubic_fwd", "ydl_bicubic_bwd", int(mode == L.RESIZE_BICUBIC_AC)) if cubic else ("ydl_resize_fwd", "ydl_resize_bwd", mode)
         L.call(fwd, x.dt, arg, _p(x.t), x.ld, _p(out.t), out.ld, x.N, x.H, x.W, Ho, Wo, x.C,
                scale_h, scale_w, _stream())
-        if self.record:
-            def bw():
-                if not out.is_set() or not x.need:
-                    return
+
+        def bw():
+            if x.need:
                 gx, acc = self.grad_target(x)
                 L.call(bwd, x.dt, arg, _p(self._gbuf(out)), out.ld, _p(gx), x.ld, acc,
                        x.N, x.H, x.W, Ho, Wo, x.C, scale_h, scale_w, _stream())
-            self.bw.append(bw)
-        return out
+        return self._record(out, bw)
 
     def copy(self, x: Var, out: Var) -> Var:
         """out[:] = x (channel-slice aware); backward adds d(out) into d(x)."""
         if x.lazy or x.virtual:
             return self.materialize(x, out=out)
         L.call("ydl_copy2d", x.dt, _p(x.t), x.ld, _p(out.t), out.ld, x.npix, x.C, 0, _stream())
-        if self.record:
-            def bw():
-                if not out.is_set() or not x.need:
-                    return
+
+        def bw():
+            if x.need:
                 gx, acc = self.grad_target(x)
                 L.call("ydl_copy2d", x.dt, _p(self._gbuf(out)), out.ld, _p(gx), x.ld, x.npix, x.C, acc, _stream())
-            self.bw.append(bw)
-        return out
+        return self._record(out, bw)
 
     def add(self, a: Var, b: Var, out: Optional[Var] = None) -> Var:
         """out = a + b (element-wise, same shape); backward hands d(out) to both.  ``out`` may be a concat slice."""
         a, b = self._flat(a) if (a.lazy or a.virtual) else a, self._flat(b) if (b.lazy or b.virtual) else b
-        if out is None:
-            out = self.new(a.N, a.C, a.H, a.W, f32=(a.dt == L.YDL_F32))
-        elif (out.N, out.C, out.H, out.W) != (a.N, a.C, a.H, a.W):
-            raise RuntimeError("add: output slice has the wrong shape")
+        out = self._out("add", (a.N, a.C, a.H, a.W), out, f32=(a.dt == L.YDL_F32))
         st = _stream()
         L.call("ydl_copy2d", a.dt, _p(a.t), a.ld, _p(out.t), out.ld, a.npix, a.C, 0, st)
         L.call("ydl_copy2d", b.dt, _p(b.t), b.ld, _p(out.t), out.ld, b.npix, b.C, 1, st)
-        if self.record:
-            def bw():
-                if not out.is_set():
-                    return
-                for v in (a, b):
-                    if v.need:
-                        gv, acc = self.grad_target(v)
-                        L.call("ydl_copy2d", v.dt, _p(self._gbuf(out)), out.ld, _p(gv), v.ld, v.npix, v.C, acc, _stream())
-            self.bw.append(bw)
-        return out
+
+        def bw():
+            for v in (a, b):
+                if v.need:
+                    gv, acc = self.grad_target(v)
+                    L.call("ydl_copy2d", v.dt, _p(self._gbuf(out)), out.ld, _p(gv), v.ld, v.npix, v.C, acc, _stream())
+        return self._record(out, bw)
 
     # ------------------------------------------------------------------ space-to-depth / depth-to-space (csrc/s2d.hip)
     def _block_permute(self, x: Var, s: int, order: int, out: Optional[Var], down: bool) -> Var:
@@ -1136,23 +1197,18 @@ class Tape:
             if x.C % ss:
                 raise RuntimeError(f"{who}: {x.C} channels are not a multiple of s*s={ss}")
             C, shape = x.C // ss, (x.N, x.C // ss, x.H * s, x.W * s)
-        if out is None:
-            out = self.new(*shape, need=x.need, f32=(x.dt == L.YDL_F32))
-        elif (out.N, out.C, out.H, out.W) != shape or out.dt != x.dt:
-            raise RuntimeError(f"{who}: output slice has the wrong shape")
+        out = self._out(who, shape, out, need=x.need, f32=(x.dt == L.YDL_F32))
+        if out.dt != x.dt:
+            raise RuntimeError(f"{who}: the output slice has the wrong dtype")
         fwd, bwd = ("ydl_space_to_depth", "ydl_depth_to_space") if down else ("ydl_depth_to_space", "ydl_space_to_depth")
         L.call(fwd, x.dt, _p(x.t), x.ld, _p(out.t), out.ld, x.N, x.H, x.W, C, s, order, 0, _stream())
-        if not self.record or not x.need:             # the external image: nothing upstream wants a gradient
+        if not x.need:                                # the external image: nothing upstream wants a gradient
             return out
-        self._use(x)
 
         def bw():
-            if not out.is_set():
-                return
             gx, acc = self.grad_target(x)
             L.call(bwd, x.dt, _p(self._gbuf(out)), out.ld, _p(gx), x.ld, out.N, out.H, out.W, C, s, order, acc, _stream())
-        self.bw.append(bw)
-        return out
+        return self._record(out, bw, uses=(x,))
 
     def space_to_depth(self, x: Var, s: int, order: int = 0, out: Optional[Var] = None) -> Var:
         """(N, C, H, W) -> (N, s*s*C, H/s, W/s): out channel blk*C + c of pixel (ho, wo) is x's channel c at (ho*s + sy, wo*s + sx), with
@@ -1175,16 +1231,13 @@ class Tape:
         C, cp, npix = x.C, round_up(x.C, 8), x.npix
         if C != m.bn.num_features:
             raise RuntimeError(f"BatchNorm2d input channel mismatch: got {C}, the layer has {m.bn.num_features}")
-        if out is None:
-            out = self.new(x.N, C, x.H, x.W)
-        elif (out.N, out.C, out.H, out.W) != (x.N, C, x.H, x.W):
-            raise RuntimeError("bn_act: output slice has the wrong shape")
+        out = self._out("bn_act", (x.N, C, x.H, x.W), out)
         st = _stream()
         cf = m.coeffs(self.device)
         if self.train:
             lib = L.lib()
             bm = lib.ydl_bn_stats_block_m()
-            ws = torch.empty(lib.ydl_bn_stats_ws_bytes(npix, C) // 4, dtype=torch.float32, device=self.device)
+            ws = self._ws(lib.ydl_bn_stats_ws_bytes(npix, C))
             L.call("ydl_bn_stats", self.dt, _p(x.t), x.ld, _p(ws), npix, C, st)
             self._bn_coeffs(m, cf, C, st, (ws, (npix + bm - 1) // bm, bm, npix, 1))
         else:
@@ -1194,32 +1247,17 @@ class Tape:
             return out
         if not self.train:
             raise RuntimeError("backward through eval-mode BatchNorm is not supported")
-        if x.need:
-            self._use(x)
 
         def bw():
-            if not out.is_set() or not (x.need or any(m.trainable()[1:])):
+            if not (x.need or any(m.trainable()[1:])):
                 return
             st2 = _stream()
-            gx, acc = self.grad_target(x) if x.need else (None, 1)
             # first writer of d/dx: the pass writes it in place; otherwise (or when nobody wants it) into a buffer of its own
-            dy = Var(self, gx, x.ld, False) if not acc else self.new(x.N, C, x.H, x.W)
-            self._bn_bwd_rows(m, x, cf, act, out, None, L.RES_NONE, dy, self._bn_grad_rows(m, cp), npix, C, cp, st2)
-            if x.need and acc:
-                L.call("ydl_copy2d", x.dt, _p(dy.t), dy.ld, _p(gx), x.ld, npix, C, 1, st2)
-        self.bw.append(bw)
-        return out
+            self._grad_via(x, lambda dy: self._bn_bwd_rows(m, x, cf, act, out, None, L.RES_NONE, dy, self._bn_grad_rows(m, cp), npix, C,
+                                                           cp, st2), st2)
+        return self._record(out, bw, uses=(x,))
 
     # ------------------------------------------------------------------ learnable activations (csrc/act.hip)
-    @staticmethod
-    def _param_grad(p: torch.nn.Parameter, device) -> torch.Tensor:
-        """gradient row of a per-channel parameter; a frozen one gets a scratch row (the launch writes all its rows)"""
-        if not p.requires_grad:
-            return torch.empty(p.numel(), dtype=torch.float32, device=device)
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
-
     def acon(self, z: Var, m, out: Optional[Var] = None) -> Var:
         """AconC behind a materialised BatchNorm output: out = d * sigmoid(beta * d) + p2 * z, d = (p1 - p2) * z, with ``m.p1``,
         ``m.p2``, ``m.beta`` of shape (1, C, 1, 1) (utils/activations.py).  The backward is one pass (ydl_acon_bwd): dz and the three
@@ -1228,38 +1266,21 @@ class Tape:
         if out is not None and not out.aligned():
             return self.copy(self.acon(z, m), out)
         C, cp, hw = z.C, round_up(z.C, 8), z.H * z.W
-        if out is None:
-            out = self.new(z.N, C, z.H, z.W)
-        elif (out.N, out.C, out.H, out.W) != (z.N, C, z.H, z.W):
-            raise RuntimeError("acon: output slice has the wrong shape")
+        out = self._out("acon", (z.N, C, z.H, z.W), out)
         ps = (m.p1, m.p2, m.beta)
         if any(p.numel() != C or not p.is_contiguous() or p.dtype != torch.float32 for p in ps):
             raise RuntimeError(f"acon: p1 / p2 / beta must be contiguous f32 rows of {C} channels")
         L.call("ydl_acon_fwd", self.dt, _p(z.t), z.ld, _p(ps[0]), _p(ps[1]), _p(ps[2]), 0, _p(out.t), out.ld, z.npix, hw, C, cp, _stream())
-        if not self.record:
-            return out
-        if z.need:
-            self._use(z)
 
         def bw():
-            if not out.is_set():
-                return
             st = _stream()
             g1, g2, gb = (self._param_grad(p, self.device) for p in ps)
-            ws = torch.empty(L.lib().ydl_acon_bwd_ws_bytes(z.npix, hw, 0, cp) // 4, dtype=torch.float32, device=self.device)
-            if z.need:
-                gz, acc = self.grad_target(z)
-                ldz = z.ld
-            else:                                   # nothing upstream wants dz: the pass still forms the parameter sums
-                scratch = self.new(z.N, C, z.H, z.W)
-                gz, acc, ldz = scratch.t, 0, scratch.ld
+            ws = self._ws(L.lib().ydl_acon_bwd_ws_bytes(z.npix, hw, 0, cp))
+            gz, ldz, acc = self._grad_or_scratch(z)   # (nothing upstream wants dz: the pass still forms the parameter sums)
             L.call("ydl_acon_bwd", self.dt, _p(z.t), z.ld, _p(self._gbuf(out)), out.ld, _p(ps[0]), _p(ps[1]), _p(ps[2]), 0,
                    _p(gz), ldz, acc, _p(g1), _p(g2), _p(gb), 1, _p(ws), z.npix, hw, C, cp, st)
-            for p in ps:
-                if p.requires_grad:
-                    _cfg.mark_touched(p)
-        self.bw.append(bw)
-        return out
+            self._touch(*ps)
+        return self._record(out, bw, uses=(z,))
 
     def max2(self, a: Var, b: Var, out: Optional[Var] = None) -> Var:
         """out = max(a, b) element-wise (FReLU's merge); the backward routes d(out) to the larger operand, half to each on a tie"""
@@ -1269,50 +1290,19 @@ class Tape:
         if out is not None and not out.aligned():
             return self.copy(self.max2(a, b), out)
         cp = round_up(a.C, 8)
-        if out is None:
-            out = self.new(a.N, a.C, a.H, a.W)
-        elif (out.N, out.C, out.H, out.W) != (a.N, a.C, a.H, a.W):
-            raise RuntimeError("max2: output slice has the wrong shape")
+        out = self._out("max2", (a.N, a.C, a.H, a.W), out)
         L.call("ydl_max2_fwd", self.dt, _p(a.t), a.ld, _p(b.t), b.ld, _p(out.t), out.ld, a.npix, cp, _stream())
-        if not self.record:
-            return out
-        for v in (a, b):
-            if v.need:
-                self._use(v)
 
         def bw():
-            if not out.is_set() or not (a.need or b.need):
+            if not (a.need or b.need):
                 return
             ga, acca = self.grad_target(a) if a.need else (None, 0)
             gb, accb = self.grad_target(b) if b.need else (None, 0)
             L.call("ydl_max2_bwd", self.dt, _p(a.t), a.ld, _p(b.t), b.ld, _p(self._gbuf(out)), out.ld, _p(ga), a.ld, acca,
                    _p(gb), b.ld, accb, a.npix, cp, _stream())
-        self.bw.append(bw)
-        return out
+        return self._record(out, bw, uses=(a, b))
 
     # ------------------------------------------------------------------ ConvNeXt pieces (csrc/convnext.hip)
-    def _touch(self, *params) -> None:
-        for p in params:
-            if p is not None and p.requires_grad:
-                _cfg.mark_touched(p)
-
-    def _cn_out(self, who: str, x: Var, out: Optional[Var]) -> Var:
-        if x.C % 8:
-            raise RuntimeError(f"{who}: {x.C} channels are not a multiple of 8")
-        if out is None:
-            return self.new(x.N, x.C, x.H, x.W)
-        if (out.N, out.C, out.H, out.W) != (x.N, x.C, x.H, x.W) or not out.aligned():
-            raise RuntimeError(f"{who}: the output slice has the wrong shape or is not 16-byte aligned")
-        return out
-
-    def _grad_or_scratch(self, v: Var):
-        """(buffer, ld, accumulate) for a launch that always writes d/dv: v's gradient, or a scratch tensor when nobody wants it"""
-        if v.need:
-            g, acc = self.grad_target(v)
-            return g, v.ld, acc
-        s = self.new(v.N, v.C, v.H, v.W)
-        return s.t, s.ld, 0
-
     def dw_conv(self, x: Var, m) -> Var:
         """plain depth-wise k x k convolution, stride 1, padding k // 2, no BatchNorm: ydl_dwconv2_fwd without its statistics rows.
         ``m`` holds the [C][k*k] master (``master_dw`` / ``grad_dw``); its bias, if any, belongs to the consumer
@@ -1321,25 +1311,18 @@ class Tape:
         C, k = x.C, m.k
         y = self.new(x.N, C, x.H, x.W)
         L.call("ydl_dwconv2_fwd", self.dt, _p(x.t), x.ld, _p(m.master_dw()), _p(y.t), y.ld, None, x.N, x.H, x.W, C, k, 1, _stream())
-        if not self.record:
-            return y
-        if x.need:
-            self._use(x)
 
         def bw():
-            if not y.is_set():
-                return
             st = _stream()
             dy = self._gbuf(y)
             if m.weight.requires_grad:
-                ws = torch.empty(L.lib().ydl_dwconv2_wgrad_ws_bytes(C, k) // 4, dtype=torch.float32, device=self.device)
+                ws = self._ws(L.lib().ydl_dwconv2_wgrad_ws_bytes(C, k))
                 L.call("ydl_dwconv2_wgrad", self.dt, _p(x.t), x.ld, _p(dy), y.ld, _p(m.grad_dw()), _p(ws), x.N, x.H, x.W, C, k, 1, st)
                 self._touch(m.weight)
             if x.need:
                 gx, acc = self.grad_target(x)
                 L.call("ydl_dwconv2_dgrad", self.dt, _p(dy), y.ld, _p(m.master_dw()), _p(gx), x.ld, acc, x.N, x.H, x.W, C, k, 1, st)
-        self.bw.append(bw)
-        return y
+        return self._record(y, bw, uses=(x,))
 
     def layer_norm(self, x: Var, m, pre_bias=None, out: Optional[Var] = None) -> Var:
         """LayerNorm over the channels of every pixel: out = (u - mean_c u) / sqrt(var_c u + m.eps) * m.weight + m.bias with
@@ -1352,58 +1335,40 @@ class Tape:
         ps = (m.weight, m.bias) + ((pre_bias,) if pre_bias is not None else ())
         if any(p.numel() != C or not p.is_contiguous() or p.dtype != torch.float32 for p in ps):
             raise RuntimeError(f"layer_norm: weight / bias / pre_bias must be contiguous f32 rows of {C} channels")
-        out = self._cn_out("layer_norm", x, out)
+        out = self._out("layer_norm", (x.N, C, x.H, x.W), out, aligned=True)
         stats = torch.empty((x.npix, 2), dtype=torch.float32, device=self.device) if self.record else None
         L.call("ydl_ln_fwd", self.dt, _p(x.t), x.ld, _p(pre_bias), _p(m.weight), _p(m.bias), float(m.eps), _p(out.t), out.ld, _p(stats),
                x.npix, C, _stream())
-        if not self.record:
-            return out
-        if x.need:
-            self._use(x)
 
         def bw():
-            if not out.is_set():
-                return
             gg, gb = self._param_grad(m.weight, self.device), self._param_grad(m.bias, self.device)
             gp = self._param_grad(pre_bias, self.device) if pre_bias is not None else None
-            ws = torch.empty(L.lib().ydl_ln_bwd_ws_bytes(x.npix, C) // 4, dtype=torch.float32, device=self.device)
+            ws = self._ws(L.lib().ydl_ln_bwd_ws_bytes(x.npix, C))
             gx, ldx, acc = self._grad_or_scratch(x)
             L.call("ydl_ln_bwd", self.dt, _p(x.t), x.ld, _p(pre_bias), _p(m.weight), _p(stats), _p(self._gbuf(out)), out.ld, _p(gx), ldx,
                    acc, _p(gg), _p(gb), _p(gp), _p(ws), x.npix, C, _stream())
             self._touch(*ps)
-        self.bw.append(bw)
-        return out
+        return self._record(out, bw, uses=(x,))
 
     def bias_gelu(self, z: Var, m) -> Var:
         """out = GELU(z + m.bias), the exact (erf) form; ``z`` is the output of the bias-free GEMM in front.  Backward: one pass
         (ydl_bias_gelu_bwd) gives dz and adds the bias gradient into ``m.bias.grad``."""
         z = self._flat(z)
         C, b = z.C, m.bias
-        if b.numel() != C or not b.is_contiguous() or b.dtype != torch.float32:
-            raise RuntimeError(f"bias_gelu: the bias must be a contiguous f32 row of {C} channels")
-        out = self._cn_out("bias_gelu", z, None)
+        if C % 8 or b.numel() != C or not b.is_contiguous() or b.dtype != torch.float32:
+            raise RuntimeError(f"bias_gelu: the bias must be a contiguous f32 row of {C} channels, a multiple of 8")
+        out = self.new(z.N, C, z.H, z.W)
         L.call("ydl_bias_gelu_fwd", self.dt, _p(z.t), z.ld, _p(b), _p(out.t), out.ld, z.npix, C, _stream())
-        if not self.record:
-            return out
-        if z.need:
-            self._use(z)
 
         def bw():
-            if not out.is_set():
-                return
             st = _stream()
-            dy = self._gbuf(out)
-            ws = torch.empty(L.lib().ydl_bias_gelu_bwd_ws_bytes(z.npix, C) // 4, dtype=torch.float32, device=self.device)
-            gz, acc = self.grad_target(z) if z.need else (None, 1)
+            dy = Var(self, self._gbuf(out), out.ld, False)
+            ws = self._ws(L.lib().ydl_bias_gelu_bwd_ws_bytes(z.npix, C))
             # first writer of d/dz: straight into it; otherwise in place over dy, then added (or dropped when nobody wants it)
-            dst, ldd = (gz, z.ld) if not acc else (dy, out.ld)
-            L.call("ydl_bias_gelu_bwd", self.dt, _p(z.t), z.ld, _p(b), _p(dy), out.ld, _p(dst), ldd, _p(self._param_grad(b, self.device)),
-                   _p(ws), z.npix, C, st)
-            if z.need and acc:
-                L.call("ydl_copy2d", z.dt, _p(dy), out.ld, _p(gz), z.ld, z.npix, C, 1, st)
+            self._grad_via(z, lambda dz: L.call("ydl_bias_gelu_bwd", self.dt, _p(z.t), z.ld, _p(b), _p(dy.t), dy.ld, _p(dz.t), dz.ld,
+                                                _p(self._param_grad(b, self.device)), _p(ws), z.npix, C, st), st, aside=dy)
             self._touch(b)
-        self.bw.append(bw)
-        return out
+        return self._record(out, bw, uses=(z,))
 
     def scale_residual(self, y: Var, m, keep: Optional[torch.Tensor], x: Var, gamma: Optional[torch.Tensor] = None) -> Var:
         """out = x + keep[n] * m.layer_scale[c] * y: the layer-scaled residual of a ConvNeXt block with the per-sample keep factors of
@@ -1412,46 +1377,33 @@ class Tape:
         (MBConv: ones; ``m`` is not read then and the row's gradient goes to a scratch row)."""
         y, x = self._flat(y), self._flat(x)
         C, hw, g = y.C, y.H * y.W, m.layer_scale if gamma is None else gamma
-        if (x.N, x.C, x.H, x.W) != (y.N, C, y.H, y.W):
-            raise RuntimeError("scale_residual: the branch and the residual differ in shape")
+        if C % 8 or (x.N, x.C, x.H, x.W) != (y.N, C, y.H, y.W):
+            raise RuntimeError(f"scale_residual: the branch ({C} channels, a multiple of 8) and the residual differ in shape")
         if g.numel() != C or not g.is_contiguous() or g.dtype != torch.float32:
             raise RuntimeError(f"scale_residual: layer_scale must be a contiguous f32 row of {C} channels")
         if keep is not None and (keep.numel() != y.N or keep.dtype != torch.float32 or not keep.is_contiguous()):
             raise RuntimeError(f"scale_residual: keep must hold {y.N} f32 factors")
-        out = self._cn_out("scale_residual", y, None)
+        out = self.new(y.N, C, y.H, y.W)
         L.call("ydl_scale_res_fwd", self.dt, _p(y.t), y.ld, _p(g), _p(keep), _p(x.t), x.ld, _p(out.t), out.ld, y.N, hw, C, _stream())
-        if not self.record:
-            return out
-        for v in (y, x):
-            if v.need:
-                self._use(v)
 
         def bw():
-            if not out.is_set():
-                return
             st = _stream()
             dout = self._gbuf(out)
-            ws = torch.empty(L.lib().ydl_scale_res_bwd_ws_bytes(y.N, hw, C) // 4, dtype=torch.float32, device=self.device)
-            gy, ldy, accy = self._grad_or_scratch(y)
-            if accy:                                    # another consumer wrote d/dy first: form ours aside, then add
-                tmp = self.new(y.N, C, y.H, y.W)
-                gy_, ldy = tmp.t, tmp.ld
-            else:
-                gy_ = gy
-            gx, accx = None, 0
-            if x.need and not self._alias_grad(x, out, dout):
-                gx, accx = self.grad_target(x)
-            dg = self._param_grad(g, self.device) if gamma is None else torch.empty(C, dtype=torch.float32, device=self.device)
-            L.call("ydl_scale_res_bwd", self.dt, _p(dout), out.ld, _p(y.t), y.ld, _p(g), _p(keep), _p(gy_), ldy, _p(gx), x.ld, accx,
-                   _p(dg), _p(ws), y.N, hw, C, st)
-            if accy:
-                L.call("ydl_copy2d", y.dt, _p(gy_), ldy, _p(gy), y.ld, y.npix, C, 1, st)
+            ws = self._ws(L.lib().ydl_scale_res_bwd_ws_bytes(y.N, hw, C))
+
+            def launch(dy: Var):
+                gx, accx = None, 0
+                if x.need and not self._alias_grad(x, out, dout):
+                    gx, accx = self.grad_target(x)
+                dg = self._param_grad(g, self.device) if gamma is None else torch.empty(C, dtype=torch.float32, device=self.device)
+                L.call("ydl_scale_res_bwd", self.dt, _p(dout), out.ld, _p(y.t), y.ld, _p(g), _p(keep), _p(dy.t), dy.ld, _p(gx), x.ld, accx,
+                       _p(dg), _p(ws), y.N, hw, C, st)
+            self._grad_via(y, launch, st)                # (another consumer wrote d/dy first: ours is formed aside, then added)
             if keep is not None:
                 self._keep.append(keep)
             if gamma is None:
                 self._touch(g)
-        self.bw.append(bw)
-        return out
+        return self._record(out, bw, uses=(y, x))
 
     # ------------------------------------------------------------------ squeeze-and-excitation (csrc/se.hip)
     def squeeze_excite(self, x: Var, m) -> Var:
@@ -1474,7 +1426,7 @@ class Tape:
             raise RuntimeError(f"squeeze_excite: fc1 / fc2 must be 1x1 convolutions {C} -> {Cs} -> {C} with contiguous f32 weights and biases")
         f32 = dict(dtype=torch.float32, device=self.device)
         S = lib.ydl_se_pool_splits(N, HW)
-        part = torch.empty(lib.ydl_se_pool_ws_bytes(N, HW, C) // 4, **f32)
+        part = self._ws(lib.ydl_se_pool_ws_bytes(N, HW, C))
         pooled, z, gate = torch.empty((3, N, C), **f32).unbind(0)
         h = torch.empty((N, Cs), **f32)
         st = _stream()
@@ -1482,13 +1434,9 @@ class Tape:
         L.call("ydl_se_excite_fwd", _p(part), S, _p(ps[0]), _p(ps[1]), _p(ps[2]), _p(ps[3]), m.act_code, m.gate_code, _p(pooled), _p(h),
                _p(z), _p(gate), N, HW, C, Cs, st)
         out = self.scale_channels(x, gate)
-        if not self.record:
-            return out
-        if x.need:
-            self._use(x)
 
         def bw():
-            if not out.is_set() or not (x.need or any(p.requires_grad for p in ps)):
+            if not (x.need or any(p.requires_grad for p in ps)):
                 return
             st2 = _stream()
             dout = self._gbuf(out)
@@ -1496,15 +1444,14 @@ class Tape:
             L.call("ydl_se_pool_fwd", self.dt, _p(dout), out.ld, _p(x.t), x.ld, _p(dgate), N, HW, C, st2)
             grads = [self._param_grad(p, self.device) if p.requires_grad else None for p in ps]
             dpooled = torch.empty((N, C), **f32)
-            ws = torch.empty(lib.ydl_se_excite_bwd_ws_bytes(N, C, Cs) // 4, **f32)
+            ws = self._ws(lib.ydl_se_excite_bwd_ws_bytes(N, C, Cs))
             L.call("ydl_se_excite_bwd", _p(dgate), S, _p(pooled), _p(h), _p(z), _p(ps[0]), _p(ps[2]), m.act_code, m.gate_code, _p(dpooled),
                    _p(grads[0]), _p(grads[1]), _p(grads[2]), _p(grads[3]), _p(ws), N, C, Cs, st2)
             self._touch(*ps)
             if x.need:
                 gx, acc = self.grad_target(x)
                 L.call("ydl_se_scale_bwd", self.dt, _p(dout), out.ld, _p(gate), _p(dpooled), _p(gx), x.ld, acc, N, HW, C, st2)
-        self.bw.append(bw)
-        return out
+        return self._record(out, bw, uses=(x,))
 
     def patch_conv(self, x: Var, m, out: Optional[Var] = None) -> Var:
         """patchify convolution, kernel = stride = ``m.patch``, no padding: ``space_to_depth(x, k, order=0)`` and the 1x1 ``conv_bias``
@@ -1567,17 +1514,16 @@ class Tape:
         out.rep = x.rep                                   # point-wise: stays lazy
         sn, sc, sh, sw = out.t.stride()
         L.call("ydl_softmax_fwd", x.dt, _p(x.t), x.ld, _p(out.t), sn, sc, sh, sw, x.N, x.H, x.W, x.C, 1, 1, _stream())
-        if self.record:
-            def bw():
-                if not out.is_set() or not x.need:
-                    return
-                dp = self._gbuf(out)
-                gx, acc = self.grad_target(x)
-                assert acc == 0, "softmax input must have a single consumer"
-                L.call("ydl_softmax_bwd", x.dt, _p(out.t), _p(dp), sn, sc, sh, sw, _p(gx), x.ld, x.N, x.H, x.W, x.C, 1, 1,
-                       _stream())
-            self.bw.append(bw)
-        return out
+
+        def bw():
+            if not x.need:
+                return
+            dp = self._gbuf(out)
+            gx, acc = self.grad_target(x)
+            assert acc == 0, "softmax input must have a single consumer"
+            L.call("ydl_softmax_bwd", x.dt, _p(out.t), _p(dp), sn, sc, sh, sw, _p(gx), x.ld, x.N, x.H, x.W, x.C, 1, 1,
+                   _stream())
+        return self._record(out, bw)
 
     def softmax_nchw(self, x: Var) -> torch.Tensor:
         """nn.Softmax(1) producing the region's external output directly: f32 NCHW contiguous (no extra pass).
@@ -1648,16 +1594,21 @@ class Tape:
         L.call("ydl_global_pool_fwd", x.dt, _p(x.t), x.ld, _p(avg.t), avg.ld, _p(mx.t), mx.ld, _p(amax), x.N, HW, x.C,
                _stream())
         out = avg if kind == "avg" else mx
-        if self.record:
-            def bw():
-                if not out.is_set() or not x.need:
-                    return
-                g = self._gbuf(out)
-                gx, acc = self.grad_target(x)
-                L.call("ydl_global_pool_bwd", x.dt, _p(g) if kind == "avg" else None, out.ld,
-                       _p(g) if kind == "max" else None, out.ld, _p(amax), _p(gx), x.ld, acc, x.N, HW, x.C, _stream())
-            self.bw.append(bw)
-        return out
+
+        def bw():
+            if not x.need:
+                return
+            g = self._gbuf(out)
+            gx, acc = self.grad_target(x)
+            L.call("ydl_global_pool_bwd", x.dt, _p(g) if kind == "avg" else None, out.ld,
+                   _p(g) if kind == "max" else None, out.ld, _p(amax), _p(gx), x.ld, acc, x.N, HW, x.C, _stream())
+        return self._record(out, bw)
+
+    def _scale_channels_bwd(self, x: Var, out: Var, gate: torch.Tensor, st) -> None:
+        """d x (+)= d out * gate[n, c], the backward of ``out = scale_channels(x, gate)`` for x (ydl_scale_channels has no accumulate
+        flag: ``_grad_via``)"""
+        self._grad_via(x, lambda dx: L.call("ydl_scale_channels", x.dt, _p(self._gbuf(out)), out.ld, _p(gate), _p(dx.t), dx.ld, x.N,
+                                            x.H * x.W, x.C, st), st)
 
     def gate_mul(self, x: Var, a: Var, b: Var) -> Var:
         """out = x * sigmoid(a + b) with a, b of shape (N, C, 1, 1) (GAM: the bilinear expansion of a 1x1 map is constant)"""
@@ -1665,36 +1616,17 @@ class Tape:
         gate = torch.empty((x.N, x.C), dtype=torch.float32, device=self.device)
         L.call("ydl_gate_fwd", x.dt, _p(a.t), a.ld, _p(b.t), b.ld, _p(gate), x.N, x.C, _stream())
         out = self.scale_channels(x, gate)
-        if self.record:
-            def bw():
-                if not out.is_set():
-                    return
-                dout = self._gbuf(out)
-                st = _stream()
-                HW = x.H * x.W
-                dgate = torch.empty((x.N, x.C), dtype=torch.float32, device=self.device)
-                L.call("ydl_channel_dot", x.dt, _p(dout), out.ld, _p(x.t), x.ld, _p(dgate), x.N, HW, x.C, st)
-                ga, acca = self.grad_target(a)
-                gb, accb = self.grad_target(b)
-                L.call("ydl_gate_bwd", x.dt, _p(gate), _p(dgate), _p(ga), a.ld, acca, _p(gb), b.ld, accb, x.N, x.C, st)
-                if x.need:
-                    if x.is_set():
-                        tmp = self.new_like(x)
-                        L.call("ydl_scale_channels", x.dt, _p(dout), out.ld, _p(gate), _p(tmp.t), tmp.ld, x.N, HW, x.C, st)
-                        gx, acc = self.grad_target(x)
-                        L.call("ydl_copy2d", x.dt, _p(tmp.t), tmp.ld, _p(gx), x.ld, x.npix, x.C, 1, st)
-                    else:
-                        gx, _ = self.grad_target(x)
-                        L.call("ydl_scale_channels", x.dt, _p(dout), out.ld, _p(gate), _p(gx), x.ld, x.N, HW, x.C, st)
-            self.bw.append(bw)
-        return out
 
-    # ------------------------------------------------------------------ DCNv3 module pieces (NHWC is the tape's native layout)
-    def _flat(self, x: Var) -> Var:
-        x = self.materialize(x)
-        if not x.aligned():
-            x = self.copy(x, self.new(x.N, x.C, x.H, x.W, need=x.need, f32=(x.dt == L.YDL_F32)))
-        return x
+        def bw():
+            st = _stream()
+            dgate = torch.empty((x.N, x.C), dtype=torch.float32, device=self.device)
+            L.call("ydl_channel_dot", x.dt, _p(self._gbuf(out)), out.ld, _p(x.t), x.ld, _p(dgate), x.N, x.H * x.W, x.C, st)
+            ga, acca = self.grad_target(a)
+            gb, accb = self.grad_target(b)
+            L.call("ydl_gate_bwd", x.dt, _p(gate), _p(dgate), _p(ga), a.ld, acca, _p(gb), b.ld, accb, x.N, x.C, st)
+            if x.need:
+                self._scale_channels_bwd(x, out, gate, st)
+        return self._record(out, bw)
 
     # ------------------------------------------------------------------ depth-wise, grouped and cross Conv + BN + act
     def _side_bn_act(self, fam, x: Var, m, act: int, out: Optional[Var], res: Optional[Var], res_mode: int) -> Var:
@@ -1719,10 +1651,7 @@ class Tape:
             raise RuntimeError(f"{kind} input channel mismatch: got {x.C}, weight expects {m.c1}")
         Ho, Wo = size(x)
         y = self.new(x.N, Cout, Ho, Wo)
-        if out is None:
-            out = self.new(x.N, Cout, Ho, Wo)
-        elif (out.N, out.C, out.H, out.W) != (x.N, Cout, Ho, Wo):
-            raise RuntimeError(f"{who}: output slice has the wrong shape")
+        out = self._out(who, (x.N, Cout, Ho, Wo), out)
         st = _stream()
         w, wt = weights()
         cf = m.coeffs(self.device)
@@ -1734,7 +1663,7 @@ class Tape:
             raise RuntimeError(f"{who}: " + (L.lib().ydl_last_error() or b"?").decode())
         if self.train:
             nbytes, bm = stats(gp, npix)
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+            ws = self._ws(nbytes)
             fwd(gp, x, w, y, _p(ws), st)
             self._bn_coeffs(m, cf, Cout, st, (ws, (npix + bm - 1) // bm, bm, npix, 1))
         else:
@@ -1745,15 +1674,9 @@ class Tape:
             return out
         if not self.train:
             raise RuntimeError("backward through eval-mode BatchNorm is not supported")
-        if x.need:
-            self._use(x)
-        if res is not None and res.need and res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT):
-            self._use(res)
         self._keep.append(geom)         # the ctypes struct outlives the enqueue
 
         def bw():
-            if not out.is_set():
-                return
             st2 = _stream()
             dy = self.new(x.N, Cout, Ho, Wo)
             self._bn_bwd_rows(m, y, cf, act, out, res, res_mode, dy, self._bn_grad_rows(m, cp), npix, Cout, cp, st2)
@@ -1762,12 +1685,11 @@ class Tape:
             self._keep.append(gb_)
             if m.trainable()[0]:
                 wgrad(gpb, x, dy, m.grad_dw(), st2)
-                _cfg.mark_touched(m.conv.weight)
+                self._touch(m.conv.weight)
             if x.need:
                 gx, acc = self.grad_target(x)
                 dgrad(gpb, x, dy, wt, gx, acc, st2)
-        self.bw.append(bw)
-        return out
+        return self._record(out, bw, uses=(x, res if res_mode in (L.RES_BEFORE_ACT, L.RES_AFTER_ACT) else None))
 
     def _geom_family(self, entry: str, arg: int):
         """refuse, stats, fwd, wgrad, dgrad of ``_side_bn_act`` for the kernels that take a ConvGeom and one more integer (``entry`` =
@@ -1785,8 +1707,7 @@ class Tape:
             L.call(entry + "_fwd", gp, arg, self.dt, _p(x.t), _p(w), _p(y.t), ws, st)
 
         def wgrad(gp, x, dy, gk, st):                        # gk: KRSC [Cout][taps][Cin / groups], the kernel's dw layout
-            nws = max(getattr(lib, entry + "_wgrad_ws_bytes")(gp, arg, self.dt) // 4, 4)
-            ws = torch.empty(nws, dtype=torch.float32, device=self.device)
+            ws = self._ws(max(getattr(lib, entry + "_wgrad_ws_bytes")(gp, arg, self.dt), 16))
             L.call(entry + "_wgrad", gp, arg, self.dt, _p(x.t), _p(dy.t), _p(gk), _p(ws), st)
 
         def dgrad(gp, x, dy, wt, gx, acc, st):
@@ -1802,10 +1723,10 @@ class Tape:
         C, k, lib = m.c1, m.k, L.lib()
 
         def size(x):
-            return (x.H + 2 * (k // 2) - k) // s + 1, (x.W + 2 * (k // 2) - k) // s + 1
+            return _out_size(x.H, k, s, k // 2), _out_size(x.W, k, s, k // 2)
 
         def weights():
-            wm = m.master_dw()                                   # f32 [C][k*k]: both directions read the master
+            wm = m.master_dw()                                  # f32 [C][k*k]: both directions read the master
             return wm, wm
 
         def stats(gp, npix):
@@ -1818,7 +1739,7 @@ class Tape:
             # k = 3 at stride 1 (DCNv3's dw_conv) stays on the stride-1 entry point and its vectorised kernel until
             # ydl_dwconv2_wgrad has been measured against it at those shapes; its last argument is the padding, 1 like s
             wg = "ydl_dwconv_wgrad" if (k == 3 and s == 1) else "ydl_dwconv2_wgrad"
-            ws = torch.empty(getattr(lib, wg + "_ws_bytes")(C, k) // 4, dtype=torch.float32, device=self.device)
+            ws = self._ws(getattr(lib, wg + "_ws_bytes")(C, k))
             L.call(wg, self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws), x.N, x.H, x.W, C, k, s, st)
 
         def dgrad(gp, x, dy, wt, gx, acc, st):
@@ -1844,8 +1765,7 @@ class Tape:
         k, s, ax = m.k, m.s, m.axis
 
         def size(x):
-            Ho, Wo = ((n + 2 * (k // 2) - k) // s + 1 for n in (x.H, x.W))
-            return (Ho if ax == L.AXIS_H else x.H), (Wo if ax == L.AXIS_W else x.W)
+            return (_out_size(x.H, k, s, k // 2) if ax == L.AXIS_H else x.H), (_out_size(x.W, k, s, k // 2) if ax == L.AXIS_W else x.W)
         # weights: [Cout][k][Cin] and [Cin][k][Cout], ydl_weight_prep with kk = k
         fam = ("xconv_bn_act", "cross Conv", m.c2, k, s, size, lambda: m.compute_weights(self))
         return self._side_bn_act(fam + self._geom_family("ydl_xconv", ax), x, m, act, out, res, res_mode)
@@ -1856,15 +1776,21 @@ class Tape:
         assert x.C == G * P
         out = self.new(x.N, x.C, x.H, x.W)
         L.call("ydl_group_softmax_fwd", self.dt, _p(x.t), x.ld, _p(out.t), out.ld, x.npix, G, P, _stream())
-        if self.record:
-            def bw():
-                if not out.is_set() or not x.need:
-                    return
+
+        def bw():
+            if x.need:
                 gx, acc = self.grad_target(x)
                 L.call("ydl_group_softmax_bwd", self.dt, _p(out.t), out.ld, _p(self._gbuf(out)), out.ld, _p(gx), x.ld, acc,
                        x.npix, G, P, _stream())
-            self.bw.append(bw)
-        return out
+        return self._record(out, bw)
+
+    def _cast_grads(self, pairs, st) -> None:
+        """the tail of a backward whose kernel forms f32 gradients: (v, its dense f32 gradient or None) -> ydl_cast_f32 into (or added
+        to) d/dv in the compute dtype, for every v that wants one"""
+        for v, g32 in pairs:
+            if g32 is not None and v.need:
+                gv, acc = self.grad_target(v)
+                L.call("ydl_cast_f32", v.dt, _p(g32), g32.shape[-1], _p(gv), v.ld, v.npix, v.C, acc, st)
 
     def dcnv3(self, x: Var, offset: Var, mask: Var, k: int, s: int, pad: int, dil: int, G: int, Gc: int, scale: float) -> Var:
         """the deformable sampling op itself (ydl_dcnv3_fwd / _bwd; functions/dcnv3_func.py:19-61).  The op wants dense
@@ -1878,28 +1804,21 @@ class Tape:
             return buf
         xd, od, md = dense(x), dense(offset), dense(mask)
         N, H, W, C = xd.shape
-        Ho = (H + 2 * pad - (dil * (k - 1) + 1)) // s + 1
-        Wo = (W + 2 * pad - (dil * (k - 1) + 1)) // s + 1
+        Ho, Wo = _out_size(H, k, s, pad, dil), _out_size(W, k, s, pad, dil)
         out = self.new(N, C, Ho, Wo)
         assert out.ld == C, "DCNv3: channels must be a multiple of 8"
         L.call("ydl_dcnv3_fwd", self.dt, _p(xd), _p(od), _p(md), _p(out.t), k, k, s, s, pad, pad, dil, dil, G, Gc,
                ctypes.c_float(scale), N, H, W, Ho, Wo, _stream())
-        if self.record:
-            def bw():
-                if not out.is_set():
-                    return
-                st2 = _stream()
-                gin = zero_(torch.empty(xd.shape, dtype=torch.float32, device=self.device))
-                goff = torch.empty(od.shape, dtype=torch.float32, device=self.device)
-                gmsk = torch.empty(md.shape, dtype=torch.float32, device=self.device)
-                L.call("ydl_dcnv3_bwd", self.dt, _p(xd), _p(od), _p(md), _p(self._gbuf(out)), _p(gin), _p(goff), _p(gmsk),
-                       k, k, s, s, pad, pad, dil, dil, G, Gc, ctypes.c_float(scale), N, H, W, Ho, Wo, st2)
-                for v, g32 in ((x, gin), (offset, goff), (mask, gmsk)):
-                    if v.need:
-                        gv, acc = self.grad_target(v)
-                        L.call("ydl_cast_f32", v.dt, _p(g32), g32.shape[-1], _p(gv), v.ld, v.npix, v.C, acc, st2)
-            self.bw.append(bw)
-        return out
+
+        def bw():
+            st2 = _stream()
+            gin = zero_(torch.empty(xd.shape, dtype=torch.float32, device=self.device))
+            goff = torch.empty(od.shape, dtype=torch.float32, device=self.device)
+            gmsk = torch.empty(md.shape, dtype=torch.float32, device=self.device)
+            L.call("ydl_dcnv3_bwd", self.dt, _p(xd), _p(od), _p(md), _p(self._gbuf(out)), _p(gin), _p(goff), _p(gmsk),
+                   k, k, s, s, pad, pad, dil, dil, G, Gc, ctypes.c_float(scale), N, H, W, Ho, Wo, st2)
+            self._cast_grads(((x, gin), (offset, goff), (mask, gmsk)), st2)
+        return self._record(out, bw)
 
     def _conv_shift_fwd(self, gp, x: Var, w: torch.Tensor, out: Var, shift, st, act: int = L.ACT_NONE, res: Optional[Var] = None,
                         res_mode: int = L.RES_NONE) -> None:
@@ -1933,14 +1852,10 @@ class Tape:
         k, s, p = m.k, m.s, m.p
         if x.C != Cin:
             raise RuntimeError(f"{m._wname} input channel mismatch: got {x.C}, weight expects {Cin}")
-        Ho = (x.H + 2 * p - k) // s + 1
-        Wo = (x.W + 2 * p - k) // s + 1
+        Ho, Wo = _out_size(x.H, k, s, p), _out_size(x.W, k, s, p)
         w, wt = m.compute_weights(self)
-        if out is None:
-            out = self.new(x.N, Cout, Ho, Wo)
-        elif (out.N, out.C, out.H, out.W) != (x.N, Cout, Ho, Wo) or not out.aligned():
-            raise RuntimeError("conv_bias: the output slice has the wrong shape or is not 16-byte aligned")
-        geom = L.ConvGeom(x.N, x.H, x.W, Cin, Ho, Wo, Cout, k, s, p, x.ld, out.ld, 0)
+        out = self._out("conv_bias", (x.N, Cout, Ho, Wo), out, aligned=True)
+        geom =L.ConvGeom(x.N, x.H, x.W, Cin, Ho, Wo, Cout, k, s, p, x.ld, out.ld, 0)
         gp = ctypes.byref(geom)
         self._conv_shift_fwd(gp, x, w, out, m.bias_coeffs if (bias and m.bias is not None) else None, _stream())
         if self.record:
@@ -1958,26 +1873,14 @@ class Tape:
 
     def _bias_grad(self, m, dy: Var, st) -> None:
         """bias gradient of a transposed convolution: ydl_channel_sum over dy, added into ``m.bias.grad``"""
-        if m.bias is None or not m.bias.requires_grad:
-            return
-        if m.bias.grad is None:
-            m.bias.grad = torch.zeros_like(m.bias)
-        self._channel_sum_grad(dy, m.bias.grad, m.bias, st)
+        if m.bias is not None and m.bias.requires_grad:
+            self._channel_sum_grad(dy, self._param_grad(m.bias, self.device), m.bias, st)
 
     def _channel_sum_grad(self, dy: Var, grad: torch.Tensor, param, st) -> None:
         """grad += the per-channel sums of dy (ydl_channel_sum); ``param``: the parameter to report as written, or None"""
-        ws = torch.empty(L.lib().ydl_channel_sum_ws_bytes(dy.C) // 4, dtype=torch.float32, device=self.device)
+        ws = self._ws(L.lib().ydl_channel_sum_ws_bytes(dy.C), keep=True)
         L.call("ydl_channel_sum", self.dt, _p(dy.t), dy.ld, _p(grad), _p(ws), dy.npix, dy.C, 1, st)
-        self._keep.append(ws)
-        if param is not None:
-            _cfg.mark_touched(param)
-
-    def _tconv_out(self, x: Var, C2: int, out: Optional[Var], who: str) -> Var:
-        if out is None:
-            return self.new(x.N, C2, 2 * x.H, 2 * x.W)
-        if (out.N, out.C, out.H, out.W) != (x.N, C2, 2 * x.H, 2 * x.W) or not out.aligned():
-            raise RuntimeError(f"{who}: the output slice has the wrong shape or is not 16-byte aligned")
-        return out
+        self._touch(param)
 
     def conv_transpose(self, x: Var, m, out: Optional[Var] = None) -> Var:
         """``nn.ConvTranspose2d(c1, c2, k, 2, p, output_padding)`` in the forms that double the map (modules._TCONV_FORMS), with no new
@@ -1993,7 +1896,7 @@ class Tape:
         if x.C != c1:
             raise RuntimeError(f"ConvTranspose2d input channel mismatch: got {x.C}, weight expects {c1}")
         w, wt = m.compute_weights(self)
-        out = self._tconv_out(x, c2, out, "conv_transpose")
+        out = self._out("conv_transpose", (x.N, c2, 2 * x.H, 2 * x.W), out, aligned=True)
         geom = L.ConvGeom(x.N, out.H, out.W, c2, x.H, x.W, c1, m.k, 2, m.p, out.ld, x.ld, 0)
         gp = ctypes.byref(geom)
         st = _stream()
@@ -2001,23 +1904,17 @@ class Tape:
         if m.bias is not None:
             ones, bias = m.bias_coeffs(self.device)
             self._bn_apply(out, ones, bias, L.ACT_NONE, out, out.npix, round_up(out.C, 8), st)
-        if self.record:
-            if x.need:
-                self._use(x)
 
-            def bw():
-                if not out.is_set():
-                    return
-                st2 = _stream()
-                dy = Var(self, self._gbuf(out), out.ld, False)
-                self._bias_grad(m, dy, st2)
-                m.wgrad(self, gp, dy, x, st2)
-                if x.need:
-                    gx, acc = self.grad_target(x)
-                    L.call("ydl_conv_fwd", gp, self.dt, _p(dy.t), _p(w), _p(gx), None, acc, st2)
-                self._keep.append(geom)
-            self.bw.append(bw)
-        return out
+        def bw():
+            st2 = _stream()
+            dy = Var(self, self._gbuf(out), out.ld, False)
+            self._bias_grad(m, dy, st2)
+            m.wgrad(self, gp, dy, x, st2)
+            if x.need:
+                gx, acc = self.grad_target(x)
+                L.call("ydl_conv_fwd", gp, self.dt, _p(dy.t), _p(w), _p(gx), None, acc, st2)
+            self._keep.append(geom)
+        return self._record(out, bw, uses=(x,))
 
     def dw_conv_transpose(self, x: Var, m, out: Optional[Var] = None) -> Var:
         """``DWConvTranspose2d`` (models/common.py:73-76), depth-wise at stride 2 in the forms that double the map: the kernels of
@@ -2027,32 +1924,25 @@ class Tape:
         C, k, p, op = m.in_channels, m.k, m.p, m.op
         if x.C != C:
             raise RuntimeError(f"DWConvTranspose2d input channel mismatch: got {x.C}, weight expects {C}")
-        out = self._tconv_out(x, C, out, "dw_conv_transpose")
+        out = self._out("dw_conv_transpose", (x.N, C, 2 * x.H, 2 * x.W), out, aligned=True)
         wm = m.master_dw()
         st = _stream()
         L.call("ydl_dwtconv_fwd", self.dt, _p(x.t), x.ld, _p(wm), _p(m.bias.detach()) if m.bias is not None else None, _p(out.t), out.ld,
                x.N, x.H, x.W, C, k, p, op, st)
-        if self.record:
-            if x.need:
-                self._use(x)
 
-            def bw():
-                if not out.is_set():
-                    return
-                st2 = _stream()
-                dy = Var(self, self._gbuf(out), out.ld, False)
-                self._bias_grad(m, dy, st2)
-                if m.weight.requires_grad:
-                    gk = m.grad_dw()
-                    ws = torch.empty(L.lib().ydl_dwtconv_wgrad_ws_bytes(C, k) // 4, dtype=torch.float32, device=self.device)
-                    L.call("ydl_dwtconv_wgrad", self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws), x.N, x.H, x.W, C, k, p, op, st2)
-                    self._keep.append(ws)
-                    _cfg.mark_touched(m.weight)
-                if x.need:
-                    gx, acc = self.grad_target(x)
-                    L.call("ydl_dwtconv_dgrad", self.dt, _p(dy.t), dy.ld, _p(wm), _p(gx), x.ld, acc, x.N, x.H, x.W, C, k, p, op, st2)
-            self.bw.append(bw)
-        return out
+        def bw():
+            st2 = _stream()
+            dy = Var(self, self._gbuf(out), out.ld, False)
+            self._bias_grad(m, dy, st2)
+            if m.weight.requires_grad:
+                gk = m.grad_dw()
+                ws = self._ws(L.lib().ydl_dwtconv_wgrad_ws_bytes(C, k), keep=True)
+                L.call("ydl_dwtconv_wgrad", self.dt, _p(x.t), x.ld, _p(dy.t), dy.ld, _p(gk), _p(ws), x.N, x.H, x.W, C, k, p, op, st2)
+                self._touch(m.weight)
+            if x.need:
+                gx, acc = self.grad_target(x)
+                L.call("ydl_dwtconv_dgrad", self.dt, _p(dy.t), dy.ld, _p(wm), _p(gx), x.ld, acc, x.N, x.H, x.W, C, k, p, op, st2)
+        return self._record(out, bw, uses=(x,))
 
     def deform_conv(self, x: Var, offset: Var, mask: Optional[Var], m, gm, act: int, mask_sigmoid: bool = False,
                     out: Optional[Var] = None, res: Optional[Var] = None, res_mode: int = L.RES_NONE) -> Var:
@@ -2074,8 +1964,7 @@ class Tape:
         if G < 1 or offset.C != 2 * G * K or x.C % G or (mask is not None and mask.C != G * K):
             raise RuntimeError(f"DeformConv2d: offset has {offset.C} channels (2*G*{K} expected), mask "
                                f"{mask.C if mask is not None else None}")
-        Ho = (x.H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1
-        Wo = (x.W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+        Ho, Wo = _out_size(x.H, kh, sh, ph, dh), _out_size(x.W, kw, sw, pw, dw)
         if (offset.H, offset.W) != (Ho, Wo) or (mask is not None and (mask.H, mask.W) != (Ho, Wo)):
             raise RuntimeError("DeformConv2d: offset / mask resolution does not match the output")
         kc = gm.c1
@@ -2103,10 +1992,7 @@ class Tape:
                 L.call("ydl_deform_bwd", self.dt, _p(x.t), x.ld, _p(offset.t), offset.ld, _p(mask.t) if mask is not None else None,
                        mask.ld if mask is not None else 0, int(mask_sigmoid), _p(self._gbuf(col)), ld, _p(gin), _p(goff), _p(gmsk),
                        x.N, x.H, x.W, x.C, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, G, st2)
-                for v, g32 in ((x, gin), (offset, goff), (mask, gmsk)):
-                    if g32 is not None:
-                        gv, acc = self.grad_target(v)
-                        L.call("ydl_cast_f32", v.dt, _p(g32), g32.shape[-1], _p(gv), v.ld, v.npix, v.C, acc, st2)
+                self._cast_grads(((x, gin), (offset, goff), (mask, gmsk)), st2)
             self.bw.append(bw)
         gm.mark_step(self)
         return self.conv_bn_act(col, gm, 1, 0, act, out=out, res=res, res_mode=res_mode)
@@ -2149,21 +2035,7 @@ class Tape:
         """out = x * gate[n, c] with a constant ``gate`` (f32 [N][C], e.g. RFB's ``scale``); backward d x += d out * gate"""
         x = self.materialize(x)
         out = self.scale_channels(x, gate)
-        if self.record and x.need:
-            def bw():
-                if not out.is_set():
-                    return
-                st = _stream()
-                if x.is_set():
-                    tmp = self.new_like(x)
-                    L.call("ydl_scale_channels", x.dt, _p(self._gbuf(out)), out.ld, _p(gate), _p(tmp.t), tmp.ld, x.N, x.H * x.W, x.C, st)
-                    gx, acc = self.grad_target(x)
-                    L.call("ydl_copy2d", x.dt, _p(tmp.t), tmp.ld, _p(gx), x.ld, x.npix, x.C, 1, st)
-                else:
-                    gx, _ = self.grad_target(x)
-                    L.call("ydl_scale_channels", x.dt, _p(self._gbuf(out)), out.ld, _p(gate), _p(gx), x.ld, x.N, x.H * x.W, x.C, st)
-            self.bw.append(bw)
-        return out
+        return self._record(out, lambda: self._scale_channels_bwd(x, out, gate, _stream())) if x.need else out
 
     def local_attention(self, x: Var, mod) -> Var:
         """AttentionConv / AttentionStem (models/common.py:1509-1627): the bias-free 1x1 projections Q, K, V^0..V^{m-1} of x as
@@ -2181,12 +2053,10 @@ class Tape:
         N, H, W = x.N, x.H, x.W
         Cp = round_up(C, 8)
         st = _stream()
-        es = 4 if self.dt == L.YDL_F32 else 2
         qkv = self.new(N, len(projs) * Cp, H, W, zero=(Cp != C))
         geom = L.ConvGeom(N, H, W, Cin, H, W, C, 1, 1, 0, x.ld, qkv.ld, 0)
         gp = ctypes.byref(geom)
-        base = qkv.t.data_ptr()
-        blk = [ctypes.c_void_p(base + i * Cp * es) for i in range(len(projs))]
+        blk = _blocks(qkv.t, len(projs), Cp)
         wts = []
         for i, pr in enumerate(projs):
             w, wt = pr.compute_weights(self)
@@ -2199,39 +2069,31 @@ class Tape:
         lse = torch.empty((x.npix, Cp), dtype=torch.float32, device=self.device) if self.record else None
         L.call("ydl_local_attn_fwd", self.dt, blk[0], qkv.ld, blk[1], qkv.ld, blk[2], qkv.ld, Cp, m, rh, rw, _p(emb), _p(out.t), out.ld,
                _p(lse), N, H, W, C, ks, st)
-        if self.record:
-            if x.need:
-                self._use(x)
 
-            def bw():
-                if not out.is_set():
-                    return
-                st2 = _stream()
-                dqkv = self.new(N, len(projs) * Cp, H, W, need=False, zero=(Cp != C))
-                dbase = dqkv.t.data_ptr()
-                dblk = [ctypes.c_void_p(dbase + i * Cp * es) for i in range(len(projs))]
-                drh = drw = demb = ws = None
-                want_rel = rel is not None and (rel[0].requires_grad or rel[1].requires_grad)
-                want_tab = emb is not None and mod.table_trainable()
-                if want_rel:
-                    drh, drw = mod.grad_of(rel[0]), mod.grad_of(rel[1])
-                if want_tab:
-                    demb = torch.empty_like(emb)
-                if want_rel or want_tab:
-                    ws = torch.empty(L.lib().ydl_local_attn_bwd_ws_bytes(C, ks, m) // 4, dtype=torch.float32, device=self.device)
-                L.call("ydl_local_attn_bwd", self.dt, blk[0], qkv.ld, blk[1], qkv.ld, blk[2], qkv.ld, Cp, m, rh, rw, _p(emb),
-                       _p(out.t), out.ld, _p(lse), _p(self._gbuf(out)), out.ld, dblk[0], dblk[1], dblk[2], dqkv.ld, Cp, 0,
-                       _p(drh), _p(drw), _p(demb), _p(ws), N, H, W, C, ks, st2)
-                if want_rel:
-                    _cfg.mark_touched(rel[0])
-                    _cfg.mark_touched(rel[1])
-                if want_tab:
-                    mod.table_backward(self, emb, demb, st2)
-                for i, pr in enumerate(projs):
-                    self._conv_bias_bwd(pr, gp, x, Var(self, dqkv.t[:, i * Cp:i * Cp + C], dqkv.ld, False), wts[i], st2)
-                self._keep.extend((geom, qkv, dqkv, ws, demb))
-            self.bw.append(bw)
-        return out
+        def bw():
+            st2 = _stream()
+            dqkv = self.new(N, len(projs) * Cp, H, W, need=False, zero=(Cp != C))
+            dblk = _blocks(dqkv.t, len(projs), Cp)
+            drh = drw = demb = ws = None
+            want_rel = rel is not None and (rel[0].requires_grad or rel[1].requires_grad)
+            want_tab = emb is not None and mod.table_trainable()
+            if want_rel:
+                drh, drw = self._param_grad(rel[0], self.device), self._param_grad(rel[1], self.device)
+            if want_tab:
+                demb = torch.empty_like(emb)
+            if want_rel or want_tab:
+                ws = self._ws(L.lib().ydl_local_attn_bwd_ws_bytes(C, ks, m))
+            L.call("ydl_local_attn_bwd", self.dt, blk[0], qkv.ld, blk[1], qkv.ld, blk[2], qkv.ld, Cp, m, rh, rw, _p(emb),
+                   _p(out.t), out.ld, _p(lse), _p(self._gbuf(out)), out.ld, dblk[0], dblk[1], dblk[2], dqkv.ld, Cp, 0,
+                   _p(drh), _p(drw), _p(demb), _p(ws), N, H, W, C, ks, st2)
+            if want_rel:
+                self._touch(*rel)
+            if want_tab:
+                mod.table_backward(self, emb, demb, st2)
+            for i, pr in enumerate(projs):
+                self._conv_bias_bwd(pr, gp, x, Var(self, dqkv.t[:, i * Cp:i * Cp + C], dqkv.ld, False), wts[i], st2)
+            self._keep.extend((geom, qkv, dqkv, ws, demb))
+        return self._record(out, bw, uses=(x,))
 
     def mha(self, qkv: Var, heads: int) -> Var:
         """dense multi-head self-attention over the H*W positions of each sample (nn.MultiheadAttention's core, no mask, no
@@ -2245,10 +2107,8 @@ class Tape:
         if C % heads or d % 8 or not 8 <= d <= 128:
             raise NotImplementedError(f"mha: head dimension {C}/{heads} is not implemented (multiples of 8 between 8 and 128)")
         N, S = qkv.N, qkv.H * qkv.W
-        es = 4 if self.dt == L.YDL_F32 else 2
         scale = float(d) ** -0.5
-        base = qkv.t.data_ptr()
-        blk = [ctypes.c_void_p(base + i * C * es) for i in range(3)]
+        blk = _blocks(qkv.t, 3, C)
         out = self.new(N, C, qkv.H, qkv.W)
         lse = torch.empty(N * heads * S, dtype=torch.float32, device=self.device) if self.record else None
         L.call("ydl_mha_fwd", self.dt, blk[0], qkv.ld, blk[1], qkv.ld, blk[2], qkv.ld, _p(out.t), out.ld, _p(lse),
@@ -2258,13 +2118,12 @@ class Tape:
                 if not out.is_set():
                     return
                 st2 = _stream()
-                ws = torch.empty(L.lib().ydl_mha_bwd_ws_bytes(N, S, heads) // 4, dtype=torch.float32, device=self.device)
+                ws = self._ws(L.lib().ydl_mha_bwd_ws_bytes(N, S, heads), keep=True)
                 g, acc = self.grad_target(qkv)
-                gbase = g.data_ptr()
-                dblk = [ctypes.c_void_p(gbase + i * C * es) for i in range(3)]
+                dblk = _blocks(g, 3, C)
                 L.call("ydl_mha_bwd", self.dt, blk[0], qkv.ld, blk[1], qkv.ld, blk[2], qkv.ld, _p(out.t), out.ld, _p(lse),
                        _p(self._gbuf(out)), out.ld, dblk[0], dblk[1], dblk[2], qkv.ld, acc, _p(ws), N, S, heads, d, scale, st2)
-                self._keep.extend((ws, lse))
+                self._keep.append(lse)
             self.bw.append(bw)
         return out
 
